@@ -277,10 +277,14 @@ def build_workload(args, workload, rank, comm):
     if workload == "crossmodal":       # one 128-d VGGish-style vector per 1-s chunk (SURVEY 8d synthetic inputs)
         audio = torch.randn(B, 32, 128, generator=gen).to(torch.bfloat16).cuda()
 
+    kept = {}                                           # --dump-outputs: the step's logits (the graph's static tensor when captured)
+
     def fwd_bwd():
         flat.zero_grad()
         if workload in ("vivit", "longclip"):
-            loss, _ = net.loss(x, y)                    # BCEWithLogits(net(x), y), head + loss in one launch
+            loss, logits = net.loss(x, y)               # BCEWithLogits(net(x), y), head + loss in one launch
+            if args.dump_outputs:
+                kept["logits"] = logits
         elif workload == "frametransformer":
             loss = net.training_step((y, None, x), 0)
         else:
@@ -297,7 +301,30 @@ def build_workload(args, workload, rank, comm):
         update()
         return loss
 
-    return dict(cfg=cfg, cdt=cdt, B=B, net=net, flat=flat, step=step, fwd_bwd=fwd_bwd, update=update)
+    return dict(cfg=cfg, cdt=cdt, B=B, net=net, flat=flat, step=step, fwd_bwd=fwd_bwd, update=update, kept=kept)
+
+
+DUMP_SAMPLE = 1 << 22       # entries kept of the flat parameter / gradient buffers (2 x 16 MB of float32)
+
+
+def dump_outputs(W, loss, directory):
+    """What the timed path computed in its last step, as DIR/<name>.npy (float32): the returned loss, the logits (vivit /
+    longclip), and the flat fp32 gradients (after the exchange) and updated master weights -- all of them when they fit
+    DUMP_SAMPLE entries, else the same seeded sample of DUMP_SAMPLE sorted positions of each."""
+    import numpy as np
+    flat = W["flat"]
+    out = {"loss": loss.detach().float().reshape(1)}
+    if "logits" in W["kept"]:
+        out["logits"] = W["kept"]["logits"].detach().float()
+    if flat.total > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(1130).choice(flat.total, DUMP_SAMPLE, replace=False))
+        sel = torch.from_numpy(idx).to(flat.grad.device)
+        out["grad"], out["params"] = flat.grad[sel], flat.data[sel]
+    else:
+        out["grad"], out["params"] = flat.grad, flat.data
+    os.makedirs(directory, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(directory, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def collective_capture_ok(comm):
@@ -554,6 +581,8 @@ def run_workload(args, workload, rank, world, use_dist, comm, *, steps, warmup, 
     progress(f"{workload}: warm-up")
     elapsed, per_step, loss = timed_steps(run, steps, barrier)
     progress(f"{workload}: timed steps")
+    if args.dump_outputs and not secondary and rank == 0:      # before anything below runs the step or the optimizer again
+        dump_outputs(W, loss, args.dump_outputs)
     if use_dist:
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -792,7 +821,7 @@ def launch_ranks(args, argv):
         raise SystemExit(f"[bench] rank exit codes {rcs}; JSON line {'missing' if line is None else 'present'}")
     print(line, flush=True)
 
-DETAIL_DEFAULT = os.path.join("profiles", "r06_bench_detail.json")
+DETAIL_DEFAULT = os.path.join("profiles", "bench_detail.json")      # git-ignored: a run never rewrites a committed record
 LINE_LIMIT = 6000      # the driver keeps the last 8 KB of stdout: the ONE line must fit with room to spare
 
 
@@ -898,7 +927,7 @@ def compact_line(out):
 
 
 def emit(out, detail_path):
-    """Write the full record to the detail file (tracked under profiles/ when the run is the builder's own) and print the
+    """Write the full record to the detail file (git-ignored by default; a --detail-out under profiles/ keeps a record) and print the
     compact line, which names that file."""
     line = compact_line(out)
     if detail_path:
@@ -963,6 +992,9 @@ def main():
     ap.add_argument("--detail-out", default=DETAIL_DEFAULT, help="file (relative to the repository root) that receives the FULL "
                     "record -- per-family rooflines, per-kernel HBM rates, bucket timeline; the printed line is the compact form "
                     "and names this file; '' writes none")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one "
+                    "computed as DIR/<name>.npy (float32): loss, logits, and the flat gradients and updated weights (a fixed "
+                    "seeded sample of them when larger than 4 Mi entries), for output-for-output comparison of two builds")
     ap.add_argument("--rendezvous-only", action="store_true", help="launcher self-test (runs without a GPU): every rank joins "
                     "the process group, sums its rank over the group and rank 0 prints a JSON line with n_gpus = world")
     args = ap.parse_args()
