@@ -2179,3 +2179,71 @@ def dropout(x: Tensor, p: float, training: bool) -> Tensor:
     if p >= 1.0:
         raise ValueError("dropout p must be < 1")
     return _Dropout.apply(x, float(p))
+
+
+# ---------------------------------------------------------------------------
+# LSTM (src/models/LSTM.py): one nn.LSTM layer over a sequence, and the sigmoid -> BCELoss criterion
+# ---------------------------------------------------------------------------
+class _LstmLayer(torch.autograd.Function):
+    """One nn.LSTM(batch_first=True) layer: G = x W_ih^T on the GEMM, then the recurrent chain (biases and W_hh inside it).
+    Backward: the chain gives dG; dW_ih, dx, db on one linear_backward, dW_hh = dG^T h_prev on the weight-gradient GEMM."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh):
+        ctx.set_materialize_grads(False)
+        B, T, Fdim = x.shape
+        x2 = x.reshape(B * T, Fdim)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        wih, whh = _wc(w_ih, x.dtype), _wc(w_hh, x.dtype)
+        G = ops.linear_fwd(x2, wih)
+        h_out, h_prev, gates, c, h_last = ops.lstm_seq_fwd(G, whh, _f32(b_ih), _f32(b_hh), B, T, want_last=True)
+        ctx.save_for_backward(x2, wih, whh, h_prev, gates, c)
+        ctx.xshape = x.shape
+        return h_out, h_last
+
+    @staticmethod
+    def backward(ctx, dh_seq, dh_last):
+        x2, wih, whh, h_prev, gates, c = ctx.saved_tensors
+        if dh_seq is None and dh_last is None:
+            return None, None, None, None, None
+        if dh_seq is not None:
+            dh_seq = _as(dh_seq.contiguous(), whh.dtype)
+        if dh_last is not None:
+            dh_last = _as(dh_last.contiguous(), whh.dtype)
+        dG = ops.lstm_seq_bwd(whh, gates, c, dh_seq, dh_last)
+        H4 = dG.shape[1]
+        db = torch.empty((H4,), dtype=torch.float32, device=dG.device)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dw_ih, dx2 = ops.linear_backward(dG, x2, wih, bias_out=db)
+            dx = dx2.view(ctx.xshape)
+        else:
+            dw_ih = ops.linear_wgrad(dG, x2, bias_out=db)
+        dw_hh = ops.linear_wgrad(dG, h_prev.view(-1, h_prev.shape[-1]))
+        db_hh = ops.copy_(torch.empty_like(db), db)       # the two biases get equal gradients, in separate tensors
+        return dx, dw_ih, dw_hh, db, db_hh
+
+
+def lstm_layer(x: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Optional[Tensor], b_hh: Optional[Tensor]):
+    """One nn.LSTM(batch_first=True) layer on x [B, T, F] (compute dtype) -> (output [B, T, H], h_{T-1} [B, H])."""
+    return _LstmLayer.apply(x, w_ih, w_hh, b_ih, b_hh)
+
+
+class _SigmoidBce(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, target):
+        zc = z.contiguous()
+        t32 = _f32(target)
+        ctx.save_for_backward(zc, t32)
+        return ops.sigmoid_bce_fwd(zc, t32).view(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        zc, t32 = ctx.saved_tensors
+        return ops.sigmoid_bce_bwd(zc, t32, _f32(gloss).reshape(1)), None
+
+
+def sigmoid_bce(z: Tensor, target: Tensor) -> Tensor:
+    """nn.BCELoss()(torch.sigmoid(z), target): mean, each log term clamped at -100 (LSTM.py:55-57)."""
+    return _SigmoidBce.apply(z, target)

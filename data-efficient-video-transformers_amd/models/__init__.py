@@ -6,3 +6,5 @@ from . import frame_transformer, transformer  # noqa: F401,E402
 from .frame_transformer import FrameTransformer, TransformerBase, PositionalEncoding  # noqa: F401,E402
 from .transformer import SimpleTransformer  # noqa: F401,E402
 from . import custom_resnet, TPN  # noqa: F401,E402
+from . import LSTM  # noqa: F401,E402
+from .LSTM import LSTMRegressor  # noqa: F401,E402

@@ -906,6 +906,25 @@ def bce_logits_bwd(z: Tensor, target: Tensor, gloss: Tensor) -> Tensor:
     return dz
 
 
+def sigmoid_bce_fwd(z: Tensor, target: Tensor, want_prob: bool = False):
+    """nn.BCELoss()(sigmoid(z), target) (mean, log terms clamped at -100) -> loss [1] f32 (, sigmoid(z) f32)."""
+    _need_cuda(z, target)
+    assert z.is_contiguous() and target.is_contiguous() and target.dtype == torch.float32 and target.numel() == z.numel()
+    loss = torch.empty((1,), dtype=torch.float32, device=z.device)
+    prob = torch.empty(z.shape, dtype=torch.float32, device=z.device) if want_prob else None
+    L.check(L.load().dvt_sigmoid_bce_fwd(z.data_ptr(), target.data_ptr(), loss.data_ptr(), _p(prob), z.numel(), dt(z),
+                                         _stream()), "dvt_sigmoid_bce_fwd")
+    return (loss, prob) if want_prob else loss
+
+
+def sigmoid_bce_bwd(z: Tensor, target: Tensor, gloss: Tensor) -> Tensor:
+    _need_cuda(z, target, gloss)
+    dz = torch.empty_like(z)
+    L.check(L.load().dvt_sigmoid_bce_bwd(z.data_ptr(), target.data_ptr(), gloss.data_ptr(), dz.data_ptr(), z.numel(),
+                                         dt(z), _stream()), "dvt_sigmoid_bce_bwd")
+    return dz
+
+
 def ce_argmax_fwd(student: Tensor, teacher: Tensor) -> Tensor:
     _need_cuda(student, teacher)
     assert student.is_contiguous() and teacher.is_contiguous() and student.dtype == teacher.dtype
@@ -1909,3 +1928,44 @@ def transpose_last2(x: Tensor) -> Tensor:
     L.check(L.load().dvt_transpose_last2(x.data_ptr(), out.data_ptr(), B, R, Cc, dt(x), _stream()),
             "dvt_transpose_last2")
     return out
+
+
+# ------------------------------------------------------------------ LSTM recurrent chain
+def lstm_seq_fwd(G: Tensor, w_hh: Tensor, b_ih: Optional[Tensor], b_hh: Optional[Tensor], B: int, T: int,
+                 want_last: bool = False):
+    """The recurrent chain of one nn.LSTM layer (dvt_lstm_seq_fwd).  G [B*T, 4H] = x W_ih^T (no bias), w_hh [4H, H] in
+    G's dtype, biases f32.  -> (h_out [B, T, H], h_prev [B, T, H] (h shifted one step, zeros first), gates [B, T, 4H] f32,
+    c [B, T, H] f32, h_last [B, H] or None)."""
+    _need_cuda(G, w_hh, b_ih, b_hh)
+    H = w_hh.shape[1]
+    assert G.is_contiguous() and w_hh.is_contiguous() and w_hh.dtype == G.dtype and w_hh.shape == (4 * H, H)
+    assert G.numel() == B * T * 4 * H
+    for b in (b_ih, b_hh):
+        assert b is None or (b.dtype == torch.float32 and b.is_contiguous() and b.numel() == 4 * H)
+    dev = G.device
+    h_out = torch.empty((B, T, H), dtype=G.dtype, device=dev)
+    h_prev = torch.empty((B, T, H), dtype=G.dtype, device=dev)
+    gates = torch.empty((B, T, 4 * H), dtype=torch.float32, device=dev)
+    c = torch.empty((B, T, H), dtype=torch.float32, device=dev)
+    h_last = torch.empty((B, H), dtype=G.dtype, device=dev) if want_last else None
+    L.check(L.load().dvt_lstm_seq_fwd(G.data_ptr(), _p(b_ih), _p(b_hh), w_hh.data_ptr(), h_prev.data_ptr(),
+                                      h_out.data_ptr(), gates.data_ptr(), c.data_ptr(), _p(h_last), B, T, H, dt(G),
+                                      _stream()), "dvt_lstm_seq_fwd")
+    return h_out, h_prev, gates, c, h_last
+
+
+def lstm_seq_bwd(w_hh: Tensor, gates: Tensor, c: Tensor, dh_seq: Optional[Tensor], dh_last: Optional[Tensor]) -> Tensor:
+    """Backward through time of ``lstm_seq_fwd`` (dvt_lstm_seq_bwd) -> dG [B*T, 4H] in w_hh's dtype, the gradient of the
+    pre-activation gates."""
+    _need_cuda(w_hh, gates, c, dh_seq, dh_last)
+    B, T, H = c.shape
+    for t in (dh_seq, dh_last):
+        assert t is None or (t.dtype == w_hh.dtype and t.is_contiguous())
+    assert dh_seq is None or dh_seq.numel() == B * T * H
+    assert dh_last is None or dh_last.numel() == B * H
+    lib = L.load()
+    dG = torch.empty((B * T, 4 * H), dtype=w_hh.dtype, device=w_hh.device)
+    ws = workspace(lib.dvt_lstm_seq_bwd_workspace_bytes(B, H, dt(w_hh)), w_hh.device)
+    L.check(lib.dvt_lstm_seq_bwd(w_hh.data_ptr(), gates.data_ptr(), c.data_ptr(), _p(dh_seq), _p(dh_last),
+                                 dG.data_ptr(), _p(ws), B, T, H, dt(w_hh), _stream()), "dvt_lstm_seq_bwd")
+    return dG

@@ -877,6 +877,38 @@ int dvt_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n
 int dvt_adagrad_step(float* param, const float* grad, float* state_sum, int64_t n, float lr, float lr_decay,
                      float eps, float weight_decay, int64_t step, const uint8_t* skip64, dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- LSTM (the LSTMRegressor baseline)
+ * Additions within ABI v5: new entry points only, no existing layout or meaning changed.
+ * The recurrent chain of one nn.LSTM(batch_first=True) layer over a whole sequence (src/models/LSTM.py:32-38 builds it,
+ * :40-45 runs it), gate order i, f, g, o; h0 = c0 = 0.  The input projection G = x W_ih^T [B, T, 4H] (dtype, no bias)
+ * is computed before the call and the parameter / input gradients after the backward call, on the GEMM entry points;
+ * only h_{t-1} W_hh^T and the cell update are in the chain, one launch per step on `stream`.  Gates, c and dc are f32
+ * in every dtype; h and the gate gradients are dtype.  No atomics: two identical calls give bitwise-equal results.
+ * Limits: H a multiple of 16 (else DVT_ERR_UNSUPPORTED); dtype F32, BF16 or F16.
+ *
+ * Forward.  b_ih, b_hh [4H] f32 (either may be NULL); w_hh [4H, H] dtype.  Outputs: h_out [B, T, H] = h_t;
+ * h_prev [B, T, H] = h_{t-1} (zeros at t = 0: the operand of dW_hh = dG^T h_prev, and the chain's own input);
+ * gates [B, T, 4H] f32 = sigmoid(i), sigmoid(f), tanh(g), sigmoid(o); c [B, T, H] f32 = c_t; h_last [B, H] = h_{T-1}
+ * (NULL: not written). */
+int dvt_lstm_seq_fwd(const void* G, const float* b_ih, const float* b_hh, const void* w_hh, void* h_prev, void* h_out,
+                     float* gates, float* c, void* h_last, int64_t B, int64_t T, int64_t H, int dtype, dvt_stream_t stream);
+/* Backward through time (LSTM.py:32-38).  gates, c: the forward's outputs.  The gradient arriving at h_t is
+ * dh_seq[:, t] (dtype [B, T, H], NULL: none) plus, at t = T-1, dh_last (dtype [B, H], NULL: none); at least one is given.
+ * Output dG [B, T, 4H] dtype: the gradient of the pre-activation gates (= of G, of b_ih and of b_hh per row), from which
+ * dW_ih = dG^T x, dW_hh = dG^T h_prev, db = colsum(dG) and dx = dG W_ih are ordinary GEMMs.
+ * workspace: dvt_lstm_seq_bwd_workspace_bytes(B, H, dtype) bytes, 16-byte aligned. */
+size_t dvt_lstm_seq_bwd_workspace_bytes(int64_t B, int64_t H, int dtype);
+int dvt_lstm_seq_bwd(const void* w_hh, const float* gates, const float* c, const void* dh_seq, const void* dh_last,
+                     void* dG, void* workspace, int64_t B, int64_t T, int64_t H, int dtype, dvt_stream_t stream);
+/* The LSTMRegressor criterion nn.BCELoss()(torch.sigmoid(z), y) (LSTM.py:55-57), mean over n; each log term clamped at
+ * -100 as BCELoss does (this is not BCEWithLogits: a saturated logit gives loss 100, not its magnitude).
+ * z [n] dtype, target [n] f32, loss [1] f32, prob [n] f32 = sigmoid(z) (NULL: not written). */
+int dvt_sigmoid_bce_fwd(const void* z, const float* target, float* loss, float* prob, int64_t n, int dtype,
+                        dvt_stream_t stream);
+/* dz = gloss[0] / n * (p - y) / max(p (1 - p), 1e-12) * p (1 - p) with p = sigmoid(z): BCELoss's backward, then sigmoid's. */
+int dvt_sigmoid_bce_bwd(const void* z, const float* target, const float* gloss, void* dz, int64_t n, int dtype,
+                        dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- data-parallel gradient exchange
  * The reference is single-GPU (pl.Trainer(gpus=1), src/main.py:87); north_star partitions the clips of the global
  * batch over the 8 GPUs of a node, and the only exchange of the path is the SUM of the parameter gradients.  RCCL over

@@ -9,8 +9,9 @@ The reference's driver does ``from models.frame_transformer import FrameTransfor
 makes those imports resolve to the MI355X build, with ``main.py`` unchanged: the reference's own ``src/models`` has no
 ``__init__.py``, i.e. it is a namespace-package portion, and a regular package found anywhere on ``sys.path`` takes
 precedence over namespace portions -- also over the one in the script directory.  Modules the build does not replace
-(``models.LSTM`` main.py:13, ``basicmlp``, ``contrastivemodel``, ``pretrained``: out of scope, SURVEY section 2 rows
-8-11) keep resolving to the reference's files: every other ``models`` directory on ``sys.path`` is appended to this
+(``models.LSTM`` main.py:13 -- built, but selected by importing ``dvt_amd.models.LSTM`` --, and
+``basicmlp``, ``contrastivemodel``, ``pretrained``: out of scope) keep resolving to the
+reference's files: every other ``models`` directory on ``sys.path`` is appended to this
 package's search path.
 """
 import os
