@@ -77,6 +77,13 @@ class ConvDesc(C.Structure):
                 ("out_h", C.c_int32), ("out_w", C.c_int32), ("out_rows", C.c_void_p), ("residual_compact", C.c_int32)]
 
 
+class Conv3dDesc(C.Structure):
+    _fields_ = [("x", c_p), ("w", c_p), ("y", c_p), ("N", c_i64)] + \
+               [(n, C.c_int32) for n in ("T", "H", "W", "C", "Cout", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw",
+                                         "dtype")] + \
+               [("scale", c_p), ("shift", c_p), ("residual", c_p), ("relu", C.c_int32), ("workspace", c_p)]
+
+
 class BnAffine(C.Structure):
     _fields_ = [("mean", C.c_void_p), ("invstd", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
                 ("c_valid", C.c_int32), ("relu", C.c_int32)]
@@ -271,6 +278,12 @@ SIGNATURES = {
     "dvt_lstm_seq_bwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
     "dvt_sigmoid_bce_fwd": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_int, c_p]),
     "dvt_sigmoid_bce_bwd": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_int, c_p]),
+    "dvt_conv3d_implicit_supported": (c_int, [C.POINTER(Conv3dDesc)]),
+    "dvt_conv3d_implicit_k": (c_i64, [C.POINTER(Conv3dDesc)]),
+    "dvt_conv3d_implicit_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc)]),
+    "dvt_conv3d_implicit": (c_int, [C.POINTER(Conv3dDesc), c_p]),
+    "dvt_conv3d_weight_pack": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_p]),
+    "dvt_bn_fold": (c_int, [c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_int, c_p]),
     "dvt_comm_unique_id": (c_int, [c_p]),
     "dvt_comm_init": (c_int, [C.POINTER(c_p), c_p, c_int, c_int]),
     "dvt_comm_allreduce": (c_int, [c_p, c_p, c_i64, c_int, c_p]),

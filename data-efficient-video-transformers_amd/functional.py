@@ -2247,3 +2247,46 @@ class _SigmoidBce(torch.autograd.Function):
 def sigmoid_bce(z: Tensor, target: Tensor) -> Tensor:
     """nn.BCELoss()(torch.sigmoid(z), target): mean, each log term clamped at -100 (LSTM.py:55-57)."""
     return _SigmoidBce.apply(z, target)
+
+
+# ------------------------------------------------------------------ 3-D convolution + eval BatchNorm (inference only)
+def _conv3d_pack(conv: torch.nn.Conv3d, bn, Cp: int, dtype: torch.dtype, K: int):
+    """Packed weights [Cout, K] and the folded BatchNorm (scale, shift) of a Conv3d -> BatchNorm3d pair, made once and cached
+    on the module; the cache is dropped when a parameter or running statistic changes version (load_state_dict, an optimiser
+    step, in-place edits) or moves (``.to``)."""
+    ts = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+    stamp = tuple((t.data_ptr(), t._version) for t in ts if t is not None) + ((bn.eps,) if bn is not None else ())
+    cache = conv.__dict__.setdefault("_dvt_conv3d_cache", {})
+    key = (dtype, Cp, K)
+    hit = cache.get(key)
+    if hit is not None and hit[0] == stamp:
+        return hit[1]
+    w = ops.conv3d_weight_pack(conv.weight, Cp, K, dtype)
+    scale = shift = None
+    if bn is not None:
+        scale, shift = ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+    cache.clear()
+    cache[key] = (stamp, (w, scale, shift))
+    return w, scale, shift
+
+
+def conv3d_bn_act(x: Tensor, conv: torch.nn.Conv3d, bn, geom, *, relu: bool, residual: Optional[Tensor] = None,
+                  dtype: torch.dtype = torch.bfloat16):
+    """Inference-only conv3d -> eval BatchNorm3d (-> + residual) (-> ReLU) in ONE launch (dvt_conv3d_implicit with the
+    BatchNorm folded into its epilogue).  geom = (N, T, H, W); x NDHWC [N*T*H*W, Cp] in ``dtype`` (Cp >= conv.in_channels,
+    a multiple of 8, channels past in_channels zero).  -> (y [N*To*Ho*Wo, Cout], To, Ho, Wo).  ``bn`` may be None."""
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in conv.parameters())
+                                    or (bn is not None and any(p.requires_grad for p in bn.parameters()))):
+        raise RuntimeError("conv3d_bn_act is inference-only (no backward): call it under torch.no_grad() / "
+                           "torch.inference_mode()")
+    if bn is not None and (bn.training or bn.running_mean is None):
+        raise RuntimeError("conv3d_bn_act folds an eval-mode BatchNorm (running statistics): put the module in eval()")
+    assert conv.groups == 1 and conv.bias is None and tuple(conv.dilation) == (1, 1, 1)
+    if x.dtype != dtype:
+        raise TypeError(f"conv3d_bn_act: map is {x.dtype}, compute dtype {dtype}")
+    k, s, p = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding)
+    Cout = conv.out_channels
+    K = ops.conv3d_implicit_k(x, geom, Cout, k, s, p)
+    w, scale, shift = _conv3d_pack(conv, bn, x.shape[1], dtype, K)
+    y = ops.conv3d_implicit(x, w, geom, Cout, k, s, p, scale=scale, shift=shift, residual=residual, relu=relu)
+    return (y,) + ops.conv3d_out(geom, k, s, p)

@@ -180,6 +180,12 @@ class ResNet(nn.Module):
                     pyramid.append(fm)
         return pyramid
 
+    def embed(self, x):
+        """x [N, 3, H, W] -> [N, 512 * expansion]: AdaptiveAvgPool2d(1) of x4, what torchvision's resnet with ``fc = Identity()``
+        returns (the image / location experts of the reference's EmbeddingExtractor)."""
+        y, N, H, W = self.forward_nhwc(x)[-1]
+        return F.mean_rows(y.view(N, H * W, y.shape[1]))
+
     def forward(self, x):
         maps = []
         for (y, N, H, W) in self.forward_nhwc(x):

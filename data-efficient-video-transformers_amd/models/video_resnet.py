@@ -105,6 +105,24 @@ def _virtual_bn_pair(pair, N, T, H, W, dtype) -> bool:
     return ops.conv3x1_window_geometry(N, T, H * W, 144, 64, dtype)
 
 
+class Conv3DSimple(nn.Conv3d):
+    """Full 3x3x3 convolution (torchvision.models.video.resnet.Conv3DSimple)."""
+
+    def __init__(self, in_planes, out_planes, midplanes=None, stride=1, padding=1):
+        super().__init__(in_planes, out_planes, kernel_size=(3, 3, 3), stride=stride, padding=padding, bias=False)
+
+    @staticmethod
+    def get_downsample_stride(stride):
+        return stride, stride, stride
+
+
+def _conv3d(fm, conv, bn, relu, dtype, residual=None):
+    """conv3d -> eval BN (-> + residual) (-> ReLU) on an NDHWC matrix, one launch (F.conv3d_bn_act)."""
+    y, N, T, H, W = fm
+    out, To, Ho, Wo = F.conv3d_bn_act(y, conv, bn, (N, T, H, W), relu=relu, residual=residual, dtype=dtype)
+    return (out, N, To, Ho, Wo)
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
@@ -119,6 +137,8 @@ class BasicBlock(nn.Module):
         self.stride = stride
 
     def forward_ndhwc(self, fm, dtype):
+        if isinstance(self.conv1[0], nn.Conv3d):                   # Conv3DSimple (r3d_18): inference path
+            return self._forward_3d(fm, dtype)
         y, N, T, H, W = fm
         c1, c2 = self.conv1[0], self.conv2[0]
         if _virtual_bn_pair(c1, N, T, H, W, dtype):
@@ -145,6 +165,22 @@ class BasicBlock(nn.Module):
         out = _spatial(out, c2[0], c2[1], True, dtype)
         return _temporal(out, c2[3], self.conv2[1], True, dtype, residual=residual)     # out += residual; relu
 
+    def _forward_3d(self, fm, dtype):
+        out = _conv3d(fm, self.conv1[0], self.conv1[1], True, dtype)
+        residual = fm[0]
+        if self.downsample is not None:
+            residual = _conv3d(fm, self.downsample[0], self.downsample[1], False, dtype)[0]
+        return _conv3d(out, self.conv2[0], self.conv2[1], True, dtype, residual=residual)     # out += residual; relu
+
+
+class BasicStem(nn.Sequential):
+    """Conv3d(3, 64, (3, 7, 7), (1, 2, 2), (1, 3, 3)) -> BN -> ReLU (torchvision.models.video.resnet.BasicStem)."""
+
+    def __init__(self):
+        super().__init__(
+            nn.Conv3d(3, 64, kernel_size=(3, 7, 7), stride=(1, 2, 2), padding=(1, 3, 3), bias=False),
+            nn.BatchNorm3d(64), nn.ReLU(inplace=True))
+
 
 class R2Plus1dStem(nn.Sequential):
     def __init__(self):
@@ -156,14 +192,19 @@ class R2Plus1dStem(nn.Sequential):
 
 
 class VideoResNet(nn.Module):
-    def __init__(self, layers=(2, 2, 2, 2), num_classes=400, *, compute_dtype=torch.bfloat16):
+    """block / conv_makers / stem: torchvision's VideoResNet arguments (defaults: R(2+1)D-18)."""
+
+    def __init__(self, layers=(2, 2, 2, 2), num_classes=400, *, compute_dtype=torch.bfloat16, block=None, conv_makers=None,
+                 stem=None):
         super().__init__()
+        block = BasicBlock if block is None else block
+        conv_makers = [Conv2Plus1D] * 4 if conv_makers is None else list(conv_makers)
         self.inplanes = 64
-        self.stem = R2Plus1dStem()
-        self.layer1 = self._make_layer(64, layers[0], 1)
-        self.layer2 = self._make_layer(128, layers[1], 2)
-        self.layer3 = self._make_layer(256, layers[2], 2)
-        self.layer4 = self._make_layer(512, layers[3], 2)
+        self.stem = R2Plus1dStem() if stem is None else stem()
+        self.layer1 = self._make_layer(64, layers[0], 1, block, conv_makers[0])
+        self.layer2 = self._make_layer(128, layers[1], 2, block, conv_makers[1])
+        self.layer3 = self._make_layer(256, layers[2], 2, block, conv_makers[2])
+        self.layer4 = self._make_layer(512, layers[3], 2, block, conv_makers[3])
         self.avgpool = nn.AdaptiveAvgPool3d((1, 1, 1))
         self.fc = nn.Linear(512, num_classes)
         self.compute_dtype = compute_dtype
@@ -177,22 +218,24 @@ class VideoResNet(nn.Module):
                 nn.init.normal_(m.weight, 0, 0.01)
                 nn.init.constant_(m.bias, 0)
 
-    def _make_layer(self, planes, blocks, stride):
+    def _make_layer(self, planes, blocks, stride, block=BasicBlock, conv_builder=Conv2Plus1D):
         downsample = None
-        if stride != 1 or self.inplanes != planes:
-            ds = Conv2Plus1D.get_downsample_stride(stride)
-            downsample = nn.Sequential(nn.Conv3d(self.inplanes, planes, kernel_size=1, stride=ds, bias=False),
-                                       nn.BatchNorm3d(planes))
-        layers = [BasicBlock(self.inplanes, planes, Conv2Plus1D, stride, downsample)]
-        self.inplanes = planes
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            ds = conv_builder.get_downsample_stride(stride)
+            downsample = nn.Sequential(nn.Conv3d(self.inplanes, planes * block.expansion, kernel_size=1, stride=ds, bias=False),
+                                       nn.BatchNorm3d(planes * block.expansion))
+        layers = [block(self.inplanes, planes, conv_builder, stride, downsample)]
+        self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(BasicBlock(self.inplanes, planes, Conv2Plus1D))
+            layers.append(block(self.inplanes, planes, conv_builder))
         return nn.Sequential(*layers)
 
     def features(self, x):
         """x [N, 3, T, H, W] -> pooled [N, 512]."""
         if x.dim() != 5 or x.shape[1] != 3:
             raise ValueError("VideoResNet expects clips [N, 3, T, H, W]")
+        if isinstance(self.stem, BasicStem):
+            return self._features_3d(x)
         dt = self.compute_dtype
         N, _, T, H, W = x.shape
         frames = x.permute(0, 2, 1, 3, 4)                  # [N, T, 3, H, W]: per-frame NCHW
@@ -214,9 +257,32 @@ class VideoResNet(nn.Module):
         y, N, T, H, W = fm
         return F.mean_rows(y.view(N, T * H * W, y.shape[1]))          # AdaptiveAvgPool3d(1)
 
+    def _features_3d(self, x):
+        """Full-3-D tree (r3d_18): every convolution one dvt_conv3d_implicit launch; eval mode, no autograd."""
+        if self.training:
+            raise NotImplementedError("r3d_18 is an inference-only feature extractor here (no training / backward path): "
+                                      "call .eval() and run it under torch.no_grad()")
+        dt = self.compute_dtype
+        N, _, T, H, W = x.shape
+        # [N, 3, T, H, W] -> NDHWC [N*T*H*W, 8] in the compute dtype, planes 3..7 zero (the kernel's 16-byte channel chunks)
+        if dt in (torch.bfloat16, torch.float16):
+            y = ops.nchw_to_nhwc_pad(x.reshape(N, 3, T * H, W), dt, 8)
+        else:                                                   # (the one-pass form writes 16-bit maps only)
+            xt = ops.transpose_last2((x if x.dtype == dt else ops.cast(x, dt)).reshape(N, 3, T * H * W))
+            y = ops.zeros((N * T * H * W, 8), dt, x.device)
+            ops.copy2d(xt, y, N * T * H * W, 3, 3, 8)
+        fm = _conv3d((y, N, T, H, W), self.stem[0], self.stem[1], True, dt)
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in layer:
+                fm = blk.forward_ndhwc(fm, dt)
+        y, N, T, H, W = fm
+        return F.mean_rows(y.view(N, T * H * W, y.shape[1]))          # AdaptiveAvgPool3d(1)
+
     def forward(self, x):
         feats = self.features(x)
         fc = self.fc[0] if isinstance(self.fc, nn.Sequential) else self.fc
+        if not hasattr(fc, "weight"):                                # fc = Identity(): the pooled features (the expert)
+            return feats
         return F.linear(feats, fc.weight, fc.bias)
 
 
@@ -225,3 +291,11 @@ def r2plus1d_18(pretrained=False, **kwargs):
         raise RuntimeError("pretrained=True downloads Kinetics weights (torchvision); there is no network here -- "
                            "load a state_dict explicitly")
     return VideoResNet((2, 2, 2, 2), **kwargs)
+
+
+def r3d_18(pretrained=False, **kwargs):
+    """torchvision.models.video.r3d_18: 3x3x3 convolutions throughout, inference only."""
+    if pretrained:
+        raise RuntimeError("pretrained=True downloads Kinetics weights (torchvision); there is no network here -- "
+                           "load a state_dict explicitly")
+    return VideoResNet((2, 2, 2, 2), block=BasicBlock, conv_makers=[Conv3DSimple] * 4, stem=BasicStem, **kwargs)

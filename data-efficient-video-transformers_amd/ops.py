@@ -1969,3 +1969,84 @@ def lstm_seq_bwd(w_hh: Tensor, gates: Tensor, c: Tensor, dh_seq: Optional[Tensor
     L.check(lib.dvt_lstm_seq_bwd(w_hh.data_ptr(), gates.data_ptr(), c.data_ptr(), _p(dh_seq), _p(dh_last),
                                  dG.data_ptr(), _p(ws), B, T, H, dt(w_hh), _stream()), "dvt_lstm_seq_bwd")
     return dG
+
+
+# ------------------------------------------------------------------ 3-D convolution (inference; the r3d_18 video expert)
+def conv3d_desc(x: Tensor, w: Optional[Tensor], geom, Cout: int, k, stride, pad, *, dtype: Optional[torch.dtype] = None,
+                y: Optional[Tensor] = None) -> L.Conv3dDesc:
+    """geom = (N, T, H, W); k / stride / pad = (t, h, w) triples.  x NDHWC [N*T*H*W, C] (C % 8 == 0)."""
+    N, T, H, W = geom
+    d = L.Conv3dDesc()
+    d.x, d.w, d.y = _p(x), _p(w), _p(y)
+    d.N, d.T, d.H, d.W, d.C, d.Cout = N, T, H, W, x.shape[1], Cout
+    d.kt, d.kh, d.kw = k
+    d.st, d.sh, d.sw = stride
+    d.pt, d.ph, d.pw = pad
+    d.dtype = _DT[dtype if dtype is not None else x.dtype]
+    return d
+
+
+def conv3d_out(geom, k, stride, pad):
+    """(To, Ho, Wo) of a 3-D convolution."""
+    return tuple((n + 2 * p - kk) // s + 1 for n, kk, s, p in zip(geom[1:], k, stride, pad))
+
+
+def conv3d_implicit_k(x: Tensor, geom, Cout: int, k, stride, pad) -> int:
+    """Row length of the packed weights dvt_conv3d_implicit expects for this geometry."""
+    d = conv3d_desc(x, None, geom, Cout, k, stride, pad)
+    K = L.load().dvt_conv3d_implicit_k(C.byref(d))
+    if K < 0:
+        L.check(-2, "dvt_conv3d_implicit_k")          # DVT_ERR_UNSUPPORTED, with the library's message
+    return int(K)
+
+
+def conv3d_weight_pack(w: Tensor, Cp: int, ld: int, dtype: torch.dtype) -> Tensor:
+    """nn.Conv3d weight f32 [Cout, Cin, kt, kh, kw] -> packed [Cout, ld] in dtype (column ((dt*kh+dh)*kw+dw)*Cp + c)."""
+    _need_cuda(w)
+    w = w.detach().float().contiguous()
+    Cout, Cin, kt, kh, kw = w.shape
+    out = torch.empty((Cout, ld), dtype=dtype, device=w.device)
+    L.check(L.load().dvt_conv3d_weight_pack(w.data_ptr(), out.data_ptr(), _DT[dtype], Cout, Cin, kt, kh, kw, Cp, ld,
+                                            _stream()), "dvt_conv3d_weight_pack")
+    return out
+
+
+def bn_fold(gamma: Optional[Tensor], beta: Optional[Tensor], running_mean: Tensor, running_var: Tensor, eps: float):
+    """Eval-mode BatchNorm -> (scale, shift) f32 [C]: y = x * scale + shift."""
+    f = lambda t: None if t is None else t.detach().float().contiguous()      # noqa: E731
+    gamma, beta, mean, var = f(gamma), f(beta), f(running_mean), f(running_var)
+    _need_cuda(gamma, beta, mean, var)
+    Cc = mean.numel()
+    scale = torch.empty(Cc, dtype=torch.float32, device=mean.device)
+    shift = torch.empty_like(scale)
+    L.check(L.load().dvt_bn_fold(_p(gamma), _p(beta), mean.data_ptr(), var.data_ptr(), float(eps), scale.data_ptr(),
+                                 shift.data_ptr(), Cc, _stream()), "dvt_bn_fold")
+    return scale, shift
+
+
+def conv3d_implicit(x: Tensor, w: Tensor, geom, Cout: int, k, stride, pad, *, scale: Optional[Tensor] = None,
+                    shift: Optional[Tensor] = None, residual: Optional[Tensor] = None, relu: bool = False) -> Tensor:
+    """y [N*To*Ho*Wo, Cout] = relu?(conv3d(x, w) * scale + shift + residual) in x's dtype (dvt_conv3d_implicit).
+    x NDHWC [N*T*H*W, C], w packed [Cout, conv3d_implicit_k(..)] (conv3d_weight_pack)."""
+    _need_cuda(x, w, scale, shift, residual)
+    x = x.contiguous()
+    if w.dtype != x.dtype:
+        raise TypeError(f"conv3d_implicit: weights {w.dtype} != map {x.dtype}")
+    To, Ho, Wo = conv3d_out(geom, k, stride, pad)
+    M = geom[0] * To * Ho * Wo
+    if residual is not None:
+        residual = residual.contiguous()
+        if residual.dtype != x.dtype or residual.numel() != M * Cout:
+            raise ValueError("conv3d_implicit: residual must be [N*To*Ho*Wo, Cout] in the map's dtype")
+    y = torch.empty((M, Cout), dtype=x.dtype, device=x.device)
+    d = conv3d_desc(x, w, geom, Cout, k, stride, pad, y=y)
+    lib = L.load()
+    K = lib.dvt_conv3d_implicit_k(C.byref(d))
+    if K > 0 and tuple(w.shape) != (Cout, K):
+        raise ValueError(f"conv3d_implicit: packed weights {tuple(w.shape)} != ({Cout}, {K})")
+    d.scale, d.shift, d.residual, d.relu = _p(scale), _p(shift), _p(residual), int(relu)
+    ws = workspace(lib.dvt_conv3d_implicit_workspace_bytes(C.byref(d)), x.device, slot="conv3d")
+    d.workspace = _p(ws)
+    with _timed("conv3d_implicit", 2 * M * Cout * x.shape[1] * k[0] * k[1] * k[2]):
+        L.check(lib.dvt_conv3d_implicit(C.byref(d), _stream()), "dvt_conv3d_implicit")
+    return y

@@ -909,6 +909,47 @@ int dvt_sigmoid_bce_fwd(const void* z, const float* target, float* loss, float* 
 int dvt_sigmoid_bce_bwd(const void* z, const float* target, const float* gloss, void* dz, int64_t n, int dtype,
                         dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- 3-D convolution (the r3d_18 video expert)
+ * Additions within ABI v5: new entry points only, no existing layout or meaning changed.
+ * Full kt x kh x kw convolution forward as an implicit GEMM, for inference (torchvision r3d_18: Conv3DSimple, BasicStem and
+ * the 1x1x1 strided downsamples, behind the reference's EmbeddingExtractor, src/models/pretrained/models.py).
+ * x NDHWC [N*T*H*W, C] in dtype, C a multiple of 8 (zero-extend fewer channels: the stem's 3 planes run as 8);
+ * w [Cout][K] with K = dvt_conv3d_implicit_k(desc) = kt*kh*kw*C rounded up to 32, column ((dt*kh + dh)*kw + dw)*C + c,
+ * zero beyond (dvt_conv3d_weight_pack writes it so); y [N*To*Ho*Wo, Cout] in dtype, To = (T + 2 pt - kt) / st + 1 etc.
+ * Epilogue on the fp32 accumulators, every part optional (NULL / 0: off):
+ *   y = relu ? max(0, acc * scale[co] + shift[co] + residual[m, co]) : acc * scale[co] + shift[co] + residual[m, co]
+ * scale / shift f32 [Cout] (an eval-mode BatchNorm folded by dvt_bn_fold), residual [M, Cout] in dtype.
+ * dtype BF16 / F16 (fp32 accumulation) or F32 (exact fp32 MFMA).  Geometries with few output tiles and a deep K split the
+ * reduction into fp32 slabs in `workspace` (dvt_conv3d_implicit_workspace_bytes(desc) bytes, 16-byte aligned; 0: none
+ * needed) summed in a fixed order by a second launch.  No atomics: two identical calls give bitwise-equal results.
+ * x and w must each be < 2 GiB (else DVT_ERR_UNSUPPORTED: split the batch).  The caller zero-initialises the descriptor. */
+typedef struct dvt_conv3d_desc {
+  const void* x;
+  const void* w;
+  void* y;
+  int64_t N;
+  int32_t T, H, W, C, Cout;
+  int32_t kt, kh, kw, st, sh, sw, pt, ph, pw;
+  int32_t dtype;
+  const float* scale;
+  const float* shift;
+  const void* residual;
+  int32_t relu;
+  void* workspace;
+} dvt_conv3d_desc;
+int dvt_conv3d_implicit_supported(const dvt_conv3d_desc* desc);   /* 1: dvt_conv3d_implicit takes the geometry */
+int64_t dvt_conv3d_implicit_k(const dvt_conv3d_desc* desc);         /* row length of the packed weights; -1: unsupported */
+size_t dvt_conv3d_implicit_workspace_bytes(const dvt_conv3d_desc* desc);
+int dvt_conv3d_implicit(const dvt_conv3d_desc* desc, dvt_stream_t stream);
+/* w f32 [Cout][Cin][kt][kh][kw] (nn.Conv3d.weight) -> dst [Cout][ld] in dst_dtype, column ((dt*kh + dh)*kw + dw)*Cp + c,
+ * zero for c >= Cin and for columns >= kt*kh*kw*Cp.  Cp >= Cin, ld >= kt*kh*kw*Cp. */
+int dvt_conv3d_weight_pack(const float* w, void* dst, int dst_dtype, int Cout, int Cin, int kt, int kh, int kw, int Cp,
+                           int64_t ld, dvt_stream_t stream);
+/* Eval-mode BatchNorm as a per-channel affine: scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale
+ * (gamma / beta NULL: 1 / 0).  All f32 [C]. */
+int dvt_bn_fold(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                float* scale, float* shift, int C, dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- data-parallel gradient exchange
  * The reference is single-GPU (pl.Trainer(gpus=1), src/main.py:87); north_star partitions the clips of the global
  * batch over the 8 GPUs of a node, and the only exchange of the path is the SUM of the parameter gradients.  RCCL over
