@@ -52,8 +52,9 @@ template <> struct Mma16f<f16> {
 // the first had written them (conv3x1_fwd<.., 1>: `v_mfma_f32_16x16x32 v[4:7] .. ; s_waitcnt lgkmcnt(0) ; v_mfma_f32_16x16x16
 // v[4:7], .., v[4:7]`).  With NPB position blocks per wave the k-step-major order puts NPB - 1 independent MFMAs between the
 // two; below four blocks that distance is made up with wait states: 16 of them (`s_nop 15` = 64 cycles) outlast the 16-cycle
-// issue + write-back of either shape.  tests: test_temporal_forward_with_one_two_and_five_position_blocks_per_wave (the
-// unfenced build, -DDVT_NO_MFMA_SHAPE_FENCE, fails it at NPB = 1: profiles/r06_mfma_shape_hazard.md).
+// issue + write-back of either shape.  tests: tests/test_gpu_mfma_exact.py (exact results at every NPB of both forms; the
+// unfenced build, -DDVT_NO_MFMA_SHAPE_FENCE, failed the tolerance test at NPB = 1: profiles/r06_mfma_shape_hazard.md) and
+// tests/test_isa_hazards.py (tools/check_mfma_hazards.py on the listing, which flags the unfenced build at NPB 1 - 3).
 template <int NPB>
 __device__ __forceinline__ void mfma_shape_fence() {
 #ifndef DVT_NO_MFMA_SHAPE_FENCE
@@ -495,6 +496,19 @@ int dvt_conv3x1_fwd_supported(int64_t N, int T, int L, int Cin, int Cout, int dt
                  N * T * L < ((int64_t)1 << 31) ? 1 : 0;
 }
 
+int dvt_conv3x1_fwd_plan(int64_t N, int T, int L, int Cin, int Cout, int dtype, int* npb, int* pipelined) {
+  DVT_REQUIRE(npb && pipelined, "dvt_conv3x1_fwd_plan: npb and pipelined are required");
+  *npb = 0;
+  *pipelined = 0;
+  if (Cin != kCI || !dvt_conv3x1_fwd_supported(N, T, L, Cin, Cout, dtype)) return 0;
+  Window q;
+  int xs_ = 0;
+  *pipelined = tfp_plan(T, L, &q, &xs_) != 0 ? 1 : 0;      // (the launcher's choice, as in dvt_conv3x1_fwd)
+  if (!*pipelined) tf_plan(T, L, &q);
+  *npb = q.KP >> 5;
+  return 1;
+}
+
 int64_t dvt_conv3x1_fwd_stats_parts(int64_t N, int T, int L, int Cin) {
   if (Cin == 64) return dvt_internal::conv3x1_c64_stats_parts(N, T, L);
   Window q;
@@ -543,27 +557,35 @@ int dvt_conv3x1_fwd(const void* x, const dvt_bn_affine* x_affine, const void* w,
   const int grid = tf_grid(N, p.w_);
   hipStream_t st = (hipStream_t)stream;
   const bool h = dtype == DVT_F16;
+  // Which form takes which block count follows from the LDS budget: a tile of KP <= 96 positions has windows of at most
+  // 128 positions (40 KiB), so three of them and the staging images always fit and the pipelined form takes it; from
+  // KP = 128 up (>= 132 window positions) they never do, and the form above runs.  Only those six instantiations are built
+  // (dvt_conv3x1_fwd_plan reports the choice; tests/test_isa_hazards.py checks it over the geometries).  The bound is tight
+  // at KP = 128, S = 2: 3 x 43008 (132 x 320 = 42240 bytes rounded UP to 1 KiB) + 2 x 128 x 128 + 4096 = 165888 > 160 KiB only by
+  // the rounding -- a change to kXRow, to that rounding or to the staging size must re-check it (the DVT_REQUIRE defaults
+  // below then fire instead of launching a kernel that was not built).
   if (pipe) {
     const int lds = (nwin - 1) * p.xs + p.w_.x_bytes + 2 * p.w_.KP * 128;
     switch (p.w_.KP >> 5) {
       case 1: h ? tfp_launch<f16, 1>(p, grid, lds, st) : tfp_launch<bf16, 1>(p, grid, lds, st); break;
       case 2: h ? tfp_launch<f16, 2>(p, grid, lds, st) : tfp_launch<bf16, 2>(p, grid, lds, st); break;
       case 3: h ? tfp_launch<f16, 3>(p, grid, lds, st) : tfp_launch<bf16, 3>(p, grid, lds, st); break;
-      case 4: h ? tfp_launch<f16, 4>(p, grid, lds, st) : tfp_launch<bf16, 4>(p, grid, lds, st); break;
-      case 5: h ? tfp_launch<f16, 5>(p, grid, lds, st) : tfp_launch<bf16, 5>(p, grid, lds, st); break;
-      default: h ? tfp_launch<f16, 6>(p, grid, lds, st) : tfp_launch<bf16, 6>(p, grid, lds, st); break;
+      default: DVT_REQUIRE(false, "dvt_conv3x1_fwd: the pipelined form takes 1 - 3 position blocks per wave");
     }
     DVT_LAUNCH_CHECK("dvt_conv3x1_fwd(pipelined)");
     return DVT_OK;
   }
   const int lds = 2 * p.w_.x_bytes;
   switch (p.w_.KP >> 5) {
+#ifdef DVT_TF_NO_PIPE
     case 1: h ? tf_launch<f16, 1>(p, grid, lds, st) : tf_launch<bf16, 1>(p, grid, lds, st); break;
     case 2: h ? tf_launch<f16, 2>(p, grid, lds, st) : tf_launch<bf16, 2>(p, grid, lds, st); break;
     case 3: h ? tf_launch<f16, 3>(p, grid, lds, st) : tf_launch<bf16, 3>(p, grid, lds, st); break;
+#endif
     case 4: h ? tf_launch<f16, 4>(p, grid, lds, st) : tf_launch<bf16, 4>(p, grid, lds, st); break;
     case 5: h ? tf_launch<f16, 5>(p, grid, lds, st) : tf_launch<bf16, 5>(p, grid, lds, st); break;
-    default: h ? tf_launch<f16, 6>(p, grid, lds, st) : tf_launch<bf16, 6>(p, grid, lds, st); break;
+    case 6: h ? tf_launch<f16, 6>(p, grid, lds, st) : tf_launch<bf16, 6>(p, grid, lds, st); break;
+    default: DVT_REQUIRE(false, "dvt_conv3x1_fwd: the form without helper waves takes 4 - 6 position blocks per wave");
   }
   DVT_LAUNCH_CHECK("dvt_conv3x1_fwd");
   return DVT_OK;

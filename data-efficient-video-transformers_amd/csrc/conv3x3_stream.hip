@@ -143,6 +143,11 @@ __global__ __launch_bounds__(512) void conv3x3_stream_kernel(const StreamParams 
   constexpr int HALO = NTAP == 9 ? 1 : 0;      // zero columns either side of the patch rows
   static_assert(NST % 3 == 0 && NST >= 3 && TPS * CO * CK * 2 == kWStage && (NSTEP & 1) == 0, "stage geometry");
   static_assert(NTAP == 9 || CK == 64, "the (3, 1) form exists for 128-byte pixels");
+  // 48-channel chunks alternate 16x16x32 and 16x16x16 steps on the same accumulators, and the hardware does not interlock a
+  // dependent accumulate across the two opcodes (conv3x1_fwd.hip, mfma_shape_fence).  The scheduler orders the eight MFMAs of
+  // a step freely: in the 288-channel instantiation it put only 2 MFMAs between a 16x16x16 step and the next 16x16x32 step on
+  // one accumulator (tools/check_mfma_hazards.py; the 144-channel one keeps >= 3), so that transition gets 16 wait states.
+  constexpr bool kShapeFence = CK == 48 && NCH == 6;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const wring = smem;
   char* const pbuf = smem + 3 * kWStage;
@@ -428,6 +433,10 @@ __global__ __launch_bounds__(512) void conv3x3_stream_kernel(const StreamParams 
 #pragma unroll
             for (int t = 0; t < 2; ++t) acc[u][t] = Elem16<E>::mma(wf8[j][u], xf8[j][t], acc[u][t]);
         } else if ((j & 1) == 0) {
+          if constexpr (kShapeFence) {
+            asm volatile("s_nop 15" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+          }
 #pragma unroll
           for (int u = 0; u < NB; ++u)
 #pragma unroll

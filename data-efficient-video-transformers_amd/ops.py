@@ -1534,6 +1534,17 @@ def conv3x1_window_geometry(N: int, T: int, Lp: int, Cin: int, Cout: int, dtype:
         bool(lib.dvt_conv3x1_wgrad_supported(N, T, Lp, Cin, Cout, _DT[dtype]))
 
 
+def conv3x1_fwd_plan(N: int, T: int, Lp: int, dtype: torch.dtype):
+    """(position blocks per wave, pipelined) of the 144 -> 64 window forward dvt_conv3x1_fwd launches for this geometry, i.e.
+    which conv3x1_fwd_kernel / conv3x1_fwd_pipe_kernel instantiation runs; None where it does not take it.  Host only."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        return None
+    npb, pipe = C.c_int(), C.c_int()
+    rc = L.load().dvt_conv3x1_fwd_plan(N, T, Lp, 144, 64, _DT[dtype], C.byref(npb), C.byref(pipe))
+    L.check(min(rc, 0), "dvt_conv3x1_fwd_plan")
+    return (npb.value, bool(pipe.value)) if rc == 1 else None
+
+
 def conv3x1_fwd_supported(x: Tensor, wp: Tensor, N: int, T: int, Lp: int, Cin: int, Cout: int) -> bool:
     if not x.is_cuda or x.dtype not in (torch.bfloat16, torch.float16) or wp.dtype != x.dtype:
         return False

@@ -657,6 +657,10 @@ typedef struct dvt_bn_affine {
 } dvt_bn_affine;
 int dvt_conv3x1_fwd_supported(int64_t N, int T, int L, int Cin, int Cout, int dtype);
 int64_t dvt_conv3x1_fwd_stats_parts(int64_t N, int T, int L, int Cin);
+/* Which kernel dvt_conv3x1_fwd launches for the 144 -> 64 form (host only, no HIP call): *npb = 16-position blocks per wave
+ * (1 .. 6, the template parameter of conv3x1_fwd_kernel / conv3x1_fwd_pipe_kernel), *pipelined = 1 for the form with helper
+ * waves.  Returns 1, or 0 (both outputs 0) where dvt_conv3x1_fwd_supported refuses the geometry or Cin != 144 (since ABI v5). */
+int dvt_conv3x1_fwd_plan(int64_t N, int T, int L, int Cin, int Cout, int dtype, int* npb, int* pipelined);
 int dvt_conv3x1_fwd(const void* x, const dvt_bn_affine* x_affine, const void* w, int64_t ldw, void* y, float* stats_partial,
                     int64_t N, int T, int L, int Cin, int dtype, dvt_stream_t stream);
 int dvt_conv3x1_wgrad_supported(int64_t N, int T, int L, int Cin, int Cout, int dtype);

@@ -921,27 +921,17 @@ def test_temporal_weight_gradient_from_lds_sliding_windows(dvt, device, dtype, N
     assert rel_l2(acc.view(64, 144, 3) - old.view(64, 144, 3), ref) < 2e-5
 
 
-def _window_position_blocks(T, Lp):
-    """16-position blocks per wave of the window forward for a clip geometry (csrc/conv3x1_window.h: window_plan picks the
-    longest segment S <= 16 with Lp % S == 0 and (T * S) % 32 == 0 whose two windows fit; blocks = T * S / 32)."""
-    for S in range(16, 1, -1):
-        if Lp % S or (T * S) % 32:
-            continue
-        xbytes = (((T + 2) * S * 320) + 1023) & ~1023
-        if 2 * xbytes + 4096 > 160 * 1024 or (xbytes >> 10) > 72:
-            continue
-        return T * S // 32 if 2 * xbytes >= 32768 else 0        # (tf_plan: the statistics scratch overlays the two windows)
-    return 0
-
-
-# one to six position blocks per wave: with one or two, the 16x16x16 tail of a tap follows the tap's last 16x16x32 step on
-# the SAME accumulator with at most one other MFMA in between (ADVICE r5; csrc/conv3x1_fwd.hip: mfma_shape_fence)
+# every instantiation the launcher picks (dvt_conv3x1_fwd_plan: 1 - 3 position blocks per wave with helper waves, 4 - 6
+# without).  With fewer than four blocks the 16x16x16 tail of a tap follows the tap's last 16x16x32 step on the SAME
+# accumulator with at most two other MFMAs in between (csrc/conv3x1_fwd.hip: mfma_shape_fence); exact cases of
+# the same kernels: tests/test_gpu_mfma_exact.py
 _WINDOW_FWD_GEOMS = [(2, 12, 8, 7), (3, 12, 56, 56), (40, 12, 8, 8), (1, 8, 4, 4), (5, 16, 4, 6), (2, 8, 7, 8), (2, 20, 2, 4),
-                     (3, 2, 4, 4), (300, 2, 4, 8)]
+                     (3, 2, 4, 4), (300, 2, 4, 8), (3, 64, 2, 1), (2, 64, 3, 1)]
 
 
-def test_window_forward_geometries_cover_every_block_count():
-    assert {_window_position_blocks(T, H * W) for _, T, H, W in _WINDOW_FWD_GEOMS} == {1, 2, 3, 4, 5, 6}
+def test_window_forward_geometries_cover_every_block_count(dvt):
+    forms = {dvt.ops.conv3x1_fwd_plan(N, T, H * W, torch.bfloat16) for N, T, H, W in _WINDOW_FWD_GEOMS}
+    assert forms == {(1, True), (2, True), (3, True), (4, False), (5, False), (6, False)}
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

@@ -15,9 +15,11 @@ without them).  A handful per kernel is set-up code; more than GENERIC_LIMIT nul
 usage: tools/check_flat_ops.py [path/to/libdvt_hip.so]      (exit 1 when a kernel outside ALLOWED has FLAT instructions or
                                                             more than GENERIC_LIMIT generic-pointer null checks)
 """
-import os, re, shutil, subprocess, sys, tempfile
+import os, re, sys
 
-LLVM = "/opt/rocm/lib/llvm/bin"
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_listing import kernel_listings  # noqa: E402
+
 GENERIC_LIMIT = 12
 ALLOWED_GENERIC = ("patchify_generic",)   # real null checks of optional global pointers in an unrolled loop (any-patch-size fallback)
 ALLOWED = ("rocprim",)          # kernel-name substrings that may keep FLAT accesses (library code: the segmented sort of eval_metrics.hip)
@@ -27,24 +29,12 @@ def flat_ops(so_path, generic=None):
     """{kernel symbol: count of flat_load / flat_store / flat_atomic instructions} for the gfx950 code objects of so_path;
     generic (a dict, optional) receives {kernel symbol: count of 64-bit null checks (v_cmp_ne_u64 .., 0)}."""
     out = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        so = shutil.copy(so_path, tmp)
-        subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", so], check=True, capture_output=True, cwd=tmp)
-        for name in sorted(os.listdir(tmp)):
-            if "gfx950" not in name:
-                continue
-            dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", os.path.join(tmp, name)], check=True,
-                                 capture_output=True, text=True).stdout
-            cur = None
-            for line in dis.splitlines():
-                m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-                if m:
-                    cur = m.group(1)
-                    out.setdefault(cur, 0)
-                elif cur is not None and re.match(r"^\s+flat_(load|store|atomic)", line):
-                    out[cur] += 1
-                elif cur is not None and generic is not None and re.match(r"^\s+v_cmp_ne_u64_e32 vcc, 0,", line):
-                    generic[cur] = generic.get(cur, 0) + 1
+    for sym, insns in kernel_listings(so_path).items():
+        out[sym] = sum(1 for _, t in insns if re.match(r"flat_(load|store|atomic)", t))
+        if generic is not None:
+            n = sum(1 for _, t in insns if t.startswith("v_cmp_ne_u64_e32 vcc, 0,"))
+            if n:
+                generic[sym] = n
     return out
 
 
