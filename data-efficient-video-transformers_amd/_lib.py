@@ -284,6 +284,14 @@ SIGNATURES = {
     "dvt_conv3d_implicit_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc)]),
     "dvt_conv3d_implicit": (c_int, [C.POINTER(Conv3dDesc), c_p]),
     "dvt_conv3d_weight_pack": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_p]),
+    "dvt_bn1d_relu_fwd": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_int, c_f, c_f,
+                                  c_int, c_int, c_p]),
+    "dvt_bn1d_relu_bwd": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_int, c_i64, c_i64, c_int,
+                                  c_int, c_int, c_p]),
+    "dvt_adam_step_dev": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_p, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_int, c_p]),
+    "dvt_ce_labels_fwd": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p]),
+    "dvt_ce_labels_bwd": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_int, c_p]),
+    "dvt_gather_rows_ptr": (c_int, [c_p, c_i64, c_int, c_p, c_i64, c_i64, c_int, c_p]),
     "dvt_bn_fold": (c_int, [c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_int, c_p]),
     "dvt_comm_unique_id": (c_int, [c_p]),
     "dvt_comm_init": (c_int, [C.POINTER(c_p), c_p, c_int, c_int]),

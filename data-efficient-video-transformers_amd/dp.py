@@ -484,6 +484,28 @@ class FlatParameters:
         self._packed_valid = False
         self._after_step()
 
+    def adam_step(self, lr, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+        """torch.optim.Adam semantics (coupled L2 decay: contrastivemodel.py:64) in one launch: the update, the 16-bit
+        mirror and the device step counter.  ``lr``: a device fp32 scalar (``optim.Adam.lr_dev()``, which the LR scheduler
+        writes: a captured step follows it) or a float (kept in a scalar of this object, rewritten when it changes).
+        The bias-correction count is global, as in ``adamw_step``."""
+        if self.exp_avg is None:
+            self.init_optimizer_state()
+        if not isinstance(lr, torch.Tensor):
+            if getattr(self, "_lr_dev", None) is None:
+                self._lr_dev, self._lr_host = torch.full((1,), float(lr), dtype=torch.float32, device=self.data.device), lr
+            elif self._lr_host != lr:
+                self._lr_dev.fill_(float(lr))
+                self._lr_host = lr
+            lr = self._lr_dev
+        self.step_count += 1
+        ops.adam_step_dev_(self.data, self.grad, self.exp_avg, self.exp_avg_sq, self.step_dev, lr, beta1=betas[0],
+                           beta2=betas[1], eps=eps, weight_decay=weight_decay, skip=self.skip_mask, mirror=self.compute)
+        if self.compute is not None:
+            self.compute_valid = True
+        self._packed_valid = False
+        self._after_step()
+
     def sgd_step(self, lr: float, momentum: float = 0.0, weight_decay: float = 0.0) -> None:
         """torch.optim.SGD semantics (frame_transformer.py:124-126) in one launch over the flat buffers."""
         if momentum != 0.0 and getattr(self, "momentum_buf", None) is None:

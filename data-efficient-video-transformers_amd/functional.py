@@ -2290,3 +2290,235 @@ def conv3d_bn_act(x: Tensor, conv: torch.nn.Conv3d, bn, geom, *, relu: bool, res
     w, scale, shift = _conv3d_pack(conv, bn, x.shape[1], dtype, K)
     y = ops.conv3d_implicit(x, w, geom, Cout, k, s, p, scale=scale, shift=shift, residual=residual, relu=relu)
     return (y,) + ops.conv3d_out(geom, k, s, p)
+
+
+# ---------------------------------------------------------------------------
+# MLP baselines on expert embeddings (src/models/contrastivemodel.py, src/models/basicmlp.py)
+# ---------------------------------------------------------------------------
+def _bn_grad_targets(bn_w: Tensor, bn_b: Tensor):
+    """-> (dgamma, dbeta, accumulate, finish): where the BatchNorm kernel writes its parameter gradients (the sinks of a
+    ``dp.FlatParameters``, or new tensors) and ``finish()`` -> (dgamma, dbeta) to return to autograd."""
+    sg, sb = _sink(bn_w), _sink(bn_b)
+    C = bn_w.shape[0]
+    if sg is not None and sb is not None and sg.fresh == sb.fresh:
+        def finish():
+            sg.mark_written()
+            sb.mark_written()
+            return None, None
+        return sg.buf.view(-1), sb.buf.view(-1), not sg.fresh, finish
+    dg = torch.empty(C, dtype=torch.float32, device=bn_w.device)
+    db = torch.empty(C, dtype=torch.float32, device=bn_w.device)
+
+    def finish_tmp():
+        if sg is None and sb is None:
+            return dg, db
+        for s, t in ((sg, dg), (sb, db)):            # sinks that disagree on their accumulate flag: the slow form
+            if s is not None:
+                _emit_into(s, t)
+        return (dg if sg is None else None), (db if sb is None else None)
+    return dg, db, False, finish_tmp
+
+
+def _bn_module_args(bn, training: bool):
+    if bn.momentum is None:
+        raise NotImplementedError("BatchNorm1d(momentum=None) (cumulative average) has no HIP kernel")
+    if not bn.affine:
+        raise NotImplementedError("BatchNorm1d(affine=False) has no HIP kernel")
+    track = bn.track_running_stats and bn.running_mean is not None
+    if not training and not track:
+        raise NotImplementedError("eval-mode BatchNorm1d without running statistics has no HIP kernel")
+    return ((bn.running_mean, bn.running_var, bn.num_batches_tracked) if track else (None, None, None))
+
+
+def batch_norm1d_relu(z: Tensor, bn: torch.nn.BatchNorm1d, segments: int = 1, training: Optional[bool] = None) -> Tensor:
+    """``bn(relu(z))`` on z [S*B, C] where the S row segments of B rows are S separate calls of the module (each with its
+    own batch statistics; running statistics updated segment after segment, ``num_batches_tracked`` += S).  One launch
+    forward, one backward (which also applies the ReLU mask).  ``training`` defaults to ``bn.training``."""
+    training = bn.training if training is None else bool(training)
+    return _BatchNorm1dReluOp.apply(z, bn.weight, bn.bias, bn, int(segments), training)
+
+
+class _BatchNorm1dReluOp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, w, b, bn, segments, training):
+        zc = z.contiguous()
+        rm, rv, nbt = _bn_module_args(bn, training)
+        y, mean, inv = ops.bn1d_relu_fwd(zc, w.detach(), b.detach(), rm, rv, nbt if training else None, segments=segments,
+                                         training=training, eps=bn.eps, momentum=bn.momentum)
+        ctx.save_for_backward(zc, mean, inv)
+        ctx.params = (w, b)
+        ctx.segments, ctx.training = segments, training
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        zc, mean, inv = ctx.saved_tensors
+        w, b = ctx.params
+        dg, db, acc, finish = _bn_grad_targets(w, b)
+        dz = ops.bn1d_relu_bwd(_as(dy.contiguous(), zc.dtype), zc, w.detach(), mean, inv, segments=ctx.segments,
+                               training=ctx.training, dgamma=dg, dbeta=db, accumulate=acc)
+        dgr, dbr = finish()
+        return dz, dgr, dbr, None, None, None
+
+
+class _CrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index):
+        lc = logits.contiguous()
+        lab = labels.contiguous()
+        loss, lse = ops.ce_labels_fwd(lc, lab, ignore_index)
+        ctx.save_for_backward(lc, lab, lse)
+        ctx.ignore = ignore_index
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        lc, lab, lse = ctx.saved_tensors
+        return ops.ce_labels_bwd(lc, lab, lse, _f32(gloss).reshape(1), ctx.ignore), None, None
+
+
+def cross_entropy(logits: Tensor, labels: Tensor, ignore_index: int = ops.CE_IGNORE_INDEX) -> Tensor:
+    """nn.CrossEntropyLoss()(logits [M, C], labels int64 [M]): mean over the rows whose label is not ``ignore_index``
+    (basicmlp.py:38), fp32 arithmetic.  A label outside [0, C) gives a NaN loss instead of an out-of-bounds read."""
+    if labels.dtype != torch.int64:
+        raise TypeError(f"cross_entropy: labels must be int64, got {labels.dtype}")
+    return _CrossEntropy.apply(logits, labels, int(ignore_index))
+
+
+class MlpLayer:
+    """One layer of ``mlp_chain``: ``linear`` (y = x W^T (+ b), optionally ReLU in the GEMM epilogue, optionally an fp32
+    output), ``bn_relu`` (y = bn(relu(x)): its input is a pre-activation) or ``dropout`` (after a ReLU Linear)."""
+
+    __slots__ = ("kind", "module", "relu", "out_f32", "p")
+
+    def __init__(self, kind, module=None, *, relu=False, out_f32=False, p=0.0):
+        self.kind, self.module, self.relu, self.out_f32, self.p = kind, module, bool(relu), bool(out_f32), float(p)
+
+    def params(self):
+        if self.kind == "linear":
+            return [self.module.weight, self.module.bias]
+        if self.kind == "bn_relu":
+            return [self.module.weight, self.module.bias]
+        return []
+
+
+class _MlpChain(torch.autograd.Function):
+    """A chain of Linear / ReLU / BatchNorm1d-after-ReLU / Dropout layers, forward and backward as kernel launches.
+    Where a ReLU sits between two Linears it is the first one's RELU epilogue, and in the backward the DRELU epilogue of the
+    second one's data-gradient GEMM (aux = the rectified activation): the gradient that leaves a Linear is already
+    masked for the layer below.  BatchNorm's ReLU is in its own kernels; Dropout after a ReLU is one gated launch back."""
+
+    @staticmethod
+    def forward(ctx, x, layers, segments, training, returned, *params):
+        ctx.set_materialize_grads(False)       # an unused output (the embedding in a training step) costs no launch back
+        h = x.contiguous()
+        saved, outs, it = [], [], iter(params)
+        for L_ in layers:
+            if L_.kind == "linear":
+                w, b = next(it), next(it)
+                wc = _wc(w, h.dtype)
+                y = ops.linear_fwd(h, wc, _f32(b), epilogue=L.EPI_RELU if L_.relu else L.EPI_NONE,
+                                   out_dtype=torch.float32 if L_.out_f32 else None)
+                saved.append((h, wc, w, b))
+            elif L_.kind == "bn_relu":
+                w, b = next(it), next(it)
+                bn = L_.module
+                rm, rv, nbt = _bn_module_args(bn, training)
+                y, mean, inv = ops.bn1d_relu_fwd(h, w.detach(), b.detach(), rm, rv, nbt if training else None,
+                                                 segments=segments, training=training, eps=bn.eps, momentum=bn.momentum)
+                saved.append((h, mean, inv, w, b))
+            else:
+                st = _rng.tensor(h.device)
+                y = ops.dropout(h, L_.p, st, _rng.take(h.numel()))
+                saved.append((y,))
+            outs.append(y)
+            h = y
+        ctx.layers, ctx.segments, ctx.training, ctx.returned = layers, segments, training, returned
+        ctx.saved, ctx.outs = saved, outs
+        ctx.nparams = len(params)
+        return tuple(outs[i] for i in returned)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        layers, saved, outs = ctx.layers, ctx.saved, ctx.outs
+        extra = {i: g for i, g in zip(ctx.returned, grads)}
+        pgrads = []
+        g, masked = None, False
+        for k in range(len(layers) - 1, -1, -1):
+            L_ = layers[k]
+            e = extra.get(k)
+            if e is not None:
+                e = _as(e.contiguous(), outs[k].dtype)
+                if L_.kind == "linear" and L_.relu:
+                    e = ops.act_bwd(e, outs[k], ops.ACT_RELU)
+                    if g is not None and not masked:
+                        g = ops.act_bwd(g, outs[k], ops.ACT_RELU)
+                    masked = True
+                g = e if g is None else ops.add(g, e)
+            if L_.kind == "linear":
+                h, wc, w, b = saved[k]
+                if g is None:
+                    pgrads[:0] = [None, None]
+                    continue
+                if L_.relu and not masked:
+                    g = ops.act_bwd(_as(g, outs[k].dtype), outs[k], ops.ACT_RELU)
+                dy2 = _as(g.contiguous(), h.dtype)
+                sw, sb = _sink(w), _sink(b)
+                below_relu = k > 0 and layers[k - 1].kind == "linear" and layers[k - 1].relu
+                if k > 0 or ctx.needs_input_grad[0]:
+                    epi = L.EPI_DRELU if below_relu else L.EPI_NONE
+                    dw, db, dx = _linear_bwd(sw, sb, dy2, h, wc, b is not None, epilogue=epi,
+                                             aux=h if below_relu else None)
+                    g, masked = dx, below_relu
+                else:
+                    dw, db = _emit_wgrad_bias(sw, sb, dy2, h, b is not None)
+                    g = None
+                pgrads[:0] = [dw, db]
+            elif L_.kind == "bn_relu":
+                h, mean, inv, w, b = saved[k]
+                if g is None:
+                    pgrads[:0] = [None, None]
+                    continue
+                dg, db, acc, finish = _bn_grad_targets(w, b)
+                g = ops.bn1d_relu_bwd(_as(g.contiguous(), h.dtype), h, w.detach(), mean, inv, segments=ctx.segments,
+                                      training=ctx.training, dgamma=dg, dbeta=db, accumulate=acc)
+                masked = False
+                pgrads[:0] = list(finish())
+            else:
+                (y,) = saved[k]
+                if g is not None:              # gate = the dropout output: zero where dropped or where the ReLU below cut
+                    g = ops.dropout_fused(_as(g.contiguous(), y.dtype), L_.p, None, 0, gate=y)
+                    masked = True
+        ctx.saved = ctx.outs = None
+        dx = g if ctx.needs_input_grad[0] else None
+        return (dx, None, None, None, None) + tuple(pgrads)
+
+
+def mlp_chain(x: Tensor, layers, *, segments: int = 1, training: bool = True, returned=None):
+    """Run ``layers`` (a sequence of ``MlpLayer``) on x [S*B, D] (compute dtype) -> the outputs of the layers whose
+    indices are in ``returned`` (default: the last).  ``segments``: S views of B rows each, run in one launch per layer
+    (BatchNorm keeps per-view statistics).  ``training``: BatchNorm batch statistics and Dropout (else eval forms)."""
+    keep = [i for i, L_ in enumerate(layers) if not (L_.kind == "dropout" and (not training or L_.p <= 0.0))]
+    if returned is not None:
+        if any(i not in keep or layers[i].kind == "dropout" for i in returned):
+            raise ValueError("mlp_chain: a returned layer must be a Linear or a BatchNorm")
+        returned = tuple(keep.index(i) for i in returned)
+    layers = [layers[i] for i in keep]
+    for i, L_ in enumerate(layers):
+        prev = layers[i - 1] if i else None
+        if L_.kind == "dropout" and not (prev is not None and prev.kind == "linear" and prev.relu):
+            raise ValueError("mlp_chain: Dropout must follow a Linear with ReLU")
+        if L_.kind == "dropout" and L_.p >= 1.0:
+            raise ValueError("dropout p must be < 1")
+        if L_.kind == "bn_relu" and prev is not None and (prev.kind != "linear" or prev.relu):
+            raise ValueError("mlp_chain: bn_relu reads a pre-activation (a Linear without ReLU, or the input)")
+    returned = (len(layers) - 1,) if returned is None else tuple(returned)
+    params = []
+    for L_ in layers:
+        params += L_.params()
+    return _MlpChain.apply(x, layers, int(segments), bool(training), returned, *params)
+
+
+def contrastive_loss_rows(reps: Tensor, temperature: float) -> Tensor:
+    """ContrastiveLoss on reps = cat(z_i, z_j) [2B, D] already in one tensor (the two views of ``step_views``)."""
+    return _Contrastive.apply(reps, temperature)

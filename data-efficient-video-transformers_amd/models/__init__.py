@@ -8,3 +8,6 @@ from .transformer import SimpleTransformer  # noqa: F401,E402
 from . import custom_resnet, TPN  # noqa: F401,E402
 from . import LSTM  # noqa: F401,E402
 from .LSTM import LSTMRegressor  # noqa: F401,E402
+from . import contrastivemodel, basicmlp  # noqa: F401,E402
+from .contrastivemodel import SpatioTemporalContrastiveModel  # noqa: F401,E402
+from .basicmlp import BasicMLP  # noqa: F401,E402

@@ -2061,3 +2061,115 @@ def conv3d_implicit(x: Tensor, w: Tensor, geom, Cout: int, k, stride, pad, *, sc
     with _timed("conv3d_implicit", 2 * M * Cout * x.shape[1] * k[0] * k[1] * k[2]):
         L.check(lib.dvt_conv3d_implicit(C.byref(d), _stream()), "dvt_conv3d_implicit")
     return y
+
+
+# ------------------------------------------------------------------ MLP baselines on expert embeddings (csrc/embed_mlp.hip)
+def _ld(t: Tensor) -> int:
+    assert t.dim() == 2 and t.stride(1) == 1
+    return t.stride(0)
+
+
+def bn1d_relu_fwd(z: Tensor, gamma: Tensor, beta: Tensor, running_mean: Optional[Tensor], running_var: Optional[Tensor],
+                  num_batches_tracked: Optional[Tensor], *, segments: int, training: bool, eps: float, momentum: float):
+    """y = BatchNorm1d(relu(z)) on z [S*B, C] (S = segments, each with its own batch statistics) -> (y, mean, invstd):
+    mean / invstd f32 [S, C] in training, [C] (from the running statistics) in eval."""
+    _need_cuda(z, gamma, beta, running_mean, running_var, num_batches_tracked)
+    R, Cc = z.shape
+    if R % segments:
+        raise ValueError(f"bn1d_relu: {R} rows do not split into {segments} segments")
+    B = R // segments
+    for t in (gamma, beta, running_mean, running_var):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == Cc)
+    assert num_batches_tracked is None or num_batches_tracked.dtype == torch.int64
+    y = torch.empty((R, Cc), dtype=z.dtype, device=z.device)
+    shape = (segments, Cc) if training else (Cc,)
+    mean = torch.empty(shape, dtype=torch.float32, device=z.device)
+    invstd = torch.empty(shape, dtype=torch.float32, device=z.device)
+    L.check(L.load().dvt_bn1d_relu_fwd(z.data_ptr(), _ld(z), y.data_ptr(), Cc, gamma.data_ptr(), beta.data_ptr(),
+                                       _p(running_mean), _p(running_var), _p(num_batches_tracked), mean.data_ptr(),
+                                       invstd.data_ptr(), B, Cc, segments, eps, momentum, int(training), dt(z), _stream()),
+            "dvt_bn1d_relu_fwd")
+    return y, mean, invstd
+
+
+def bn1d_relu_bwd(dy: Tensor, z: Tensor, gamma: Tensor, mean: Tensor, invstd: Tensor, *, segments: int, training: bool,
+                  dgamma: Optional[Tensor] = None, dbeta: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
+    """dz = [z > 0] * dBN/dx (one launch); dgamma / dbeta f32 [C] written (or added to, ``accumulate``) when given."""
+    _need_cuda(dy, z, gamma, mean, invstd, dgamma, dbeta)
+    R, Cc = z.shape
+    assert dy.shape == z.shape and dy.dtype == z.dtype
+    for t in (dgamma, dbeta):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == Cc)
+    dz = torch.empty((R, Cc), dtype=z.dtype, device=z.device)
+    L.check(L.load().dvt_bn1d_relu_bwd(dy.data_ptr(), _ld(dy), z.data_ptr(), _ld(z), gamma.data_ptr(), mean.data_ptr(),
+                                       invstd.data_ptr(), dz.data_ptr(), Cc, _p(dgamma), _p(dbeta), int(accumulate),
+                                       R // segments, Cc, segments, int(training), dt(z), _stream()), "dvt_bn1d_relu_bwd")
+    return dz
+
+
+def adam_step_dev_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step_dev2: Tensor, lr_dev: Tensor, *,
+                   beta1: float, beta2: float, eps: float, weight_decay: float, skip: Optional[Tensor] = None,
+                   mirror: Optional[Tensor] = None) -> None:
+    """torch.optim.Adam (coupled L2 decay) + optional 16-bit mirror + device step counter (int64[2]) in one launch; the
+    learning rate is read from the device scalar ``lr_dev`` (f32)."""
+    _need_cuda(param, grad, exp_avg, exp_avg_sq, step_dev2, lr_dev, mirror)
+    for t in (param, grad, exp_avg, exp_avg_sq):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == param.numel()
+    assert step_dev2.dtype == torch.int64 and step_dev2.numel() == 2 and lr_dev.dtype == torch.float32
+    if mirror is not None:
+        assert mirror.numel() == param.numel() and mirror.is_contiguous() and mirror.dtype in (torch.bfloat16, torch.float16)
+    L.check(L.load().dvt_adam_step_dev(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                       param.numel(), lr_dev.data_ptr(), beta1, beta2, eps, weight_decay,
+                                       step_dev2.data_ptr(), _skip(skip, param), _p(mirror),
+                                       _DT[mirror.dtype] if mirror is not None else 0, _stream()), "dvt_adam_step_dev")
+
+
+CE_IGNORE_INDEX = -100
+
+
+def ce_labels_fwd(logits: Tensor, labels: Tensor, ignore_index: int = CE_IGNORE_INDEX):
+    """nn.CrossEntropyLoss() (mean, ignore_index) -> (loss f32 [1], lse f32 [M + 1]: per-row log-sum-exp, then the count)."""
+    _need_cuda(logits, labels)
+    M, Cc = logits.shape
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == M
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    lse = torch.empty(M + 1, dtype=torch.float32, device=logits.device)
+    L.check(L.load().dvt_ce_labels_fwd(logits.data_ptr(), _ld(logits), labels.data_ptr(), loss.data_ptr(), lse.data_ptr(),
+                                       M, Cc, ignore_index, dt(logits), _stream()), "dvt_ce_labels_fwd")
+    return loss, lse
+
+
+def ce_labels_bwd(logits: Tensor, labels: Tensor, lse: Tensor, gloss: Tensor,
+                  ignore_index: int = CE_IGNORE_INDEX) -> Tensor:
+    _need_cuda(logits, labels, lse, gloss)
+    M, Cc = logits.shape
+    assert gloss.dtype == torch.float32 and lse.numel() == M + 1
+    d = torch.empty((M, Cc), dtype=logits.dtype, device=logits.device)
+    L.check(L.load().dvt_ce_labels_bwd(logits.data_ptr(), _ld(logits), labels.data_ptr(), lse.data_ptr(), gloss.data_ptr(),
+                                       d.data_ptr(), Cc, M, Cc, ignore_index, dt(logits), _stream()), "dvt_ce_labels_bwd")
+    return d
+
+
+def gather_rows_ptr(rows, D: int, dtype: torch.dtype, device) -> Tensor:
+    """rows: a list (one per output row) of lists of GPU tensors, each holding one row of ``numel()`` elements ->
+    [len(rows), D] in ``dtype``, row r = cat(rows[r]) (zero past the parts' total width), in ONE launch.  The pointer
+    table is built on the host and copied to the device once."""
+    R, P = len(rows), len(rows[0])
+    out = torch.empty((R, D), dtype=dtype, device=device)
+    tab = torch.empty((R, P, 3), dtype=torch.int64)
+    keep = []
+    for r, parts in enumerate(rows):
+        if len(parts) != P:
+            raise ValueError("gather_rows_ptr: every row needs the same number of parts")
+        if sum(t.numel() for t in parts) != D:
+            raise ValueError(f"gather_rows_ptr: row {r} has {sum(t.numel() for t in parts)} elements, expected {D}")
+        for j, t in enumerate(parts):
+            _need_cuda(t)
+            if t.device != out.device or not t.is_contiguous():
+                raise ValueError("gather_rows_ptr: parts must be contiguous tensors on the output's device")
+            tab[r, j, 0], tab[r, j, 1], tab[r, j, 2] = t.data_ptr(), t.numel(), dt(t)
+            keep.append(t)
+    table = tab.to(out.device)
+    L.check(L.load().dvt_gather_rows_ptr(table.data_ptr(), R, P, out.data_ptr(), D, D, _DT[dtype], _stream()),
+            "dvt_gather_rows_ptr")
+    return out

@@ -1,9 +1,9 @@
 """HIP-backed optimizers behind the ``torch.optim.Optimizer`` interface that Lightning's trainer drives
 (``configure_optimizers`` of the reference: frame_transformer.py:123-134, transformer.py:58-61).
 
-Per-parameter launches of the fused update kernels (``dvt_adamw_step`` / ``dvt_sgd_step`` /
+Per-parameter launches of the fused update kernels (``dvt_adamw_step`` / ``dvt_adam_step_dev`` / ``dvt_sgd_step`` /
 ``dvt_adagrad_step``); a model wrapped in ``dp.FlatParameters`` should use its one-launch
-``adamw_step`` / ``sgd_step`` / ``adagrad_step`` instead.  State names match torch's
+``adamw_step`` / ``adam_step`` / ``sgd_step`` / ``adagrad_step`` instead.  State names match torch's
 (``exp_avg``, ``exp_avg_sq``, ``momentum_buffer``, ``sum``, ``step``) so optimizer state dicts
 written by the reference load unchanged.
 """
@@ -57,6 +57,62 @@ class AdamW(_Base):
                 ops.adamw_step_(p.data, g, st["exp_avg"], st["exp_avg_sq"], lr=grp["lr"], beta1=grp["betas"][0],
                                 beta2=grp["betas"][1], eps=grp["eps"], weight_decay=grp["weight_decay"],
                                 step=st["step"])
+                self._invalidate(p)
+        return loss
+
+
+class Adam(_Base):
+    """torch.optim.Adam (amsgrad off) with coupled L2 weight decay (``g += weight_decay * p`` before the moments):
+    contrastivemodel.py:64 and basicmlp.py:49.  The optimizer owns one device fp32 LR scalar per parameter group
+    (``lr_dev(i)``) that every update reads, and one device step counter per parameter (``state["step"]``, int64[2]:
+    steps taken, launch ticket), so ``step()`` has no host synchronisation and can be captured in a hipGraph; a captured
+    step follows a new rate written by ``sync_lr()`` (which ``lr_scheduler.LinearWarmupCosineAnnealingLR.step`` calls)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
+        if amsgrad:
+            raise NotImplementedError("Adam(amsgrad=True) has no HIP kernel")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
+        self._lr_dev = []
+        self._lr_host = []
+        for grp in self.param_groups:
+            dev = grp["params"][0].device if grp["params"] else torch.device("cpu")
+            self._lr_dev.append(torch.full((1,), float(grp["lr"]), dtype=torch.float32, device=dev))
+            self._lr_host.append(float(grp["lr"]))
+
+    def lr_dev(self, group: int = 0) -> torch.Tensor:
+        """The device fp32 scalar the updates of param group ``group`` read their learning rate from."""
+        return self._lr_dev[group]
+
+    def sync_lr(self) -> None:
+        """Write each group's ``lr`` into its device scalar where it changed (a fill launch on the current stream)."""
+        for i, grp in enumerate(self.param_groups):
+            lr = float(grp["lr"])
+            if lr != self._lr_host[i]:
+                self._lr_dev[i].fill_(lr)
+                self._lr_host[i] = lr
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        if not capturing:                 # a rate set by hand; inside a capture the scalar is written from outside
+            self.sync_lr()
+        for i, grp in enumerate(self.param_groups):
+            for p in grp["params"]:
+                g = _grad32(p)
+                if g is None:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st["step"] = torch.zeros(2, dtype=torch.int64, device=p.device)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                ops.adam_step_dev_(p.data, g, st["exp_avg"], st["exp_avg_sq"], st["step"], self._lr_dev[i],
+                                   beta1=grp["betas"][0], beta2=grp["betas"][1], eps=grp["eps"],
+                                   weight_decay=grp["weight_decay"])
                 self._invalidate(p)
         return loss
 

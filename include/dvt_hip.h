@@ -954,6 +954,49 @@ int dvt_conv3d_weight_pack(const float* w, void* dst, int dst_dtype, int Cout, i
 int dvt_bn_fold(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
                 float* scale, float* shift, int C, dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- the MLP baselines on expert embeddings
+ * Additions within ABI v5: new entry points only, no existing layout or meaning changed.
+ * SpatioTemporalContrastiveModel (src/models/contrastivemodel.py) and BasicMLP (src/models/basicmlp.py); their GEMMs run on
+ * dvt_gemm.  No atomics in any reduction: two identical calls give bitwise-equal results.  dtype F32, BF16 or F16.
+ *
+ * y = BatchNorm1d(relu(z)) on S * B rows of C columns (S = 1 or 2 segments of B rows, each with its own batch statistics:
+ * two views in one launch).  z [S*B][ldz], y [S*B][ldy] in dtype; gamma, beta, running_mean, running_var f32 [C].
+ * training: mean and biased variance per segment (centred two-pass form), save_mean / save_invstd f32 [S, C]; the running
+ * statistics (NULL: not tracked) take momentum * (mean, unbiased variance) segment 0 first, then segment 1, and
+ * *num_batches_tracked (NULL: none) += S -- exactly S successive nn.BatchNorm1d calls.  B = 1 is refused, as torch does.
+ * eval: the affine form from the running statistics; save_mean / save_invstd (optional) f32 [C] receive running_mean and
+ * 1 / sqrt(running_var + eps). */
+int dvt_bn1d_relu_fwd(const void* z, int64_t ldz, void* y, int64_t ldy, const float* gamma, const float* beta,
+                      float* running_mean, float* running_var, int64_t* num_batches_tracked, float* save_mean,
+                      float* save_invstd, int64_t B, int64_t C, int S, float eps, float momentum, int training, int dtype,
+                      dvt_stream_t stream);
+/* Backward of dvt_bn1d_relu_fwd: dz = [z > 0] * d/dx BN(x) (the ReLU of the prologue applied in the same pass).
+ * save_mean / save_invstd: the forward's ([S, C] training, [C] eval).  dgamma / dbeta f32 [C] (NULL: not wanted) are the
+ * sums over the segments in order, added to the buffers when `accumulate`. */
+int dvt_bn1d_relu_bwd(const void* dy, int64_t lddy, const void* z, int64_t ldz, const float* gamma, const float* save_mean,
+                      const float* save_invstd, void* dz, int64_t lddz, float* dgamma, float* dbeta, int accumulate,
+                      int64_t B, int64_t C, int S, int training, int dtype, dvt_stream_t stream);
+/* torch.optim.Adam (amsgrad off, coupled L2 decay: g += weight_decay * p before the moments) over n f32 elements, the
+ * learning rate read from the device scalar lr_dev[0] (a captured step sees a new value without re-capture).
+ * step_dev2, skip64 and mirror as dvt_adamw_step_fused. */
+int dvt_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
+                      float beta1, float beta2, float eps, float weight_decay, int64_t* step_dev2, const uint8_t* skip64,
+                      void* mirror, int mirror_dtype, dvt_stream_t stream);
+/* nn.CrossEntropyLoss() on integer labels: loss[0] = mean over the rows whose label != ignore_index of
+ * logsumexp(x_r) - x_r[label_r], fp32 arithmetic.  logits [M][ld] dtype, labels int64 [M]; lse f32 [M + 1] receives the
+ * per-row log-sum-exp and, at [M], the number of counted rows.  A label outside [0, C) is never used as an index: the
+ * loss (and that row's gradient) become NaN. */
+int dvt_ce_labels_fwd(const void* logits, int64_t ld, const int64_t* labels, float* loss, float* lse, int64_t M, int64_t C,
+                      int64_t ignore_index, int dtype, dvt_stream_t stream);
+/* dlogits[r] = gloss[0] / count * (softmax(x_r) - onehot(label_r)); zero rows for ignore_index. */
+int dvt_ce_labels_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* lse, const float* gloss,
+                      void* dlogits, int64_t lddl, int64_t M, int64_t C, int64_t ignore_index, int dtype,
+                      dvt_stream_t stream);
+/* out[r][0:D] = concatenation of `parts` source rows, cast to dtype; columns past the sources' total width are zero.
+ * table: int64 [rows][parts][3] on the device, {address, width, source dtype} per entry. */
+int dvt_gather_rows_ptr(const int64_t* table, int64_t rows, int parts, void* out, int64_t ldo, int64_t D, int dtype,
+                        dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- data-parallel gradient exchange
  * The reference is single-GPU (pl.Trainer(gpus=1), src/main.py:87); north_star partitions the clips of the global
  * batch over the 8 GPUs of a node, and the only exchange of the path is the SUM of the parameter gradients.  RCCL over
