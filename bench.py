@@ -7,12 +7,20 @@ and the fused AdamW step), ViViT metric shape of BASELINE.json
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set up, warm up,
+time the steps, write --dump-outputs if asked, print the line.  --full adds everything else
+(--no-roofline / --no-secondary / --no-cpu-baseline leave parts of it out):
   roofline      dominant kernel family (the MFMA GEMM, forward layout) measured live with
-                HIP events on the launch stream inside the timed steps: algorithmic
+                HIP events on the launch stream in a separate profiled pass: algorithmic
                 FLOPs of its launches / their summed duration, vs the dense bf16 MFMA peak.
+  secondary     the pyramid, crossmodal, longclip and frametransformer workloads, 3 timed
+                steps each (one GPU, --workload vivit).
   cpu_baseline  the CPU oracle (the reference's arithmetic restated, pinned to the
                 reference by tests/golden) timed on this host on a bounded sample.
+  optimizer     optimizer_ms_per_step: the fused AdamW step timed on its own.
+  exchange      under data parallelism, in gradient_exchange: the eager step, the bucket
+                timeline and the exposed all-reduce time.
+A --full run also writes the full record to --detail-out (profiles/bench_detail.json).
 """
 import argparse
 import json
@@ -522,8 +530,9 @@ def timed_steps(run, steps, barrier):
     return elapsed, per_step, loss
 
 
-def run_workload(args, workload, rank, world, use_dist, comm, *, steps, warmup, roofline, secondary=False):
-    """One workload, timed per the driver's contract.  Returns the JSON dict (rank 0) or None."""
+def run_workload(args, workload, rank, world, use_dist, comm, *, steps, warmup, roofline, secondary=False, full=False):
+    """One workload, timed per the driver's contract.  Returns the JSON dict (rank 0) or None.  ``full``: also the
+    measurements beyond the headline that run after the timed steps (optimizer share, data-parallel breakdown)."""
     from dvt_amd import ops
     from dvt_amd.graph import capture_step, capture_step_segments
     W = build_workload(args, workload, rank, comm)
@@ -591,7 +600,7 @@ def run_workload(args, workload, rank, world, use_dist, comm, *, steps, warmup, 
     pct = lambda q: per_step[min(len(per_step) - 1, int(q * len(per_step)))]
 
     extra = {}
-    if use_dist and not secondary:
+    if use_dist and not secondary and full:
         # the same step launched kernel by kernel from the host (what round 1 did under data parallelism)
         k = max(3, min(10, steps))
         for _ in range(2):
@@ -625,13 +634,15 @@ def run_workload(args, workload, rank, world, use_dist, comm, *, steps, warmup, 
             extra["allreduce_bytes_per_step"] = int(flat.total * (2 if flat.grad16 is not None else 4))
 
     # optimizer share of the step (SURVEY 8d asks for it separately): fused AdamW + bf16 weight mirror on the flat buffers
-    o0, o1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    o0.record()
-    for _ in range(5):
-        flat.adamw_step(lr=0.0, weight_decay=0.0)            # lr = 0: timing only, the weights stay put
-    o1.record()
-    torch.cuda.synchronize()
-    optimizer_ms = o0.elapsed_time(o1) / 5
+    optimizer_ms = None
+    if full:
+        o0, o1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        o0.record()
+        for _ in range(5):
+            flat.adamw_step(lr=0.0, weight_decay=0.0)            # lr = 0: timing only, the weights stay put
+        o1.record()
+        torch.cuda.synchronize()
+        optimizer_ms = o0.elapsed_time(o1) / 5
 
     # ---- roofline of the dominant kernel family, live HIP events (separate short pass so the
     #      event records do not perturb the headline timing)
@@ -744,7 +755,7 @@ def run_workload(args, workload, rank, world, use_dist, comm, *, steps, warmup, 
             if workload in ("vivit", "longclip") else None,
             "final_loss": round(final_loss, 5),
             "step_ms": {"p10": round(pct(0.1), 3), "median": round(pct(0.5), 3), "p90": round(pct(0.9), 3)},
-            "optimizer_ms_per_step": round(optimizer_ms, 3),
+            "optimizer_ms_per_step": round(optimizer_ms, 3) if optimizer_ms is not None else None,
             "peak_hbm_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
         }
         if note:
@@ -954,10 +965,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8, help="clips per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the bounded secondary workloads (pyramid, crossmodal, "
-                    "longclip, frametransformer: 3 timed steps each) that the default single-GPU run appends under \"secondary\"")
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure everything else the line can carry: "
+                    "the roofline pass, the secondary workloads, the CPU baseline, the optimizer share and, under data "
+                    "parallelism, the exchange breakdown; and write the full record to --detail-out.  Off: the run sets up, "
+                    "warms up, times the steps, writes --dump-outputs and prints the line, nothing more")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline pass")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the bounded secondary workloads (pyramid, "
+                    "crossmodal, longclip, frametransformer: 3 timed steps each) that a single-GPU --full run appends under "
+                    "\"secondary\"")
     ap.add_argument("--bucket-mb", type=float, default=13.0,
                     help="gradient bucket size in MiB: about one transformer layer (12.6 MB fp32 at d = 512), so that a layer's "
                     "all-reduce starts when that layer's backward ends -- with 32 MiB buckets 48 MB of gradients became ready in "
@@ -989,15 +1005,17 @@ def main():
                     "Linears as two launches (ops.PAIR_LAUNCH)")
     ap.add_argument("--attn-two-pass", action="store_true", help="A/B switch: attention backward as the dq + dk/dv kernel pair "
                     "instead of the one-pass kernel (ops.ATTN_BWD_TWO_PASS)")
-    ap.add_argument("--detail-out", default=DETAIL_DEFAULT, help="file (relative to the repository root) that receives the FULL "
+    ap.add_argument("--detail-out", default=None, help="file (relative to the repository root) that receives the FULL "
                     "record -- per-family rooflines, per-kernel HBM rates, bucket timeline; the printed line is the compact form "
-                    "and names this file; '' writes none")
+                    f"and names this file; '' writes none; default: {DETAIL_DEFAULT} under --full, none otherwise")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one "
                     "computed as DIR/<name>.npy (float32): loss, logits, and the flat gradients and updated weights (a fixed "
                     "seeded sample of them when larger than 4 Mi entries), for output-for-output comparison of two builds")
     ap.add_argument("--rendezvous-only", action="store_true", help="launcher self-test (runs without a GPU): every rank joins "
                     "the process group, sums its rank over the group and rank 0 prints a JSON line with n_gpus = world")
     args = ap.parse_args()
+    if args.detail_out is None:
+        args.detail_out = DETAIL_DEFAULT if args.full else ""
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, sys.argv[1:])            # before anything touches the GPU
@@ -1058,8 +1076,8 @@ def main():
     _LIVE["comm"] = comm
 
     out = run_workload(args, args.workload, rank, world, use_dist, comm, steps=args.steps, warmup=args.warmup,
-                       roofline=not args.no_roofline)
-    if world == 1 and not use_dist and args.workload == "vivit" and not args.no_secondary:
+                       roofline=args.full and not args.no_roofline, full=args.full)
+    if args.full and world == 1 and not use_dist and args.workload == "vivit" and not args.no_secondary:
         # BASELINE configs[2..4] -- the per-frame CNN encoder + pyramid, the cross-modal attention + distillation head, the
         # long-clip stress -- and the reference's default FrameTransformer(model='vid') (R(2+1)D-18 encoder), timed in the same
         # driver-visible line, bounded (3 timed steps each; the two CNN workloads carry their conv / BatchNorm roofline)
@@ -1069,7 +1087,7 @@ def main():
             try:
                 r = run_workload(args, wl, rank, world, False, None, steps=3, warmup=1,
                                  roofline=wl in ("pyramid", "frametransformer", "longclip") and not args.no_roofline,
-                                 secondary=True)
+                                 secondary=True, full=True)
                 sec[wl] = {k: r[k] for k in ("metric", "value", "unit", "ms_per_step", "dtype", "launch", "peak_hbm_GiB",
                                              "final_loss", "roofline") if k in r}
                 sec[wl]["workload"] = r["config"]["workload"]
@@ -1079,7 +1097,7 @@ def main():
             out["secondary"] = sec
     progress(None)                      # done: nothing collective left that could hang
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.workload == "vivit":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "vivit":
             out["cpu_baseline"] = cpu_baseline(dict(image=224, patch=16, classes=19, T=32, d=512, depth=4, heads=8, dh=64))
         emit(out, args.detail_out)
     if _LIVE["comm"] is not None:

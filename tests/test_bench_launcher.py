@@ -1,10 +1,14 @@
 """bench.py --gpus N without a launcher (the reference is pl.Trainer(gpus=1), src/main.py:87): the parent
 spawns N rank processes before any GPU call, relays rank 0's JSON line, refuses a world size that differs from --gpus and
-exits non-zero when a rank fails.  Runs on CPU (gloo) through the launcher's rendezvous-only mode."""
+exits non-zero when a rank fails.  Runs on CPU (gloo) through the launcher's rendezvous-only mode.  What a plain run does
+and what --full adds: on CPU with the GPU legs stubbed, and one real plain run on the GPU."""
 import json
 import os
 import subprocess
 import sys
+import time
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -97,3 +101,94 @@ def test_the_printed_line_is_compact_and_carries_every_workload(tmp_path, capsys
     assert line["gradient_exchange"]["exposed_allreduce_ms_per_step"] == 0.3 and line["gradient_exchange"]["devices"]
     with open(tmp_path / "detail.json") as fh:                    # the full record is in the file the line names
         assert json.load(fh)["secondary"]["pyramid"]["roofline"]["conv_families"] == fams
+
+
+def _load_bench(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def _main_with_stubs(bench, monkeypatch, capsys, argv):
+    """bench.main() with the GPU legs stubbed: -> (run_workload calls, cpu_baseline calls, the printed line)."""
+    runs, baselines = [], []
+
+    def run_workload(args, workload, rank, world, use_dist, comm, *, steps, warmup, roofline, secondary=False, full=False):
+        runs.append(dict(workload=workload, steps=steps, warmup=warmup, roofline=roofline, secondary=secondary, full=full))
+        return {"metric": f"m {workload}", "value": 100.0, "unit": "clips/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
+                "ms_per_step": 5.0, "higher_is_better": True, "dtype": "bf16", "config": {"workload": workload}}
+
+    def cpu_baseline(cfg):
+        baselines.append(cfg)
+        return {"value": 0.5, "unit": "clips/s", "cores": 16, "kind": "port", "sample": "s"}
+
+    monkeypatch.setattr(bench, "run_workload", run_workload)
+    monkeypatch.setattr(bench, "cpu_baseline", cpu_baseline)
+    monkeypatch.setattr(bench, "release_gpu_memory", lambda: None)
+    monkeypatch.setattr(bench.torch.cuda, "set_device", lambda i: None)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    capsys.readouterr()
+    bench.main()
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return runs, baselines, json.loads(lines[0])
+
+
+def test_a_plain_run_times_the_headline_only_and_full_adds_the_rest(monkeypatch, capsys, tmp_path):
+    """A plain run is the metric workload's warm-up and timed steps and nothing else: no roofline pass, no secondary
+    workloads, no CPU baseline, no optimizer / exchange breakdown, no detail file.  --full runs all of them, as before."""
+    bench = _load_bench("bench_plain_under_test")
+    runs, baselines, line = _main_with_stubs(bench, monkeypatch, capsys, ["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert runs == [dict(workload="vivit", steps=7, warmup=3, roofline=False, secondary=False, full=False)]
+    assert baselines == []
+    assert line["value"] == 100.0 and line["ms_per_step"] == 5.0
+    for k in ("secondary", "cpu_baseline", "roofline", "detail"):
+        assert k not in line, k
+
+    detail = str(tmp_path / "detail.json")
+    runs, baselines, line = _main_with_stubs(bench, monkeypatch, capsys, ["--gpus", "1", "--steps", "7", "--warmup", "3",
+                                                                          "--full", "--detail-out", detail])
+    assert runs[0] == dict(workload="vivit", steps=7, warmup=3, roofline=True, secondary=False, full=True)
+    assert [r["workload"] for r in runs[1:]] == ["pyramid", "crossmodal", "longclip", "frametransformer"]
+    assert all(r["secondary"] and r["steps"] == 3 and r["warmup"] == 1 for r in runs[1:])
+    assert [r["roofline"] for r in runs[1:]] == [True, False, True, True]
+    assert len(baselines) == 1
+    assert set(line["secondary"]) == {"pyramid", "crossmodal", "longclip", "frametransformer"}
+    assert line["cpu_baseline"]["value"] == 0.5 and line["detail"] == detail
+    with open(detail) as fh:
+        assert json.load(fh)["value"] == 100.0
+
+    # the --no-* switches still trim a --full run
+    runs, baselines, line = _main_with_stubs(bench, monkeypatch, capsys, ["--full", "--no-roofline", "--no-secondary",
+                                                                          "--no-cpu-baseline", "--detail-out", ""])
+    assert runs == [dict(workload="vivit", steps=20, warmup=5, roofline=False, secondary=False, full=True)]
+    assert baselines == [] and "detail" not in line
+
+
+@pytest.mark.gpu
+def test_a_plain_run_spends_little_outside_its_steps(tmp_path):
+    """A fresh plain run of the metric workload: one JSON line with the headline fields and nothing of --full, and at
+    most 30 s of its wall time outside the warm-up and timed steps (start-up, capture, exit)."""
+    steps, warmup = 5, 2
+    e = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    t0 = time.monotonic()
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=300, env=e)
+    wall = time.monotonic() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == "clips/sec fwd+bwd, B=8 T=32 3x224x224 bf16" and line["unit"] == "clips/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+    assert abs(line["value"] - 8 * 1e3 / line["ms_per_step"]) <= 0.01 * line["value"]
+    for k in ("secondary", "cpu_baseline", "roofline", "optimizer_ms_per_step", "detail"):
+        assert k not in line, k
+    assert sorted(os.listdir(tmp_path / "dump")) == ["grad.npy", "logits.npy", "loss.npy", "params.npy"]
+    outside = wall - (steps + warmup) * line["ms_per_step"] * 1e-3
+    assert outside < 30.0, f"{outside:.1f} s outside the steps"
