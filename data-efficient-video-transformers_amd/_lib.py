@@ -67,6 +67,11 @@ class GemmDesc(C.Structure):
     ]
 
 
+class GemmPlanInfo(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("route", "kernel", "cfg", "split", "k_per_split", "tile_m", "reduce", "colsum", "carry",
+                                           "a_kmajor", "b_kmajor", "epilogue", "out_form")]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("y", C.c_void_p), ("N", C.c_int64)] + \
                [(n, C.c_int32) for n in ("H", "W", "C", "Cout", "kh", "kw", "sh", "sw", "ph", "pw", "dtype")] + \
@@ -167,6 +172,8 @@ SIGNATURES = {
     "dvt_gemm_workspace_bytes": (C.c_size_t, [C.POINTER(GemmDesc)]),
     "dvt_gemm": (c_int, [C.POINTER(GemmDesc), c_p]),
     "dvt_gemm_route": (c_int, [C.POINTER(GemmDesc)]),
+    "dvt_gemm_plan": (c_int, [C.POINTER(GemmDesc), C.POINTER(GemmPlanInfo)]),
+    "dvt_gemm_pair_plan": (c_int, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), C.POINTER(GemmPlanInfo), C.POINTER(GemmPlanInfo)]),
     "dvt_splitk_reduce_pending": (c_int, [C.POINTER(SplitKPending), c_p]),
     "dvt_gemm_pair_fused": (c_int, [C.POINTER(GemmDesc), C.POINTER(GemmDesc)]),
     "dvt_gemm_pair": (c_int, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), c_p]),

@@ -401,6 +401,11 @@ struct GenericParams {
 
 __device__ __forceinline__ float acc_fma(float a, float b, float c) { return fmaf(a, b, c); }
 __device__ __forceinline__ double acc_fma(float a, float b, double c) { return fma((double)a, (double)b, c); }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void gemm_generic_kernel(const GenericParams p) {
@@ -501,11 +506,13 @@ __global__ __launch_bounds__(256) void gemm_tiny_kernel(const GenericParams p) {
     for (int k = 0; k < p.K; ++k)
       acc_ = acc_fma(to_f32<T>(A[(int64_t)m * p.sam + (int64_t)k * p.sak]), to_f32<T>(B[(int64_t)k * p.sbk + (int64_t)n * p.sbn]), acc_);
   }
-  float acc = (float)acc_;
   if (WAVE) {
-    acc = wave_sum(acc);
+    // (fp32: the lanes' double partials meet in double -- rounded to fp32 before the 64-lane sum they left the result
+    //  several ulp from the dot product that the fp32 parity mode promises, tests/test_gpu_gemm_exact.py)
+    acc_ = wave_sum(acc_);
     if (threadIdx.x & 63) return;
   }
+  const float acc = (float)acc_;
   const float bias = p.bias ? p.bias[n] : 0.f;
   float res = 0.f, aux = 0.f, pre = 0.f;
   if (p.epilogue == DVT_EPI_RESIDUAL) res = to_f32<T>(((const T*)p.residual)[(int64_t)m * p.ldr + n]);
@@ -749,6 +756,98 @@ static GemmRoute route_gemm(const dvt_gemm_desc* d) {
   return r;
 }
 
+// The decisions dvt_gemm takes beyond the route, each in one place: dvt_gemm launches by them and dvt_gemm_plan reports them.
+// A planned split with no workspace for its slabs runs unsplit on the 128x128 kernel.
+static GemmPlan with_workspace(const dvt_gemm_desc* d, GemmPlan pl) {
+  if (pl.split > 1 && !d->workspace) {
+    pl.use256 = false;
+    pl.split = 1;
+    pl.kps = (int)(dvt_cdiv(d->K, BK) * BK);
+  }
+  return pl;
+}
+// bias gradient fused into the LDS-DMA weight-gradient kernel (split-K slab path, cfg 0 / 5): one row of partial sums per slice
+static bool colsum_fused(const dvt_gemm_desc* d, const GemmPlan& pl) {
+  return d->colsum_out && pl.use256 && (pl.cfg == 0 || pl.cfg == 5) && pl.split > 1 && !d->a_kmajor && !d->b_kmajor &&
+         d->epilogue == DVT_EPI_NONE && d->out_dtype == DVT_F32;
+}
+// what sums the slabs of a split: the epilogue's reduce unless plain; a plain fp32 one may be deferred to the next call
+static int split_reduce_kind(const dvt_gemm_desc* d) {
+  const bool plain = d->epilogue == DVT_EPI_NONE && !d->bias && d->alpha == 1.0f;
+  if (!plain) return DVT_GEMM_R_EPILOGUE;
+  return d->out_dtype == DVT_F32 && d->defer_reduce ? DVT_GEMM_R_DEFERRED : DVT_GEMM_R_PLAIN;
+}
+// generic route: one wave per output (few outputs, long K), one thread per output (few outputs, short K), 64x64 tiles
+static int generic_kernel_kind(const dvt_gemm_desc* d) {
+  const int64_t outs = d->M * d->N;
+  if (outs <= 16384 && d->K >= 128) return DVT_GEMM_K_TINY_WAVE;
+  if (outs <= 65536 && d->K <= 32) return DVT_GEMM_K_TINY_THREAD;
+  return DVT_GEMM_K_GENERIC64;
+}
+// the form a pending reduce takes as a launch of its own (DVT_GEMM_CARRY_*)
+static int pending_reduce_kind(const dvt_splitk_pending* q) {
+  if (q->splits >= 64 && !q->cs_slab && q->M * q->N <= ((int64_t)1 << 20)) return DVT_GEMM_CARRY_WIDE;
+  return q->conv_taps > 0 ? DVT_GEMM_CARRY_CONV : DVT_GEMM_CARRY_ALONE;
+}
+
+// Everything dvt_gemm decides before it launches, and the argument checks that go with it.
+struct GemmResolved {
+  GemmRoute route;
+  GemmPlan pl;              // ROUTE_MFMA: the plan as launched (with_workspace)
+  dvt_gemm_plan_info info;
+};
+static int resolve_gemm(const dvt_gemm_desc* d, GemmResolved* r) {
+  const int rc = check_desc(d);
+  if (rc) return rc;
+  dvt_gemm_plan_info& in = r->info;
+  in = dvt_gemm_plan_info{};
+  in.cfg = -1;
+  in.split = 1;
+  r->route = route_gemm(d);
+  r->pl = r->route.pl;
+  in.route = (int)r->route.kind;
+  if (d->M == 0 || d->N == 0) return DVT_OK;                      // nothing to launch
+  DVT_REQUIRE(!d->colsum_out || !d->a_kmajor, "dvt_gemm: colsum_out needs an mn-major A");
+  DVT_REQUIRE(!d->defer_reduce || d->pending, "dvt_gemm: defer_reduce needs a pending descriptor to fill");
+  const GemmRouteKind kind = r->route.kind;
+  if (d->residual_f32 && d->epilogue == DVT_EPI_RESIDUAL) {
+    DVT_REQUIRE(d->out_dtype == DVT_F32 && d->ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(d->residual) & 15u) == 0,
+                "dvt_gemm: an fp32 residual needs an fp32 output, ldr %% 4 == 0 and a 16-byte aligned buffer");
+    if (kind != ROUTE_SMALL)
+      DVT_UNSUPPORTED("dvt_gemm: the fp32 residual epilogue is served for launch-bound shapes only (M = %lld)", (long long)d->M);
+  }
+  if (kind == ROUTE_SMALL) {
+    in.kernel = DVT_GEMM_K_SMALL;
+    in.tile_m = dvt_gemm_small_tile(d->M, d->N, d->a_kmajor != 0, d->b_kmajor != 0);
+    in.colsum = d->colsum_out ? DVT_GEMM_CS_FUSED : DVT_GEMM_CS_NONE;
+  } else {
+    DVT_REQUIRE(!d->colsum_out || d->workspace, "dvt_gemm: colsum_out needs a workspace (dvt_gemm_workspace_bytes)");
+    in.colsum = d->colsum_out ? DVT_GEMM_CS_ALONE : DVT_GEMM_CS_NONE;
+  }
+  if (kind == ROUTE_MFMA) {
+    const GemmPlan pl = r->pl = with_workspace(d, r->route.pl);
+    const int cfg = pl.use256 ? dvt_gemm_dma_cfg(pl.cfg, d->a_kmajor != 0, d->b_kmajor != 0, d->epilogue, pl.split > 1,
+                                                 d->out_dtype == DVT_F32)
+                              : -1;
+    in.kernel = cfg < 0 ? DVT_GEMM_K_MFMA128 : cfg == 8 ? DVT_GEMM_K_DMA224 : DVT_GEMM_K_DMA;
+    in.cfg = cfg;
+    in.split = pl.split;
+    in.k_per_split = pl.kps;
+    if (colsum_fused(d, pl)) in.colsum = DVT_GEMM_CS_FUSED;
+    if (pl.split > 1) in.reduce = split_reduce_kind(d);
+  } else if (kind == ROUTE_GENERIC) {
+    in.kernel = generic_kernel_kind(d);
+  }
+  in.a_kmajor = d->a_kmajor != 0;
+  in.b_kmajor = d->b_kmajor != 0;
+  in.out_form = in.split > 1 ? 2 : d->out_dtype == DVT_F32 ? 1 : 0;
+  in.epilogue = in.out_form == 2 && in.kernel != DVT_GEMM_K_MFMA128 ? DVT_EPI_NONE : d->epilogue;
+  if (d->carry && d->carry->valid)   // rides in the grid tail of a one-slice LDS-DMA launch, else runs first on its own
+    in.carry = (in.kernel == DVT_GEMM_K_DMA || in.kernel == DVT_GEMM_K_DMA224) && in.split == 1 ? DVT_GEMM_CARRY_TAIL
+                                                                                                  : pending_reduce_kind(d->carry);
+  return DVT_OK;
+}
+
 // the pending reduce as a launch of its own, any form of it (plain, fused bias gradient, convolution scatter)
 __global__ void splitk_reduce_pending_kernel(const dvt_splitk_pending q) {
   splitk_reduce_f32_part(q, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
@@ -866,7 +965,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_conv_tiled_kernel(const dvt
 
 static int launch_pending_reduce(const dvt_splitk_pending* q, hipStream_t st) {
   if (!q || !q->valid) return DVT_OK;
-  if (q->splits >= 64 && !q->cs_slab && q->M * q->N <= ((int64_t)1 << 20)) {
+  if (pending_reduce_kind(q) == DVT_GEMM_CARRY_WIDE) {
     hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3((unsigned)dvt_cdiv(q->M * q->N / 8, 32)), dim3(256), 0, st, *q);
     DVT_LAUNCH_CHECK("dvt_gemm(splitk reduce, many slabs)");
     return DVT_OK;
@@ -963,18 +1062,35 @@ size_t dvt_gemm_workspace_bytes(const dvt_gemm_desc* d) {
   return align256(slab) + cs;
 }
 
-int dvt_gemm(const dvt_gemm_desc* d, dvt_stream_t stream) {
-  int rc = check_desc(d);
+int dvt_gemm_plan(const dvt_gemm_desc* d, dvt_gemm_plan_info* info) {
+  DVT_REQUIRE(info, "dvt_gemm_plan: null info");
+  GemmResolved r;
+  const int rc = resolve_gemm(d, &r);
   if (rc) return rc;
-  if (d->M == 0 || d->N == 0) return DVT_OK;
-  hipStream_t st = (hipStream_t)stream;
-  DVT_REQUIRE(!d->colsum_out || !d->a_kmajor, "dvt_gemm: colsum_out needs an mn-major A");
+  *info = r.info;
+  return DVT_OK;
+}
 
-  const GemmRoute route = route_gemm(d);
-  if (d->defer_reduce) {
-    DVT_REQUIRE(d->pending, "dvt_gemm: defer_reduce needs a pending descriptor to fill");
-    d->pending->valid = 0;
-  }
+int dvt_gemm_pair_plan(const dvt_gemm_desc* wgrad, const dvt_gemm_desc* dgrad, dvt_gemm_plan_info* wgrad_info,
+                       dvt_gemm_plan_info* dgrad_info) {
+  DVT_REQUIRE(wgrad_info && dgrad_info, "dvt_gemm_pair_plan: null info");
+  int rc = dvt_gemm_plan(wgrad, wgrad_info);
+  if (rc) return rc;
+  rc = dvt_gemm_plan(dgrad, dgrad_info);
+  if (rc) return rc;
+  if (pair_fusable(wgrad, dgrad)) wgrad_info->kernel = dgrad_info->kernel = DVT_GEMM_K_SMALL_PAIR;
+  return DVT_OK;
+}
+
+int dvt_gemm(const dvt_gemm_desc* d, dvt_stream_t stream) {
+  GemmResolved res;
+  int rc = resolve_gemm(d, &res);
+  if (rc) return rc;
+  if (res.info.kernel == DVT_GEMM_K_NONE) return DVT_OK;
+  hipStream_t st = (hipStream_t)stream;
+
+  const GemmRoute route = res.route;
+  if (d->defer_reduce) d->pending->valid = 0;
   // a reduce carried over from an earlier call rides in this launch's grid tail when this is a one-slice LDS-DMA launch;
   // every other route performs it first, as a launch of its own
   const dvt_splitk_pending* carry = d->carry && d->carry->valid ? d->carry : nullptr;
@@ -984,12 +1100,6 @@ int dvt_gemm(const dvt_gemm_desc* d, dvt_stream_t stream) {
     if (rc) return rc;
     carry = nullptr;
   }
-  if (d->residual_f32 && d->epilogue == DVT_EPI_RESIDUAL) {
-    DVT_REQUIRE(d->out_dtype == DVT_F32 && d->ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(d->residual) & 15u) == 0,
-                "dvt_gemm: an fp32 residual needs an fp32 output, ldr %% 4 == 0 and a 16-byte aligned buffer");
-    if (route.kind != ROUTE_SMALL)
-      DVT_UNSUPPORTED("dvt_gemm: the fp32 residual epilogue is served for launch-bound shapes only (M = %lld)", (long long)d->M);
-  }
   if (route.kind == ROUTE_SMALL) {
     const GemmParams p = small_params(d);
     rc = dvt_gemm_small_launch(p, d->a_kmajor != 0, d->b_kmajor != 0, st);
@@ -997,14 +1107,8 @@ int dvt_gemm(const dvt_gemm_desc* d, dvt_stream_t stream) {
       return dvt_fail(DVT_ERR_UNSUPPORTED, "dvt_gemm: the panel-streaming kernel has no instantiation for a shape its planner accepted");
     return rc;
   }
-  DVT_REQUIRE(!d->colsum_out || d->workspace, "dvt_gemm: colsum_out needs a workspace (dvt_gemm_workspace_bytes)");
   if (route.kind == ROUTE_MFMA) {
-    GemmPlan pl = route.pl;
-    if (pl.split > 1 && !d->workspace) {   // no scratch: fall back to an unsplit 128x128 launch
-      pl.use256 = false;
-      pl.split = 1;
-      pl.kps = (int)(dvt_cdiv(d->K, BK) * BK);
-    }
+    GemmPlan pl = res.pl;                  // (no scratch for a planned split: an unsplit 128x128 launch)
     int split = pl.split;
     GemmParams p{};
     p.A = (const bf16*)d->A; p.B = (const bf16*)d->B; p.C = d->C;
@@ -1020,8 +1124,7 @@ int dvt_gemm(const dvt_gemm_desc* d, dvt_stream_t stream) {
     // bias gradient fused into the LDS-DMA weight-gradient kernel (split-K slab path, cfg 0)
     const size_t slab_bytes = split > 1 ? align256((size_t)split * (size_t)d->M * (size_t)d->N * sizeof(float)) : 0;
     float* cs_scratch = d->colsum_out ? (float*)((char*)d->workspace + slab_bytes) : nullptr;
-    const bool cs_fused = d->colsum_out && pl.use256 && (pl.cfg == 0 || pl.cfg == 5) && split > 1 && !d->a_kmajor && !d->b_kmajor &&
-                          d->epilogue == DVT_EPI_NONE && p.out_f32;
+    const bool cs_fused = colsum_fused(d, pl);
     p.colsum_slab = cs_fused ? cs_scratch : nullptr;
     if (d->colsum_out && !cs_fused) {   // same semantics through the stand-alone reduction
       rc = dvt_colsum(d->A, d->lda, d->colsum_out, cs_scratch, d->K, d->M, d->in_dtype, d->colsum_accumulate, stream);
@@ -1069,11 +1172,11 @@ int dvt_gemm(const dvt_gemm_desc* d, dvt_stream_t stream) {
       int64_t blocks = dvt_cdiv(nvec, 256);
       const int64_t cap = (int64_t)dvt_num_cus() * 8;
       if (blocks > cap) blocks = cap;
-      const bool plain = d->epilogue == DVT_EPI_NONE && !d->bias && d->alpha == 1.0f;
-      if (!plain)
+      const int reduce = res.info.reduce;
+      if (reduce == DVT_GEMM_R_EPILOGUE)
         DVT_DISPATCH_16BIT(d->in_dtype, E, hipLaunchKernelGGL((splitk_reduce_epi_kernel<E>), dim3((unsigned)blocks),
                                                               dim3(256), 0, st, (const float*)p.slab, split, p));
-      else if (p.out_f32 && d->defer_reduce) {          // left to the call that receives *pending as its `carry`
+      else if (reduce == DVT_GEMM_R_DEFERRED) {          // left to the call that receives *pending as its `carry`
         dvt_splitk_pending* q = d->pending;
         q->slab = p.slab; q->splits = split; q->valid = 1; q->M = p.M; q->N = p.N; q->C = (float*)d->C; q->ldc = d->ldc;
         q->accumulate = d->accumulate; q->cs_accumulate = d->colsum_accumulate;
@@ -1107,12 +1210,12 @@ int dvt_gemm(const dvt_gemm_desc* d, dvt_stream_t stream) {
   g.accumulate = d->accumulate; g.bias = d->bias; g.residual = d->residual; g.ldr = d->ldr;
   g.aux = d->aux; g.ldaux = d->ldaux; g.alpha = d->alpha;
   const int64_t outs = d->M * d->N;
-  if (outs <= 16384 && d->K >= 128) {            // one wave per output element
+  if (res.info.kernel == DVT_GEMM_K_TINY_WAVE) {   // one wave per output element
     DVT_DISPATCH_DTYPE(d->in_dtype, T, hipLaunchKernelGGL((gemm_tiny_kernel<T, true>), dim3((unsigned)dvt_cdiv(outs, 4)), dim3(256), 0, st, g));
     DVT_LAUNCH_CHECK("dvt_gemm(tiny)");
     return DVT_OK;
   }
-  if (outs <= 65536 && d->K <= 32) {             // one thread per output element
+  if (res.info.kernel == DVT_GEMM_K_TINY_THREAD) { // one thread per output element
     DVT_DISPATCH_DTYPE(d->in_dtype, T, hipLaunchKernelGGL((gemm_tiny_kernel<T, false>), dim3((unsigned)dvt_cdiv(outs, 256)), dim3(256), 0, st, g));
     DVT_LAUNCH_CHECK("dvt_gemm(tiny)");
     return DVT_OK;

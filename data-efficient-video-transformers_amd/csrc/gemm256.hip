@@ -760,23 +760,23 @@ int launch_cfg(const GemmParams& pin, bool ak, bool bk, int split, hipStream_t s
   if (split != 1) p.pig_blocks = 0;        // (the caller only hands a carried reduce to one-slice launches)
   const dim3 grid((unsigned)(tiles_m * p.tiles_n + p.pig_blocks), 1, (unsigned)split), block(C::NW * 64);
   const int e = p.epilogue;
+  // combination not instantiated: the caller falls back to the 128x128 kernel
+  if (!dvt_gemm_dma_instantiated(CFG, ak, bk, e, p.slab != nullptr, p.out_f32 != 0)) return 1;
   if (p.slab) {
-    if (!ak && !bk) return launch_one<E, false, false, CFG, DVT_EPI_NONE, OUT_SLAB>(p, grid, block, kSmem, st);
-    if (ak && bk) return launch_one<E, true, true, CFG, DVT_EPI_NONE, OUT_SLAB>(p, grid, block, kSmem, st);
-    if (ak && !bk) return launch_one<E, true, false, CFG, DVT_EPI_NONE, OUT_SLAB>(p, grid, block, kSmem, st);
-  } else if (p.out_f32) {
-    if (!ak && !bk && e == DVT_EPI_NONE) return launch_one<E, false, false, CFG, DVT_EPI_NONE, OUT_F32>(p, grid, block, kSmem, st);
-  } else if (ak && bk) {
+    if (!ak) return launch_one<E, false, false, CFG, DVT_EPI_NONE, OUT_SLAB>(p, grid, block, kSmem, st);
+    if (bk) return launch_one<E, true, true, CFG, DVT_EPI_NONE, OUT_SLAB>(p, grid, block, kSmem, st);
+    return launch_one<E, true, false, CFG, DVT_EPI_NONE, OUT_SLAB>(p, grid, block, kSmem, st);
+  }
+  if (p.out_f32) return launch_one<E, false, false, CFG, DVT_EPI_NONE, OUT_F32>(p, grid, block, kSmem, st);
+  if (bk) {
     if (e == DVT_EPI_NONE) return launch_one<E, true, true, CFG, DVT_EPI_NONE, OUT_BF16>(p, grid, block, kSmem, st);
     if (e == DVT_EPI_GELU) return launch_one<E, true, true, CFG, DVT_EPI_GELU, OUT_BF16>(p, grid, block, kSmem, st);
     if (e == DVT_EPI_RELU) return launch_one<E, true, true, CFG, DVT_EPI_RELU, OUT_BF16>(p, grid, block, kSmem, st);
-    if (e == DVT_EPI_RESIDUAL) return launch_one<E, true, true, CFG, DVT_EPI_RESIDUAL, OUT_BF16>(p, grid, block, kSmem, st);
-  } else if (ak && !bk) {
-    if (e == DVT_EPI_NONE) return launch_one<E, true, false, CFG, DVT_EPI_NONE, OUT_BF16>(p, grid, block, kSmem, st);
-    if (e == DVT_EPI_DGELU) return launch_one<E, true, false, CFG, DVT_EPI_DGELU, OUT_BF16>(p, grid, block, kSmem, st);
-    if (e == DVT_EPI_DRELU) return launch_one<E, true, false, CFG, DVT_EPI_DRELU, OUT_BF16>(p, grid, block, kSmem, st);
+    return launch_one<E, true, true, CFG, DVT_EPI_RESIDUAL, OUT_BF16>(p, grid, block, kSmem, st);
   }
-  return 1;   // combination not instantiated: caller falls back to the 128x128 kernel
+  if (e == DVT_EPI_NONE) return launch_one<E, true, false, CFG, DVT_EPI_NONE, OUT_BF16>(p, grid, block, kSmem, st);
+  if (e == DVT_EPI_DGELU) return launch_one<E, true, false, CFG, DVT_EPI_DGELU, OUT_BF16>(p, grid, block, kSmem, st);
+  return launch_one<E, true, false, CFG, DVT_EPI_DRELU, OUT_BF16>(p, grid, block, kSmem, st);
 }
 
 template <typename E, int CFG>
@@ -862,11 +862,10 @@ int launch_224(const GemmParams& pin, bool bk, hipStream_t st) {
   p.stream_out = (int64_t)p.M * p.N * 2 >= (int64_t)180 * 1000000;
   p.tiles_n = (int)dvt_cdiv(p.N, C::TN);
   const dim3 grid((unsigned)(dvt_cdiv(p.M, C::TM) * p.tiles_n + p.pig_blocks), 1, 1), block(C::NW * 64);
-  if (p.slab || p.out_f32) return 1;
-  if (bk && p.epilogue == DVT_EPI_NONE) return launch_one<E, true, true, 8, DVT_EPI_NONE, OUT_BF16>(p, grid, block, kSmem, st);
-  if (bk && p.epilogue == DVT_EPI_RESIDUAL) return launch_one<E, true, true, 8, DVT_EPI_RESIDUAL, OUT_BF16>(p, grid, block, kSmem, st);
-  if (!bk && p.epilogue == DVT_EPI_NONE) return launch_one<E, true, false, 8, DVT_EPI_NONE, OUT_BF16>(p, grid, block, kSmem, st);
-  return 1;
+  if (!dvt_gemm_dma_instantiated(8, true, bk, p.epilogue, p.slab != nullptr, p.out_f32 != 0)) return 1;
+  if (!bk) return launch_one<E, true, false, 8, DVT_EPI_NONE, OUT_BF16>(p, grid, block, kSmem, st);
+  if (p.epilogue == DVT_EPI_RESIDUAL) return launch_one<E, true, true, 8, DVT_EPI_RESIDUAL, OUT_BF16>(p, grid, block, kSmem, st);
+  return launch_one<E, true, true, 8, DVT_EPI_NONE, OUT_BF16>(p, grid, block, kSmem, st);
 }
 int dvt_gemm_dma_launch_224(const GemmParams& p, bool b_kmajor, hipStream_t st) {
   return p.elem == DVT_F16 ? launch_224<f16>(p, b_kmajor, st) : launch_224<bf16>(p, b_kmajor, st);

@@ -155,6 +155,26 @@ int dvt_conv_dma_launch_split(const GemmParams& p, int split, hipStream_t st);  
 int dvt_conv_wgrad_dma_launch_c6(const GemmParams& p, int split, int cfg, hipStream_t st);                             // gemm256_pp.hip
 int dvt_gemm_dma_launch_224(const GemmParams& p, bool b_kmajor, hipStream_t st);                                          // gemm256_pp.hip
 int dvt_gemm_dma_launch_pp(const GemmParams& p, bool a_kmajor, bool b_kmajor, int split, hipStream_t st);   // gemm256_pp.hip
+// The plain-GEMM instantiations of the LDS-DMA kernel (gemm256.hip: launch_cfg, launch_224): is this (configuration,
+// layout, epilogue, output) combination compiled?  slab = split-K partials (the epilogue is then applied by the reduce).
+// The launchers return 1 ("not instantiated") exactly where this says no, and dvt_gemm_plan asks the same question.
+inline bool dvt_gemm_dma_instantiated(int cfg, bool ak, bool bk, int epi, bool slab, bool out_f32) {
+  if (cfg == 8) return ak && !slab && !out_f32 && (epi == DVT_EPI_NONE || (bk && epi == DVT_EPI_RESIDUAL));
+  if (slab) return ak || !bk;
+  if (out_f32) return !ak && !bk && epi == DVT_EPI_NONE;
+  if (ak && bk) return epi == DVT_EPI_NONE || epi == DVT_EPI_GELU || epi == DVT_EPI_RELU || epi == DVT_EPI_RESIDUAL;
+  if (ak) return epi == DVT_EPI_NONE || epi == DVT_EPI_DGELU || epi == DVT_EPI_DRELU;
+  return false;
+}
+// The configuration dvt_gemm_dma_launch runs for a planned one (8 without a 224-row instantiation runs as 5), or -1: no
+// instantiation, the caller falls back to the 128x128 register-staged kernel.
+inline int dvt_gemm_dma_cfg(int cfg, bool ak, bool bk, int epi, bool slab, bool out_f32) {
+  if (cfg == 8) {
+    if (dvt_gemm_dma_instantiated(8, ak, bk, epi, slab, out_f32)) return 8;
+    cfg = 5;
+  }
+  return dvt_gemm_dma_instantiated(cfg, ak, bk, epi, slab, out_f32) ? cfg : -1;
+}
 // launch-bound shapes (gemm_small.hip): tile height (0 = shape / layout not taken), launch (1 = no instantiation)
 int dvt_gemm_small_tile(int64_t M, int64_t N, bool a_kmajor, bool b_kmajor);
 int dvt_gemm_small_launch(const GemmParams& p, bool a_kmajor, bool b_kmajor, hipStream_t st);

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -444,9 +444,11 @@ def _gemm_desc(A: Tensor, B: Tensor, M: int, N: int, K: int, *, a_kmajor: bool, 
                out: Optional[Tensor] = None, out_dtype: Optional[torch.dtype] = None, epilogue: int = L.EPI_NONE,
                bias: Optional[Tensor] = None, residual: Optional[Tensor] = None, aux: Optional[Tensor] = None,
                accumulate: bool = False, alpha: float = 1.0, split_k: int = 0, colsum_out: Optional[Tensor] = None,
-               colsum_accumulate: bool = False):
-    """-> (dvt_gemm_desc, out): argument checks, output allocation and descriptor of one product."""
-    _need_cuda(A, B, bias, residual, aux)
+               colsum_accumulate: bool = False, _launch: bool = True):
+    """-> (dvt_gemm_desc, out): argument checks, output allocation and descriptor of one product (``_launch`` False: for
+    a plan query, tensors on any device)."""
+    if _launch:
+        _need_cuda(A, B, bias, residual, aux)
     assert A.dtype == B.dtype
     if out_dtype is None:
         out_dtype = A.dtype
@@ -521,6 +523,69 @@ def gemm(A: Tensor, B: Tensor, M: int, N: int, K: int, *, a_kmajor: bool, b_kmaj
         return (out, pending) if defer_reduce else out
     L.check(lib.dvt_gemm(C.byref(d), _stream()), "dvt_gemm")
     return (out, pending) if defer_reduce else out
+
+
+class GemmPlan(NamedTuple):
+    """What one dvt_gemm call launches (dvt_gemm_plan): the kernel family, its LDS-DMA configuration (-1: none), the K
+    slices and K per slice, the panel kernel's tile rows, what sums the slabs, how colsum_out is produced and what becomes
+    of a carried reduce; then the instantiation: operand layouts, epilogue and output form ("in" = the operands' type,
+    "f32", "slab" = fp32 split-K partials).  Names: GEMM_KERNELS, GEMM_REDUCES, GEMM_COLSUMS, GEMM_CARRIES, GEMM_OUTS."""
+    kernel: str
+    cfg: int = -1
+    split: int = 1
+    k_per_split: int = 0
+    tile_m: int = 0
+    reduce: str = "none"
+    colsum: str = "none"
+    carry: str = "none"
+    a_kmajor: bool = True
+    b_kmajor: bool = True
+    epilogue: int = L.EPI_NONE
+    out: str = "in"
+
+
+GEMM_OUTS = ("in", "f32", "slab")
+GEMM_KERNELS = ("none", "small", "small_pair", "dma", "dma224", "mfma128", "generic64", "tiny_wave", "tiny_thread")
+GEMM_REDUCES = ("none", "plain", "epilogue", "deferred")
+GEMM_COLSUMS = ("none", "fused", "alone")
+GEMM_CARRIES = ("none", "tail", "alone", "wide", "conv")
+
+
+def _plan_tuple(q) -> GemmPlan:
+    return GemmPlan(GEMM_KERNELS[q.kernel], q.cfg, q.split, q.k_per_split, q.tile_m, GEMM_REDUCES[q.reduce],
+                    GEMM_COLSUMS[q.colsum], GEMM_CARRIES[q.carry], bool(q.a_kmajor), bool(q.b_kmajor), q.epilogue,
+                    GEMM_OUTS[q.out_form])
+
+
+def _plan_desc(A: Tensor, B: Tensor, M: int, N: int, K: int, *, defer_reduce: bool = False, carry=None, **kw):
+    """the descriptor ``gemm`` would pass for these arguments, with a stand-in workspace address where it would pass one"""
+    d, out = _gemm_desc(A, B, M, N, K, _launch=False, **kw)
+    keep = [out]
+    if defer_reduce:
+        keep.append(L.SplitKPending())
+        d.defer_reduce, d.pending = 1, C.pointer(keep[-1])
+    if carry is not None:
+        d.carry = C.pointer(carry)
+    d.workspace = 256 if L.load().dvt_gemm_workspace_bytes(C.byref(d)) > 0 else None
+    return d, keep
+
+
+def gemm_plan(A: Tensor, B: Tensor, M: int, N: int, K: int, **kw) -> GemmPlan:
+    """What ``gemm`` launches for the same arguments (dvt_gemm_plan: the launcher's own decisions, no launch, no device
+    needed -- the tensors may live anywhere, only their addresses, strides and types count)."""
+    d, _keep = _plan_desc(A, B, M, N, K, **kw)
+    q = L.GemmPlanInfo()
+    L.check(L.load().dvt_gemm_plan(C.byref(d), C.byref(q)), "dvt_gemm_plan")
+    return _plan_tuple(q)
+
+
+def gemm_pair_plan(wgrad: dict, dgrad: dict) -> Tuple[GemmPlan, GemmPlan]:
+    """dvt_gemm_pair's launches for two products, each given as the keyword arguments of ``gemm`` (A, B, M, N, K, ...)."""
+    wd, _kw = _plan_desc(**wgrad)
+    gd, _kg = _plan_desc(**dgrad)
+    qw, qg = L.GemmPlanInfo(), L.GemmPlanInfo()
+    L.check(L.load().dvt_gemm_pair_plan(C.byref(wd), C.byref(gd), C.byref(qw), C.byref(qg)), "dvt_gemm_pair_plan")
+    return _plan_tuple(qw), _plan_tuple(qg)
 
 
 def gemm_is_launch_bound(M: int, N: int, K: int, dtype: torch.dtype, *, a_kmajor: bool = True, b_kmajor: bool = True) -> bool:

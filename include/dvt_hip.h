@@ -322,6 +322,57 @@ int dvt_gemm(const dvt_gemm_desc* desc, dvt_stream_t stream);
 /* Which kernel family dvt_gemm would take for desc (no launch): 0 = the panel-streaming kernel of the launch-bound shapes
  * (the only one that serves residual_f32), 1 = the LDS-DMA / register-staged MFMA kernels, 2 = the generic fp32 kernel. */
 int dvt_gemm_route(const dvt_gemm_desc* desc);
+/* What dvt_gemm would launch for desc, taken from the same decisions the launcher makes (ABI v5 addition; host only, runs
+ * without a device: the CU-count dependent thresholds then assume the MI355X's 256).  The workspace, defer_reduce and
+ * carry fields of desc count: a planned split with no workspace runs unsplit on the 128x128 kernel, and `carry` reports
+ * what becomes of a valid desc->carry.  Returns what dvt_gemm returns for a descriptor it refuses, else DVT_OK. */
+enum dvt_gemm_kernel {
+  DVT_GEMM_K_NONE = 0,         /* nothing to launch (M == 0 or N == 0) */
+  DVT_GEMM_K_SMALL = 1,        /* gemm_small_kernel (panel streaming, tile_m rows per tile) */
+  DVT_GEMM_K_SMALL_PAIR = 2,   /* gemm_small_pair_kernel (dvt_gemm_pair_plan only) */
+  DVT_GEMM_K_DMA = 3,          /* gemm_dma_kernel, 256-row tiles, configuration cfg */
+  DVT_GEMM_K_DMA224 = 4,       /* gemm_dma_kernel, configuration 8 (224-row tiles) */
+  DVT_GEMM_K_MFMA128 = 5,      /* gemm_mfma_kernel (128x128 register-staged) */
+  DVT_GEMM_K_GENERIC64 = 6,    /* gemm_generic_kernel (64x64 FMA tiles) */
+  DVT_GEMM_K_TINY_WAVE = 7,    /* gemm_tiny_kernel, one wave per output */
+  DVT_GEMM_K_TINY_THREAD = 8   /* gemm_tiny_kernel, one thread per output */
+};
+enum dvt_gemm_reduce {         /* what sums the split-K slabs */
+  DVT_GEMM_R_NONE = 0,         /* no split */
+  DVT_GEMM_R_PLAIN = 1,        /* splitk_reduce_kernel (with the fused bias gradient's rows where colsum is FUSED) */
+  DVT_GEMM_R_EPILOGUE = 2,     /* splitk_reduce_epi_kernel (bias / alpha / activation / residual after the sum) */
+  DVT_GEMM_R_DEFERRED = 3      /* left undone in *desc->pending */
+};
+enum dvt_gemm_colsum {         /* how colsum_out is produced */
+  DVT_GEMM_CS_NONE = 0,
+  DVT_GEMM_CS_FUSED = 1,       /* by the GEMM launch itself (panel kernel; LDS-DMA slabs summed by the reduce) */
+  DVT_GEMM_CS_ALONE = 2        /* by dvt_colsum, a launch of its own */
+};
+enum dvt_gemm_carry {          /* what becomes of a valid desc->carry */
+  DVT_GEMM_CARRY_NONE = 0,
+  DVT_GEMM_CARRY_TAIL = 1,     /* rides in the grid tail of this call's LDS-DMA launch */
+  DVT_GEMM_CARRY_ALONE = 2,    /* launched on its own first: splitk_reduce_kernel */
+  DVT_GEMM_CARRY_WIDE = 3,     /* launched on its own first: splitk_reduce_wide_kernel (>= 64 slices, M*N <= 2^20) */
+  DVT_GEMM_CARRY_CONV = 4      /* launched on its own first: a convolution-scatter reduce */
+};
+typedef struct dvt_gemm_plan_info {
+  int32_t route;        /* as dvt_gemm_route */
+  int32_t kernel;       /* enum dvt_gemm_kernel */
+  int32_t cfg;          /* LDS-DMA configuration (DMA / DMA224), else -1 */
+  int32_t split;        /* K slices (1: none) */
+  int32_t k_per_split;  /* DMA / MFMA128: K per slice, a multiple of 64; else 0 */
+  int32_t tile_m;       /* SMALL / SMALL_PAIR: rows per tile (32 or 64); else 0 */
+  int32_t reduce;       /* enum dvt_gemm_reduce */
+  int32_t colsum;       /* enum dvt_gemm_colsum */
+  int32_t carry;        /* enum dvt_gemm_carry */
+  /* the instantiation launched: operand layouts, epilogue (DVT_EPI_NONE where the reduce applies it: LDS-DMA slabs) and
+   * output form (0 = in_dtype, 1 = f32, 2 = f32 split-K slabs) */
+  int32_t a_kmajor, b_kmajor, epilogue, out_form;
+} dvt_gemm_plan_info;
+int dvt_gemm_plan(const dvt_gemm_desc* desc, dvt_gemm_plan_info* info);
+/* dvt_gemm_pair's launches: both SMALL_PAIR when they are one launch (dvt_gemm_pair_fused), else dvt_gemm_plan of each. */
+int dvt_gemm_pair_plan(const dvt_gemm_desc* wgrad, const dvt_gemm_desc* dgrad, dvt_gemm_plan_info* wgrad_info,
+                       dvt_gemm_plan_info* dgrad_info);
 /* The two products of one Linear's backward (src/models/vit.py:20-25,39-43: dW = dy^T x with both operands mn-major,
  * dx = dy W with A k-major / B mn-major) as ONE launch when both are launch-bound shapes (the 33-token temporal encoder,
  * the CLS-row layers: a few hundred rows): they are independent, each fills a fraction of the chip, and between dependent
