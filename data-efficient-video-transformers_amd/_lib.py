@@ -72,6 +72,11 @@ class GemmPlanInfo(C.Structure):
                                            "a_kmajor", "b_kmajor", "epilogue", "out_form")]
 
 
+class AttnPlanInfo(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("family", "count", "count2", "waves", "waves2", "patch", "patch2", "workspace")] + \
+        [("lds", c_i64), ("lds2", c_i64)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("y", C.c_void_p), ("N", C.c_int64)] + \
                [(n, C.c_int32) for n in ("H", "W", "C", "Cout", "kh", "kw", "sh", "sw", "ph", "pw", "dtype")] + \
@@ -182,6 +187,7 @@ SIGNATURES = {
     "dvt_attention_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(AttnDesc)]),
     "dvt_attention_fwd": (c_int, [C.POINTER(AttnDesc), c_p]),
     "dvt_attention_bwd": (c_int, [C.POINTER(AttnDesc), c_p]),
+    "dvt_attention_plan": (c_int, [C.POINTER(AttnDesc), c_int, C.POINTER(AttnPlanInfo)]),
     "dvt_attn_cls_supported": (c_int, [C.POINTER(AttnClsDesc)]),
     "dvt_attn_cls_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(AttnClsDesc)]),
     "dvt_attn_cls_fwd": (c_int, [C.POINTER(AttnClsDesc), c_p]),

@@ -1,7 +1,7 @@
 // attention.hip -- fused softmax(q k^T * scale) v, forward and backward.
 // Scores are never written to HBM.
 //
-// 16-bit fast path (bf16 / fp16, dh == 64, Lk <= 608): one workgroup per (batch, head).
+// 16-bit fast path (bf16 / fp16, dh == 64, Lk <= 640): one workgroup per (batch, head).
 //   forward   K and V of the head are staged once in LDS as [key][64] images whose
 //             32-byte units are XOR-swizzled by (key>>1)&3 -- conflict-free both
 //             for ds_read_b128 row reads (K as the A operand of S^T = K Q^T) and
@@ -10,7 +10,7 @@
 //             MFMA *column* (lane & 15), so a lane owns one query, and the S^T
 //             accumulators are, converted to 16 bits, directly the B operand of
 //             the P V product (k order permuted identically on the V^T side).
-//             Lk <= 224: the whole 16 x Lk score tile stays in registers (one row
+//             Lk <= 352: the whole 16 x Lk score tile stays in registers (one row
 //             maximum, no rescale, no per-step cross-lane exchange); longer: online
 //             softmax over 32-key steps.
 //   backward  two kernels with the same anatomy, no atomics, bitwise reproducible:
@@ -20,10 +20,13 @@
 //                   reads lse and delta)
 //             7 MFMA products instead of the minimal 5, in exchange for no
 //             cross-wave reduction of any gradient.  Key / query loops are unrolled at
-//             compile time up to 256 (template parameter), rolled beyond.
+//             compile time up to 352 (template parameter), rolled beyond.  Lengths that pad
+//             to the same multiple of 32, at most 224, take the one-pass backward instead.
 //   staging   all loads of a batch before the first LDS write (one memory round trip);
 //   stores    output tiles transposed through a per-wave 2 KiB LDS patch and written as
-//             whole 128-byte rows.
+//             whole 128-byte rows where the patches keep the occupancy the images allow
+//             (with_patches), per lane otherwise.
+// dvt_attention_plan reports which of these a descriptor takes (resolve_fwd / resolve_bwd).
 // generic path: any dtype / head dim / length that fits LDS, fp32 FMA, one wave
 // per row (fp32 parity mode; dh = 448 / 224 / 256 / 32 heads of the reference's
 // 14-token encoders; attention-probability dropout).
@@ -1569,6 +1572,94 @@ int set_lds(K kernel, size_t bytes) {
   return 0;
 }
 
+// The decisions dvt_attention_fwd / _bwd take, each in one place: they launch by them and dvt_attention_plan reports them.
+// Fills p (patch_off of the launches included) and info; refuses what the launchers refuse.  Needs no device.
+int resolve_fwd(const dvt_attn_desc* d, AttnParams& p, dvt_attn_plan_info& r) {
+  r = dvt_attn_plan_info{};
+  r.patch = r.patch2 = -1;
+  int rc = fill_params(d, p, false, "dvt_attention_fwd");
+  if (rc) return rc;
+  if (p.B == 0) return DVT_OK;
+  if (q1_ok(d, p)) {                             // one query per (b, h): the CLS-row form of a stack's last layer
+    r.family = DVT_ATTN_F_Q1; r.waves = 4; r.lds = (int64_t)4 * p.Lkp * sizeof(float);
+    return DVT_OK;
+  }
+  if (mfma_fwd_ok(d, p)) {
+    const size_t lds_img = (size_t)2 * p.Lkp * kRowBytes;
+    const int nkp = p.Lkp >> 5;
+    r.waves = pick_waves((p.Lq + 15) / 16, lds_img, nkp > 7 && nkp <= 11 ? 12 : 16);
+    r.lds = (int64_t)with_patches(lds_img, r.waves, p);
+    r.patch = p.patch_off >= 0;
+    r.family = nkp <= 11 ? DVT_ATTN_F_RES : DVT_ATTN_F_ONLINE;  // scores of up to 352 keys stay in registers
+    r.count = nkp <= 11 ? nkp : 0;
+    return DVT_OK;
+  }
+  const int nt_s = p.Lq * p.dh >= 4096 ? 512 : 256;
+  const size_t lds_s = ((size_t)(p.Lq + 2 * p.Lk) * small_dhp(p.dh) +
+                        (size_t)small_parts(p.Lq, p.Lk, nt_s) * p.Lq * small_lp(p.Lk)) * sizeof(float);
+  if (d->dtype != DVT_F32 && d->dtype != DVT_BF16 && d->dtype != DVT_F16)
+    DVT_UNSUPPORTED("dvt_attention_fwd: dtype %d not supported", d->dtype);
+  if (p.Lq <= kSmallL && p.Lk <= kSmallL && p.dh <= kSmallDh && lds_s <= (size_t)kMaxLds) {   // short sequences: a workgroup per (b, h)
+    r.family = DVT_ATTN_F_SMALL; r.waves = nt_s / 64; r.lds = (int64_t)lds_s;
+    return DVT_OK;
+  }
+  const size_t lds = (size_t)4 * (p.dh + p.Lk) * sizeof(float);
+  if (lds > (size_t)kMaxLds) DVT_UNSUPPORTED("dvt_attention_fwd: Lk = %d, dh = %d exceed the LDS budget", p.Lk, p.dh);
+  r.family = DVT_ATTN_F_GENERIC; r.waves = 4; r.lds = (int64_t)lds;
+  return DVT_OK;
+}
+
+// pq / pkv: the parameters of the dq and dk/dv launches of the PAIR family (their patch_off differ); p of every other one
+int resolve_bwd(const dvt_attn_desc* d, AttnParams& p, AttnParams& pq, AttnParams& pkv, dvt_attn_plan_info& r) {
+  r = dvt_attn_plan_info{};
+  r.patch = r.patch2 = -1;
+  int rc = fill_params(d, p, true, "dvt_attention_bwd");
+  if (rc) return rc;
+  pq = pkv = p;
+  if (p.B == 0) return DVT_OK;
+  if (q1_ok(d, p) && dvt_aligned16(d->d_o) && dvt_aligned16(d->dq) && dvt_aligned16(d->dk) && dvt_aligned16(d->dv)) {
+    r.family = DVT_ATTN_B_Q1; r.waves = 4;
+    return DVT_OK;
+  }
+  if (mfma_bwd_ok(d, p) && fused_bwd_ok(p) && !d->bwd_two_pass) {      // one pass: Q, dO, K staged once, dK / dV in registers, dQ through LDS strips
+    const int NP = p.Lkp >> 5;
+    r.family = DVT_ATTN_B_FUSED; r.count = NP;
+    r.waves = NP + 1;                              // one compute wave per 32 keys + the dQ wave
+    r.lds = (int64_t)fused_bwd_lds(NP, r.waves);
+    return DVT_OK;
+  }
+  if (mfma_bwd_ok(d, p)) {
+    const size_t img_q = (size_t)2 * p.Lkp * kRowBytes;
+    const size_t img_kv = (size_t)2 * p.Lqp * kRowBytes + (size_t)2 * p.Lqp * sizeof(float);
+    r.family = DVT_ATTN_B_PAIR; r.workspace = 1;
+    r.count = (p.Lkp >> 5) <= 11 ? p.Lkp >> 5 : 0;       // unrolled key loop up to 352 keys, rolled beyond
+    r.count2 = (p.Lqp >> 5) <= 11 ? p.Lqp >> 5 : 0;      // unrolled query loop up to 352 queries
+    r.waves = pick_waves((p.Lq + 15) / 16, img_q);
+    r.waves2 = pick_waves((p.Lk + 15) / 16, img_kv);
+    r.lds = (int64_t)with_patches(img_q, r.waves, pq);
+    r.lds2 = (int64_t)with_patches(img_kv, r.waves2, pkv);
+    r.patch = pq.patch_off >= 0; r.patch2 = pkv.patch_off >= 0;
+    return DVT_OK;
+  }
+  if (d->dtype != DVT_F32 && d->dtype != DVT_BF16 && d->dtype != DVT_F16)
+    DVT_UNSUPPORTED("dvt_attention_bwd: dtype %d not supported", d->dtype);
+  const int nt_s = p.Lq * p.dh >= 4096 ? 512 : 256;
+  const size_t lds_s = ((size_t)2 * (p.Lq + p.Lk) * small_dhp(p.dh) +
+                        (size_t)2 * small_parts(p.Lq, p.Lk, nt_s) * p.Lq * small_lp(p.Lk) +
+                        (size_t)2 * p.Lk * small_lp(p.Lq)) * sizeof(float);
+  if (p.Lq <= kSmallL && p.Lk <= kSmallL && p.dh <= kSmallDh && lds_s <= (size_t)kMaxLds) {   // short sequences: dQ, dK, dV of a (b, h) in one launch
+    r.family = DVT_ATTN_B_SMALL; r.waves = nt_s / 64; r.lds = (int64_t)lds_s;
+    return DVT_OK;
+  }
+  const size_t lds_q = (size_t)4 * (2 * p.dh + p.Lk) * sizeof(float);
+  const size_t lds_kv = (size_t)4 * (2 * p.dh + 2 * p.Lq) * sizeof(float);
+  if (lds_q > (size_t)kMaxLds || lds_kv > (size_t)kMaxLds)
+    DVT_UNSUPPORTED("dvt_attention_bwd: Lq = %d, Lk = %d, dh = %d exceed the LDS budget", p.Lq, p.Lk, p.dh);
+  r.family = DVT_ATTN_B_GENERIC; r.workspace = 1; r.waves = r.waves2 = 4;
+  r.lds = (int64_t)lds_q; r.lds2 = (int64_t)lds_kv;
+  return DVT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1578,15 +1669,22 @@ size_t dvt_attention_bwd_workspace_bytes(const dvt_attn_desc* d) {
   return (size_t)d->B * (size_t)d->H * (size_t)d->Lq * sizeof(float);
 }
 
+int dvt_attention_plan(const dvt_attn_desc* d, int bwd, dvt_attn_plan_info* info) {
+  DVT_REQUIRE(info, "dvt_attention_plan: null info");
+  AttnParams p, pq, pkv;
+  return bwd ? resolve_bwd(d, p, pq, pkv, *info) : resolve_fwd(d, p, *info);
+}
+
 int dvt_attention_fwd(const dvt_attn_desc* d, dvt_stream_t stream) {
   AttnParams p;
-  int rc = fill_params(d, p, false, "dvt_attention_fwd");
+  dvt_attn_plan_info r;
+  int rc = resolve_fwd(d, p, r);
   if (rc) return rc;
   if (p.B == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (q1_ok(d, p)) {                             // one query per (b, h): the CLS-row form of a stack's last layer
+  const size_t lds = (size_t)r.lds;
+  if (r.family == DVT_ATTN_F_Q1) {
     const dim3 grid((unsigned)dvt_cdiv((int64_t)p.B * p.H, 4)), block(256);
-    const size_t lds = (size_t)4 * p.Lkp * sizeof(float);
     DVT_DISPATCH_16BIT(d->dtype, E, {
       if (int rc_ = set_lds(attn_fwd_q1_kernel<E>, lds)) return rc_;
       hipLaunchKernelGGL((attn_fwd_q1_kernel<E>), grid, block, lds, st, p);
@@ -1594,19 +1692,15 @@ int dvt_attention_fwd(const dvt_attn_desc* d, dvt_stream_t stream) {
     DVT_LAUNCH_CHECK("dvt_attention_fwd(q1)");
     return DVT_OK;
   }
-  if (mfma_fwd_ok(d, p)) {
-    const size_t lds_img = (size_t)2 * p.Lkp * kRowBytes;
-    const int nkp = p.Lkp >> 5;
-    const int W = pick_waves((p.Lq + 15) / 16, lds_img, nkp > 7 && nkp <= 11 ? 12 : 16);
-    const size_t lds = with_patches(lds_img, W, p);
-    const dim3 grid((unsigned)(p.B * p.H)), block(64 * W);
+  if (r.family == DVT_ATTN_F_RES || r.family == DVT_ATTN_F_ONLINE) {
+    const dim3 grid((unsigned)(p.B * p.H)), block(64 * r.waves);
 #define DVT_ATTN_FWD_RES(NKP)                                                               \
   case NKP:                                                                                 \
     if (int rc_ = set_lds(attn_fwd_mfma_res_kernel<E, NKP>, lds)) return rc_;                                         \
     hipLaunchKernelGGL((attn_fwd_mfma_res_kernel<E, NKP>), grid, block, lds, st, p);        \
     break
     DVT_DISPATCH_16BIT(d->dtype, E, {
-      switch (nkp) {                             // scores of up to 352 keys stay in registers
+      switch (r.count) {                         // 0: the online kernel
         DVT_ATTN_FWD_RES(1); DVT_ATTN_FWD_RES(2); DVT_ATTN_FWD_RES(3); DVT_ATTN_FWD_RES(4);
         DVT_ATTN_FWD_RES(5); DVT_ATTN_FWD_RES(6); DVT_ATTN_FWD_RES(7); DVT_ATTN_FWD_RES(8);
         DVT_ATTN_FWD_RES(9); DVT_ATTN_FWD_RES(10); DVT_ATTN_FWD_RES(11);
@@ -1619,26 +1713,20 @@ int dvt_attention_fwd(const dvt_attn_desc* d, dvt_stream_t stream) {
     DVT_LAUNCH_CHECK("dvt_attention_fwd(mfma)");
     return DVT_OK;
   }
-  const int nt_s = p.Lq * p.dh >= 4096 ? 512 : 256;
-  const size_t lds_s = ((size_t)(p.Lq + 2 * p.Lk) * small_dhp(p.dh) +
-                        (size_t)small_parts(p.Lq, p.Lk, nt_s) * p.Lq * small_lp(p.Lk)) * sizeof(float);
-  if (p.Lq <= kSmallL && p.Lk <= kSmallL && p.dh <= kSmallDh && lds_s <= (size_t)kMaxLds) {   // short sequences: a workgroup per (b, h)
-    const dim3 grid((unsigned)(p.B * p.H)), block(nt_s);
+  if (r.family == DVT_ATTN_F_SMALL) {            // short sequences: a workgroup per (b, h)
+    const dim3 grid((unsigned)(p.B * p.H)), block(64 * r.waves);
 #define DVT_ATTN_SMALL_FWD(T)                                                   \
   do {                                                                          \
-    if (int rc_ = set_lds(attn_small_fwd_kernel<T>, lds_s)) return rc_;                                   \
-    hipLaunchKernelGGL((attn_small_fwd_kernel<T>), grid, block, lds_s, st, p);  \
+    if (int rc_ = set_lds(attn_small_fwd_kernel<T>, lds)) return rc_;                                   \
+    hipLaunchKernelGGL((attn_small_fwd_kernel<T>), grid, block, lds, st, p);  \
   } while (0)
     if (d->dtype == DVT_F32) DVT_ATTN_SMALL_FWD(float);
     else if (d->dtype == DVT_BF16) DVT_ATTN_SMALL_FWD(bf16);
-    else if (d->dtype == DVT_F16) DVT_ATTN_SMALL_FWD(f16);
-    else DVT_UNSUPPORTED("dvt_attention_fwd: dtype %d not supported", d->dtype);
+    else DVT_ATTN_SMALL_FWD(f16);
 #undef DVT_ATTN_SMALL_FWD
     DVT_LAUNCH_CHECK("dvt_attention_fwd(short)");
     return DVT_OK;
   }
-  const size_t lds = (size_t)4 * (p.dh + p.Lk) * sizeof(float);
-  if (lds > (size_t)kMaxLds) DVT_UNSUPPORTED("dvt_attention_fwd: Lk = %d, dh = %d exceed the LDS budget", p.Lk, p.dh);
   const int64_t rows = (int64_t)p.B * p.H * p.Lq;
   const dim3 grid((unsigned)dvt_cdiv(rows, 4)), block(256);
   if (d->dtype == DVT_F32) {
@@ -1647,40 +1735,37 @@ int dvt_attention_fwd(const dvt_attn_desc* d, dvt_stream_t stream) {
   } else if (d->dtype == DVT_BF16) {
     if (int rc_ = set_lds(attn_fwd_generic_kernel<bf16>, lds)) return rc_;
     hipLaunchKernelGGL((attn_fwd_generic_kernel<bf16>), grid, block, lds, st, p);
-  } else if (d->dtype == DVT_F16) {
+  } else {
     if (int rc_ = set_lds(attn_fwd_generic_kernel<f16>, lds)) return rc_;
     hipLaunchKernelGGL((attn_fwd_generic_kernel<f16>), grid, block, lds, st, p);
-  } else {
-    DVT_UNSUPPORTED("dvt_attention_fwd: dtype %d not supported", d->dtype);
   }
   DVT_LAUNCH_CHECK("dvt_attention_fwd(generic)");
   return DVT_OK;
 }
 
 int dvt_attention_bwd(const dvt_attn_desc* d, dvt_stream_t stream) {
-  AttnParams p;
-  int rc = fill_params(d, p, true, "dvt_attention_bwd");
+  AttnParams p, pq, pkv;
+  dvt_attn_plan_info r;
+  int rc = resolve_bwd(d, p, pq, pkv, r);
   if (rc) return rc;
   if (p.B == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (q1_ok(d, p) && dvt_aligned16(d->d_o) && dvt_aligned16(d->dq) && dvt_aligned16(d->dk) && dvt_aligned16(d->dv)) {
+  if (r.family == DVT_ATTN_B_Q1) {
     const dim3 grid((unsigned)dvt_cdiv((int64_t)p.B * p.H, 4)), block(256);
     DVT_DISPATCH_16BIT(d->dtype, E, hipLaunchKernelGGL((attn_bwd_q1_kernel<E>), grid, block, 0, st, p));
     DVT_LAUNCH_CHECK("dvt_attention_bwd(q1)");
     return DVT_OK;
   }
-  if (mfma_bwd_ok(d, p) && fused_bwd_ok(p) && !d->bwd_two_pass) {      // one pass: Q, dO, K staged once, dK / dV in registers, dQ through LDS strips
-    const int NP = p.Lkp >> 5;
-    const int waves = NP + 1;                      // one compute wave per 32 keys + the dQ wave
-    const size_t lds = fused_bwd_lds(NP, waves);
-    const dim3 grid((unsigned)(p.B * p.H)), block(64 * waves);
+  if (r.family == DVT_ATTN_B_FUSED) {
+    const size_t lds = (size_t)r.lds;
+    const dim3 grid((unsigned)(p.B * p.H)), block(64 * r.waves);
 #define DVT_ATTN_BWD_FUSED(N)                                                               \
   case N:                                                                                   \
     if (int rc_ = set_lds(attn_bwd_fused_kernel<E, N>, lds)) return rc_;                                              \
     hipLaunchKernelGGL((attn_bwd_fused_kernel<E, N>), grid, block, lds, st, p);             \
     break
     DVT_DISPATCH_16BIT(d->dtype, E, {
-      switch (NP) {
+      switch (r.count) {
         DVT_ATTN_BWD_FUSED(1); DVT_ATTN_BWD_FUSED(2); DVT_ATTN_BWD_FUSED(3); DVT_ATTN_BWD_FUSED(4);
         DVT_ATTN_BWD_FUSED(5); DVT_ATTN_BWD_FUSED(6); DVT_ATTN_BWD_FUSED(7);
       }
@@ -1689,16 +1774,12 @@ int dvt_attention_bwd(const dvt_attn_desc* d, dvt_stream_t stream) {
     DVT_LAUNCH_CHECK("dvt_attention_bwd(fused)");
     return DVT_OK;
   }
-  if (mfma_bwd_ok(d, p)) {
+  if (r.family == DVT_ATTN_B_PAIR) {
     DVT_REQUIRE(d->workspace, "dvt_attention_bwd: workspace (dvt_attention_bwd_workspace_bytes) required");
-    p.delta = (float*)d->workspace;             // dq kernel -> dk/dv kernel
-    const size_t img_q = (size_t)2 * p.Lkp * kRowBytes;
-    const size_t img_kv = (size_t)2 * p.Lqp * kRowBytes + (size_t)2 * p.Lqp * sizeof(float);
+    pq.delta = pkv.delta = (float*)d->workspace;   // dq kernel -> dk/dv kernel
     const dim3 grid((unsigned)(p.B * p.H));
-    const int wq = pick_waves((p.Lq + 15) / 16, img_q), wkv = pick_waves((p.Lk + 15) / 16, img_kv);
-    const dim3 block_q(64 * wq), block_kv(64 * wkv);
-    AttnParams pq = p, pkv = p;
-    const size_t lds_q = with_patches(img_q, wq, pq), lds_kv = with_patches(img_kv, wkv, pkv);
+    const dim3 block_q(64 * r.waves), block_kv(64 * r.waves2);
+    const size_t lds_q = (size_t)r.lds, lds_kv = (size_t)r.lds2;
 #define DVT_ATTN_BWD_DQ(NKP)                                                                \
   case NKP:                                                                                 \
     if (int rc_ = set_lds(attn_bwd_dq_mfma_kernel<E, NKP>, lds_q)) return rc_;                                        \
@@ -1710,7 +1791,7 @@ int dvt_attention_bwd(const dvt_attn_desc* d, dvt_stream_t stream) {
     hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<E, NQP>), grid, block_kv, lds_kv, st, pkv);  \
     break
     DVT_DISPATCH_16BIT(d->dtype, E, {
-      switch (p.Lkp >> 5) {                      // unrolled key loop up to 352 keys
+      switch (r.count) {                         // 0: the rolled key loop
         DVT_ATTN_BWD_DQ(1); DVT_ATTN_BWD_DQ(2); DVT_ATTN_BWD_DQ(3); DVT_ATTN_BWD_DQ(4);
         DVT_ATTN_BWD_DQ(5); DVT_ATTN_BWD_DQ(6); DVT_ATTN_BWD_DQ(7); DVT_ATTN_BWD_DQ(8);
         DVT_ATTN_BWD_DQ(9); DVT_ATTN_BWD_DQ(10); DVT_ATTN_BWD_DQ(11);
@@ -1718,7 +1799,7 @@ int dvt_attention_bwd(const dvt_attn_desc* d, dvt_stream_t stream) {
           if (int rc_ = set_lds(attn_bwd_dq_mfma_kernel<E, 0>, lds_q)) return rc_;
           hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<E, 0>), grid, block_q, lds_q, st, pq);
       }
-      switch (p.Lqp >> 5) {                      // unrolled query loop up to 352 queries
+      switch (r.count2) {                        // 0: the rolled query loop
         DVT_ATTN_BWD_DKV(1); DVT_ATTN_BWD_DKV(2); DVT_ATTN_BWD_DKV(3); DVT_ATTN_BWD_DKV(4);
         DVT_ATTN_BWD_DKV(5); DVT_ATTN_BWD_DKV(6); DVT_ATTN_BWD_DKV(7); DVT_ATTN_BWD_DKV(8);
         DVT_ATTN_BWD_DKV(9); DVT_ATTN_BWD_DKV(10); DVT_ATTN_BWD_DKV(11);
@@ -1732,12 +1813,9 @@ int dvt_attention_bwd(const dvt_attn_desc* d, dvt_stream_t stream) {
     DVT_LAUNCH_CHECK("dvt_attention_bwd(dkdv)");
     return DVT_OK;
   }
-  const int nt_s = p.Lq * p.dh >= 4096 ? 512 : 256;
-  const size_t lds_s = ((size_t)2 * (p.Lq + p.Lk) * small_dhp(p.dh) +
-                        (size_t)2 * small_parts(p.Lq, p.Lk, nt_s) * p.Lq * small_lp(p.Lk) +
-                        (size_t)2 * p.Lk * small_lp(p.Lq)) * sizeof(float);
-  if (p.Lq <= kSmallL && p.Lk <= kSmallL && p.dh <= kSmallDh && lds_s <= (size_t)kMaxLds) {   // short sequences: dQ, dK, dV of a (b, h) in one launch
-    const dim3 grid((unsigned)(p.B * p.H)), block(nt_s);
+  if (r.family == DVT_ATTN_B_SMALL) {            // short sequences: dQ, dK, dV of a (b, h) in one launch
+    const size_t lds_s = (size_t)r.lds;
+    const dim3 grid((unsigned)(p.B * p.H)), block(64 * r.waves);
 #define DVT_ATTN_SMALL_BWD(T)                                                   \
   do {                                                                          \
     if (int rc_ = set_lds(attn_small_bwd_kernel<T>, lds_s)) return rc_;                                   \
@@ -1745,18 +1823,14 @@ int dvt_attention_bwd(const dvt_attn_desc* d, dvt_stream_t stream) {
   } while (0)
     if (d->dtype == DVT_F32) DVT_ATTN_SMALL_BWD(float);
     else if (d->dtype == DVT_BF16) DVT_ATTN_SMALL_BWD(bf16);
-    else if (d->dtype == DVT_F16) DVT_ATTN_SMALL_BWD(f16);
-    else DVT_UNSUPPORTED("dvt_attention_bwd: dtype %d not supported", d->dtype);
+    else DVT_ATTN_SMALL_BWD(f16);
 #undef DVT_ATTN_SMALL_BWD
     DVT_LAUNCH_CHECK("dvt_attention_bwd(short)");
     return DVT_OK;
   }
   DVT_REQUIRE(d->workspace, "dvt_attention_bwd: workspace (dvt_attention_bwd_workspace_bytes) required");
   p.delta = (float*)d->workspace;
-  const size_t lds_q = (size_t)4 * (2 * p.dh + p.Lk) * sizeof(float);
-  const size_t lds_kv = (size_t)4 * (2 * p.dh + 2 * p.Lq) * sizeof(float);
-  if (lds_q > (size_t)kMaxLds || lds_kv > (size_t)kMaxLds)
-    DVT_UNSUPPORTED("dvt_attention_bwd: Lq = %d, Lk = %d, dh = %d exceed the LDS budget", p.Lq, p.Lk, p.dh);
+  const size_t lds_q = (size_t)r.lds, lds_kv = (size_t)r.lds2;
   const int64_t qrows = (int64_t)p.B * p.H * p.Lq, krows = (int64_t)p.B * p.H * p.Lk;
   const dim3 block(256);
 #define DVT_ATTN_BWD_GENERIC(T)                                                                   \
@@ -1769,8 +1843,7 @@ int dvt_attention_bwd(const dvt_attn_desc* d, dvt_stream_t stream) {
   } while (0)
   if (d->dtype == DVT_F32) DVT_ATTN_BWD_GENERIC(float);
   else if (d->dtype == DVT_BF16) DVT_ATTN_BWD_GENERIC(bf16);
-  else if (d->dtype == DVT_F16) DVT_ATTN_BWD_GENERIC(f16);
-  else DVT_UNSUPPORTED("dvt_attention_bwd: dtype %d not supported", d->dtype);
+  else DVT_ATTN_BWD_GENERIC(f16);
 #undef DVT_ATTN_BWD_GENERIC
   DVT_LAUNCH_CHECK("dvt_attention_bwd(generic)");
   return DVT_OK;

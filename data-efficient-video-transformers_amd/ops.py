@@ -714,11 +714,16 @@ def _attn_desc(q: Tensor, k: Tensor, v: Tensor, o: Tensor, lse: Tensor, scale: f
     return d
 
 
-def attention_fwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, scale: float, dropout=None) -> Tensor:
-    """Writes o (a [B,H,Lq,dh] view of caller-owned memory); returns lse [B,H,Lq] f32."""
+def attention_fwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, scale: float, dropout=None,
+                  lse: Optional[Tensor] = None) -> Tensor:
+    """Writes o (a [B,H,Lq,dh] view of caller-owned memory); returns lse [B,H,Lq] f32 (written into `lse` if given: a
+    contiguous f32 tensor of B*H*Lq elements)."""
     _need_cuda(q, k, v, o)
     B, H, Lq, _ = q.shape
-    lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+    if lse is None:
+        lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+    else:
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() == B * H * Lq and lse.device == q.device
     d = _attn_desc(q, k, v, o, lse, scale, dropout)
     nb = (2 * q.numel() + k.numel() + v.numel()) * q.element_size()          # read q, k, v; write o
     with _timed(("hbm", "attention_fwd", q.numel(), 4.0 * q.numel() * k.shape[2]), nb):   # key carries the MFMA flops
@@ -730,9 +735,11 @@ ATTN_BWD_TWO_PASS = False      # A/B switch (bench.py --attn-two-pass): the dq +
 
 
 def attention_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, lse: Tensor, do: Tensor, dq: Tensor,
-                  dk: Tensor, dv: Tensor, scale: float, dropout=None, two_pass: Optional[bool] = None) -> None:
+                  dk: Tensor, dv: Tensor, scale: float, dropout=None, two_pass: Optional[bool] = None,
+                  ws: Optional[Tensor] = None) -> None:
     """do must share o's strides; dq/dk/dv must share q/k/v's strides (views of
-    caller-owned memory, fully overwritten)."""
+    caller-owned memory, fully overwritten).  ws: caller-owned workspace of at least
+    dvt_attention_bwd_workspace_bytes (default: the shared scratch buffer)."""
     _need_cuda(q, k, v, o, do, dq, dk, dv)
     for a, b in ((do, o), (dq, q), (dk, k), (dv, v)):
         assert a.shape == b.shape and all(sa == sb for sa, sb, n in zip(a.stride(), b.stride(), a.shape) if n > 1), \
@@ -741,13 +748,58 @@ def attention_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, lse: Tensor, do: T
     d.d_o, d.dq, d.dk, d.dv = do.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
     d.bwd_two_pass = int(ATTN_BWD_TWO_PASS if two_pass is None else two_pass)
     lib = L.load()
-    ws = workspace(lib.dvt_attention_bwd_workspace_bytes(C.byref(d)), q.device)
+    need = lib.dvt_attention_bwd_workspace_bytes(C.byref(d))
+    if ws is None:
+        ws = workspace(need, q.device)
+    else:
+        assert ws.device == q.device and ws.numel() * ws.element_size() >= need
     d.workspace = _p(ws)
     # algorithmic bytes: q, k, v, o, dO read once, dq, dk, dv written once (the one-pass form moves exactly that; the
     # two-kernel form re-reads q, k, v, dO: 13 units through the memory pipeline for these 8)
     nb = (4 * q.numel() + 2 * k.numel() + 2 * v.numel()) * q.element_size()
     with _timed(("hbm", "attention_bwd", q.numel(), 10.0 * q.numel() * k.shape[2]), nb):  # 5 products of 2*L*L*dh
         L.check(lib.dvt_attention_bwd(C.byref(d), _stream()), "dvt_attention_bwd")
+
+
+class AttnPlan(NamedTuple):
+    """What one dvt_attention_fwd / _bwd call launches (dvt_attention_plan): the kernel family (ATTN_FAMILIES), the
+    template count of the (first) launch and of the dk/dv launch (0 = rolled loop / not templated), waves per block of
+    each, whether each stores output tiles as whole rows through LDS patches (True), per lane (False) or has no such
+    choice (None), whether the workspace is used, and the dynamic LDS bytes of each launch."""
+    family: str
+    count: int = 0
+    count2: int = 0
+    waves: int = 0
+    waves2: int = 0
+    patch: Optional[bool] = None
+    patch2: Optional[bool] = None
+    workspace: bool = False
+    lds: int = 0
+    lds2: int = 0
+
+
+ATTN_FAMILIES = ("none", "q1", "res", "online", "small", "generic", "q1", "fused", "pair", "small", "generic")
+
+
+def attention_plan(q: Tensor, k: Tensor, v: Tensor, o: Tensor, *, bwd: bool = False, do: Optional[Tensor] = None,
+                   dq: Optional[Tensor] = None, dk: Optional[Tensor] = None, dv: Optional[Tensor] = None,
+                   dropout_p: float = 0.0, two_pass: Optional[bool] = None, scale: Optional[float] = None) -> AttnPlan:
+    """What ``attention_fwd`` (or, bwd=True, ``attention_bwd``) launches for the same views (dvt_attention_plan: the
+    launchers' own decisions, no launch, no device needed -- only shapes, strides, addresses, types and the sign of
+    `scale` count; default dh^-1/2, the model's).  The gradient views default to their primals' (same strides and
+    alignment)."""
+    d = _attn_desc(q, k, v, o, o, q.shape[3] ** -0.5 if scale is None else float(scale))
+    if dropout_p:
+        d.dropout_p, d.rng_state = float(dropout_p), 256
+    if bwd:
+        do, dq, dk, dv = (o if do is None else do), (q if dq is None else dq), (k if dk is None else dk), (v if dv is None else dv)
+        d.d_o, d.dq, d.dk, d.dv = do.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+        d.bwd_two_pass = int(ATTN_BWD_TWO_PASS if two_pass is None else two_pass)
+    r = L.AttnPlanInfo()
+    L.check(L.load().dvt_attention_plan(C.byref(d), int(bwd), C.byref(r)), "dvt_attention_plan")
+    opt = lambda x: None if x < 0 else bool(x)
+    return AttnPlan(ATTN_FAMILIES[r.family], r.count, r.count2, r.waves, r.waves2, opt(r.patch), opt(r.patch2),
+                    bool(r.workspace), r.lds, r.lds2)
 
 
 # ------------------------------------------------------------------ single-query attention, K / V projections folded

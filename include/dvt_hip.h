@@ -433,6 +433,37 @@ typedef struct dvt_attn_desc {
 size_t dvt_attention_bwd_workspace_bytes(const dvt_attn_desc* desc);
 int dvt_attention_fwd(const dvt_attn_desc* desc, dvt_stream_t stream);
 int dvt_attention_bwd(const dvt_attn_desc* desc, dvt_stream_t stream);
+/* What dvt_attention_fwd (bwd == 0) or dvt_attention_bwd (bwd != 0) would launch for desc, taken from the same decisions
+ * the launchers make (ABI v5 addition; host only, runs without a device).  The workspace pointer is not required: the
+ * `workspace` field says whether the launch would use it.  Returns what the launcher returns for a descriptor it refuses,
+ * else DVT_OK (family NONE when B == 0). */
+enum dvt_attn_family {
+  DVT_ATTN_F_NONE = 0,
+  DVT_ATTN_F_Q1 = 1,        /* fwd: attn_fwd_q1_kernel (Lq == 1, dh == 64) */
+  DVT_ATTN_F_RES = 2,       /* fwd: attn_fwd_mfma_res_kernel<E, count> (whole score row in registers, <= 352 keys) */
+  DVT_ATTN_F_ONLINE = 3,    /* fwd: attn_fwd_mfma_kernel (online softmax over 32-key steps) */
+  DVT_ATTN_F_SMALL = 4,     /* fwd: attn_small_fwd_kernel (both lengths <= 32) */
+  DVT_ATTN_F_GENERIC = 5,   /* fwd: attn_fwd_generic_kernel (one wave per query row) */
+  DVT_ATTN_B_Q1 = 6,        /* bwd: attn_bwd_q1_kernel */
+  DVT_ATTN_B_FUSED = 7,     /* bwd: attn_bwd_fused_kernel<E, count> (one pass) */
+  DVT_ATTN_B_PAIR = 8,      /* bwd: attn_bwd_dq_mfma_kernel<E, count> then attn_bwd_dkv_mfma_kernel<E, count2> */
+  DVT_ATTN_B_SMALL = 9,     /* bwd: attn_small_bwd_kernel */
+  DVT_ATTN_B_GENERIC = 10   /* bwd: attn_delta_kernel, attn_bwd_dq_generic_kernel, attn_bwd_dkv_generic_kernel */
+};
+typedef struct dvt_attn_plan_info {
+  int32_t family;     /* enum dvt_attn_family */
+  int32_t count;      /* template count of the (first) launch: RES NKP, FUSED NP, PAIR the dq kernel's NKP (0 = rolled) */
+  int32_t count2;     /* PAIR: the dk/dv kernel's NQP (0 = rolled); else 0 */
+  int32_t waves;      /* waves per block of the (first) launch */
+  int32_t waves2;     /* PAIR / GENERIC bwd: of the dk/dv launch; else 0 */
+  int32_t patch;      /* RES / ONLINE / PAIR dq: 1 = output tiles stored as whole rows through LDS patches, 0 = per lane;
+                       * -1 for families without the choice */
+  int32_t patch2;     /* PAIR: the same for the dk/dv launch; else -1 */
+  int32_t workspace;  /* 1 if the launch reads and writes desc->workspace */
+  int64_t lds;        /* dynamic LDS bytes of the (first) launch */
+  int64_t lds2;       /* of the dk/dv launch (PAIR, GENERIC bwd); else 0 */
+} dvt_attn_plan_info;
+int dvt_attention_plan(const dvt_attn_desc* desc, int bwd, dvt_attn_plan_info* info);
 
 /* ---------------------------------------------------------------- single-query attention with folded K / V projections
  * The reference reads only row 0 of the space transformer's output (src/models/vit.py:119-120; :126 for the temporal

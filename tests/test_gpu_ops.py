@@ -548,8 +548,8 @@ ATTN_CASES = [
     (2, 8, 15, 15, 112), (1, 3, 9, 11, 100), (1, 2, 7, 5, 30), (1, 2, 32, 32, 128), (2, 1, 1, 7, 20), (1, 1, 32, 32, 512),
     (2, 2, 325, 325, 64),          # long-clip tokens per frame (288^2): > 80 KiB of LDS, one 11-wave workgroup per CU
     (1, 2, 40, 600, 64),
-    # every compile-time key / query count of the register-resident forward (<= 224 keys) and the unrolled backward
-    # (<= 256), incl. Lq != Lk and the 225..256 band (online-softmax forward, unrolled backward)
+    # compile-time key / query counts of the register-resident forward (<= 352 keys) and the unrolled backward
+    # (<= 352), incl. Lq != Lk (every instantiation: tests/test_gpu_attention_exact.py)
     (1, 2, 90, 90, 64), (1, 2, 100, 128, 64), (1, 1, 150, 150, 64), (1, 2, 180, 190, 64), (1, 1, 250, 250, 64),
     (1, 1, 224, 224, 64),
 ]
