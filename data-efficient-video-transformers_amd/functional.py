@@ -14,9 +14,8 @@ into ``x`` inside the LayerNorm backward kernel.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional
-
-import os
 
 import torch
 
@@ -1276,49 +1275,49 @@ def _kpad(K: int, dtype: torch.dtype) -> int:
     return K if dtype == torch.float32 else (K + 63) // 64 * 64
 
 
-# Keep the im2col column matrix of every convolution for its weight-gradient GEMM instead of re-gathering it in
-# backward: ~9x the activation bytes per 3x3 layer (8 GB for ResNet-18 on 256 frames of 224^2) -- affordable in
-# 288 GB of HBM and one gather pass per layer cheaper.  Set False to trade the memory back.
-SAVE_CONV_COLUMNS = True
-# Implicit-GEMM convolution (gather fused into the GEMM operand DMA) for the forward pass and, for stride-1
-# convolutions, the data gradient, wherever the geometry allows (16-bit dtype, Cin a multiple of 32/64).
+# Implicit-GEMM convolution (gather fused into the GEMM operand DMA) for the forward pass, the weight gradient and, for
+# stride-1 convolutions, the data gradient, wherever the geometry allows (16-bit dtype, C a multiple of 8).
 IMPLICIT_CONV = True
-# BatchNorm batch statistics from the implicit convolution's GEMM epilogue (fp32 accumulators) instead of a separate pass
-# over the stored output
-FUSE_BN_STATS = True
-GENERAL_TAPS = os.environ.get("DVT_GENERAL_TAPS", "1") != "0"   # implicit kernels for any C % 8 == 0 (per-lane taps), K not padded to 64
-HALO_CONV = True          # 64 -> 64 channel 3x3 / 1 / 1 convolutions from an LDS-resident halo patch (dvt_conv3x3_c64)
+# the LDS halo / window / streamed-weight kernels on top of it (csrc/conv3x3*.hip, conv3x1*.hip, conv_stem.hip)
+HALO_CONV = True
+# the backward of a virtual BatchNorm (see _ConvBnAct.forward's in_affine) inside the temporal half's data gradient
+# (ops.conv3x1_stream_bn_bwd: the 144-plane gradient is computed twice and never stored) instead of a stored gradient + two
+# BatchNorm passes over it
+FUSED_MID_BN_BWD = True
 # data gradient of STRIDED convolutions as one implicit launch per parity class of input pixels (1 / 2 / 2 / 4 taps of a
-# 3 x 3 / 2 filter) scattering into the full-size gradient, instead of a dcol GEMM + col2im pass
-STRIDED_IMPLICIT = os.environ.get("DVT_STRIDED_IMPLICIT", "1") != "0"
-# ... for maps of at least this many input pixels: below it the four class launches are latency-bound (17 - 21 us each at
-# 12 k rows per class, `gpurun_out/r5_pyr_strided_order.txt`) and the dcol GEMM + col2im pair is as fast
-STRIDED_IMPLICIT_MIN_PIXELS = int(os.environ.get("DVT_STRIDED_IMPLICIT_MIN_PIXELS", "150000"))
+# 3 x 3 / 2 filter) scattering into the full-size gradient, for maps of at least this many input pixels: below it the four
+# class launches are latency-bound (17 - 21 us each at 12 k rows per class) and the dcol GEMM + col2im pair is as fast
+STRIDED_IMPLICIT_MIN_PIXELS = 150000
+
+
+def _pack_cached(w: Tensor, key, make) -> Tensor:
+    """A packed form of the convolution weight ``w`` (make() -> (dst, dvt_pack_entry)).  A parameter that lives in a
+    ``dp.FlatParameters`` store keeps its packed forms there and ALL of them are refreshed by one launch per optimizer step
+    (the weights only change there); any other tensor is packed on the spot."""
+    sink = _sink(w)
+    if sink is None or w.dtype != torch.float32:
+        dst, entry = make()
+        ops.conv_weight_pack_group([entry])
+        return dst
+    return sink.owner.packed_weight((sink.index,) + key, make, w._version)
 
 
 def _packed_weight(w: Tensor, kind: int, cout_l: int, cin_l: int, kh: int, kw: int, cout_p: int, cin_p: int, ld: int,
                    dtype: torch.dtype) -> Tensor:
     """The GEMM operand form of a convolution weight f32 [cout_l, cin_l, (1,) kh, kw]: kind 0 = forward [cout_p, ld] (column
     (ki*kw + kj) * cin_p + ci), kind 1 = data gradient [cin_p, kh*kw*cout_p] (rotated taps, transposed channels); channels
-    beyond the parameter's own are zero (channel-padded layers).  A parameter that lives in a ``dp.FlatParameters`` store keeps
-    its packed forms there and ALL of them are refreshed by one launch per optimizer step (the weights only change there);
-    any other tensor is packed on the spot."""
+    beyond the parameter's own are zero (channel-padded layers); cached as ``_pack_cached``."""
     def make():
         src = w.detach().contiguous()
         shape = (cout_p, ld) if kind == 0 else (cin_p, kh * kw * cout_p)
         dst = torch.empty(shape, dtype=dtype, device=w.device)
         return dst, (src, dst, cout_l, cin_l, kh, kw, cout_p, cin_p, ld, kind)
-    sink = _sink(w)
-    if sink is None or w.dtype != torch.float32:
-        dst, entry = make()
-        ops.conv_weight_pack_group([entry])
-        return dst
-    return sink.owner.packed_weight((sink.index, kind, cout_p, cin_p, ld, dtype), make, w._version)
+    return _pack_cached(w, (kind, cout_p, cin_p, ld, dtype), make)
 
 
 def _packed_class_weight(w: Tensor, cout_l: int, cin_l: int, kh: int, kw: int, cout_p: int, cin_p: int, cls, dtype) -> Tensor:
     """The data-gradient operand of one parity class of a strided convolution (dvt_pack_entry kind 2): [cin_p, nth*ntw*cout_p]
-    with the class's taps only; cached and refreshed like the other packed forms (`_packed_weight`)."""
+    with the class's taps only; cached as ``_pack_cached``."""
     sh, sw, rh, rw = cls
     ntaps = ((kh - rh + sh - 1) // sh) * ((kw - rw + sw - 1) // sw)
 
@@ -1326,30 +1325,164 @@ def _packed_class_weight(w: Tensor, cout_l: int, cin_l: int, kh: int, kw: int, c
         src = w.detach().contiguous()
         dst = torch.empty((cin_p, ntaps * cout_p), dtype=dtype, device=w.device)
         return dst, (src, dst, cout_l, cin_l, kh, kw, cout_p, cin_p, 0, 2, (sh, sw, rh, rw))
-    sink = _sink(w)
-    if sink is None or w.dtype != torch.float32:
-        dst, entry = make()
-        ops.conv_weight_pack_group([entry])
-        return dst
-    return sink.owner.packed_weight((sink.index, 2, cout_p, cin_p, (sh, sw, rh, rw), dtype), make, w._version)
+    return _pack_cached(w, (2, cout_p, cin_p, (sh, sw, rh, rw), dtype), make)
+
+# the kernel family of each product of a _ConvBnAct layer, named by _fwd_route / _wgrad_route / _dgrad_route
+FWD_ROUTES = ("stem_halo", "window", "stream", "halo", "implicit", "gemm")
+WGRAD_ROUTES = ("halo", "window", "implicit_bn", "implicit", "implicit_packed", "gemm")
+DGRAD_ROUTES = ("none", "halo", "stream", "stream3x1", "stream3x1_bn", "window", "implicit", "strided", "frames", "gemm")
 
 
-# the 7x7 / 2 stem from an LDS halo patch with the weights in registers (csrc/conv_stem.hip) instead of the implicit gather
-STEM_HALO = os.environ.get("DVT_STEM_HALO", "1") != "0"
-# weight gradient of the 64 -> 64 3x3 layers from LDS halo patches (csrc/conv3x3_wgrad.hip) instead of the implicit gather
-HALO_WGRAD = os.environ.get("DVT_HALO_WGRAD", "1") != "0"
-HALO_WGRAD_COUT = (64, 144) if os.environ.get("DVT_HALO_WGRAD_WIDE", "1") != "0" else (64,)
-# weight gradient of the (3, 1) temporal convolutions 144 -> 64 from LDS sliding windows (csrc/conv3x1_wgrad.hip)
-WINDOW_WGRAD = os.environ.get("DVT_WINDOW_WGRAD", "1") != "0"
-# ... and their forward (csrc/conv3x1_fwd.hip)
-WINDOW_FWD = os.environ.get("DVT_WINDOW_FWD", "1") != "0"
-# "virtual" BatchNorm between the two halves of such a pair: the spatial half leaves its output z and hands (mean, invstd,
-# gamma, beta) on; the temporal half's window kernels form relu(z * s + t) in LDS -- the normalised 144-plane activation is
-# never written (models/video_resnet.py decides per pair; needs both window kernels)
-WINDOW_VIRTUAL_BN = os.environ.get("DVT_WINDOW_VIRTUAL_BN", "1") != "0"
-# the backward of that virtual BatchNorm inside the temporal half's data gradient (ops.conv3x1_stream_bn_bwd: the 144-plane
-# gradient is computed twice and never stored) instead of a stored gradient + two BatchNorm passes over it
-FUSED_MID_BN_BWD = os.environ.get("DVT_FUSED_MID_BN_BWD", "1") != "0"
+def is_3x3_same(k, stride, pad) -> bool:            # the halo and streamed-weight kernels (csrc/conv3x3*.hip)
+    return ops._pair(k) == (3, 3) and ops._pair(stride) == (1, 1) and ops._pair(pad) == (1, 1)
+
+
+def is_3x1_temporal(k, stride, pad) -> bool:        # R(2+1)D's temporal convolutions in the window kernels (csrc/conv3x1*)
+    return ops._pair(k) == (3, 1) and ops._pair(stride) == (1, 1) and ops._pair(pad) == (1, 0)
+
+
+def _is_c64_halo(Cin, Cout, k, stride, pad, couts=(64,)) -> bool:      # the LDS-resident 64-channel halo patch kernels
+    return Cin == 64 and Cout in couts and is_3x3_same(k, stride, pad)
+
+
+_Layout = namedtuple("_Layout", "stem8 pair trim geom direct gen ld K")
+
+
+def _fwd_layout(x, geom, Cin_l, Cout, dtype) -> _Layout:
+    """The operand geometry of a layer's forward from shapes and dtypes alone, ahead of the input rewrite and the weight pack
+    that _fwd_route decides on.  stem8: the NCHW stem as an NHWC convolution with Cin = 8 (pair = (kh, kw, pw, kwp): over pixel
+    pairs, with ``trim`` output columns too many on the right); geom: (N, Cin, H, W, k, stride, pad, nchw) as the kernels see
+    it; direct: a 1x1 / stride-1 GEMM on x itself; gen: implicit kernels with per-lane taps; ld: the packed weight's row length."""
+    N, Cin, H, W, k, stride, pad, nchw = geom
+    (kh, kw), (sh, sw) = ops._pair(k), ops._pair(stride)
+    Ho, Wo = ops.conv_out_hw(H, W, k, stride, pad)
+    half = dtype in (torch.bfloat16, torch.float16)
+    # (frames that need a gradient: theirs is an explicit dcol GEMM + NCHW col2im over the rows of the dx_frames hint -- all
+    # frames without one -- and everything else about the layer stays implicit)
+    stem8 = IMPLICIT_CONV and nchw and Cin <= 8 and half and Cout % 8 == 0 and (N * Ho * Wo) % 32 == 0
+    pair, trim = None, 0
+    if stem8:
+        # The stem (custom_resnet.py:100: 7x7 / 2 on the 3-channel frames) as an implicit GEMM: the frames become an NHWC map
+        # with the channels zero-extended to 8 (one 16-byte chunk per pixel and tap), the weights carry the matching zero
+        # planes, and from here on it is an ordinary NHWC convolution with Cin = 8 -- no column matrix (0.94 GB at 256 frames
+        # of 224^2) in forward or in the weight gradient.
+        (ph, pw) = ops._pair(pad)
+        off = pw & 1
+        kwp = (kw + off + 1) // 2                      # pairs that cover the taps: (-1,0) (1,2) (3,4) (5,6) for 7 / pad 3
+        t = (W // 2 + (pw + off) - kwp + 1) - Wo if (sw == 2 and W % 2 == 0) else -1
+        if Cin <= 4 and Cin == Cin_l and t >= 0:
+            # Stride 2 and <= 4 channels: two horizontally adjacent pixels share a 16-byte chunk (Cpad = 4), and in that
+            # [N, H, W/2, 8] view the stem is a (kh, kwp) convolution of stride (sh, 1) over pixel pairs whose weights are
+            # the stem's, re-laid by dvt_conv_weight_pairs (zero taps where a pair sticks out of the kernel): 28 gathered
+            # chunks per output pixel instead of 49, K = 224 instead of 392 (one tile column of the weight gradient instead
+            # of two).  Its symmetric padding of (pw + off) / 2 pair columns yields `trim` output columns too many on the
+            # right (dvt_conv_desc.trim_w).  From here on it IS that convolution.
+            pair, trim = (kh, kw, pw, kwp), t
+            W, k, stride, pad = W // 2, (kh, kwp), (sh, 1), (ph, (pw + off) // 2)
+            (kh, kw), (sh, sw) = k, stride
+        Cin, nchw = 8, False
+        geom = (N, Cin, H, W, k, stride, pad, nchw)
+    K = kh * kw * Cin
+    direct = kh == 1 and kw == 1 and sh == 1 and sw == 1 and not nchw and K % 8 == 0 and x.dtype == dtype
+    # (a 1x1 / stride-1 layer the implicit kernels accept goes through them as well: the BatchNorm statistics come out of
+    # their epilogue and the weight gradient's reduce rides in the data gradient, like every other layer)
+    if direct and IMPLICIT_CONV and half and Cout % 8 == 0 and Cin % (32 if Cout <= 128 else 64) == 0 and (N * H * W) % 64 == 0:
+        direct = False
+    # C % 8 == 0 but not a whole number of k-tiles per filter tap (144 mid planes of R(2+1)D-18): the implicit kernels derive
+    # every lane's tap themselves and take K rounded up to THEIR k-tile (zero weight columns behind kh*kw*C) (and K itself,
+    # not K rounded up to 64, where the taps are whole k-tiles: 288 mid planes x 3 temporal taps = 864)
+    gen = (IMPLICIT_CONV and not direct and not nchw and not stem8 and half and x.dtype == dtype and x.is_cuda
+           and Cin % 8 == 0 and Cout % 8 == 0)
+    ld = K if direct else (ops.conv2d_implicit_k(Cin, Cout, k) if (stem8 or gen) else _kpad(K, dtype))
+    return _Layout(stem8, pair, trim, geom, direct, gen, ld, K)
+
+
+def _fwd_route(xc, wp, lay: _Layout, Cout, Cout_l, Cin_l, dtype):
+    """-> (one of FWD_ROUTES, ld): the forward's kernel family for the rewritten input ``xc`` and the weight ``wp`` packed
+    with ``lay.ld`` columns; ld differs from lay.ld where the per-lane-tap kernels refuse the operands (misaligned) and the
+    explicit path takes its 64-padded columns instead."""
+    N, Cin, H, W, k, stride, pad, nchw = lay.geom
+    padded = Cout != Cout_l or Cin != Cin_l
+    implicit = (IMPLICIT_CONV and not lay.direct and not nchw and (lay.ld == lay.K or lay.stem8 or lay.gen)
+                and xc.dtype == dtype and ops.conv2d_implicit_supported(xc, wp, N, Cin, H, W, Cout, k, stride, pad, lay.trim))
+    if not implicit:
+        return "gemm", (_kpad(lay.K, dtype) if lay.gen else lay.ld)
+    if HALO_CONV:
+        # the pixel-pair stem (7x7 / 2 / 3 on 3-channel frames, 64 output channels incl. zero extension) from an LDS halo patch
+        if (lay.pair is not None and Cout == 64 and ops._pair(k) == (7, 4) and ops._pair(stride) == (2, 1)
+                and ops._pair(pad) == (3, 2) and lay.trim == 1 and ops.conv_stem7_supported(xc, wp, N, H, W)):
+            return "stem_halo", lay.ld
+        # temporal halves of R(2+1)D-18's layer-1 pairs: a pixel segment over all frames in LDS (the 64 -> 64 form also takes
+        # a zero-extended input: the stem's 45 mid planes stored as 64)
+        if ((not padded or (Cin == 64 and Cout == Cout_l == 64)) and is_3x1_temporal(k, stride, pad)
+                and ops.conv3x1_fwd_supported(xc, wp, N, H, W, Cin, Cout)):
+            return "window", lay.ld
+        # layer 1 of ResNet-18: LDS-resident halo patch instead of nine gathers
+        if _is_c64_halo(Cin, Cout, k, stride, pad) and ops.conv3x3_c64_supported(xc, wp, N, H, W):
+            return "halo", lay.ld
+        # layers 1-2 of R(2+1)D-18, 64 <-> 144 / 128 <-> 288: halo patch, weights streamed through LDS
+        if lay.ld == lay.K and is_3x3_same(k, stride, pad) and ops.conv3x3_stream_supported(xc, wp, N, H, W, Cin, Cout):
+            return "stream", lay.ld
+    return "implicit", lay.ld
+
+
+def _wgrad_route(ctx, xc, dz, geom, Cout) -> str:
+    """One of WGRAD_ROUTES.  ctx.wg_implicit: the forward found the implicit weight-gradient kernels able to take the layer."""
+    N, Cin, H, W, k, stride, pad, _ = geom
+    if not ctx.wg_implicit:
+        return "gemm"                             # column matrix (kept from forward or gathered again) x dz
+    if ctx.pair is not None:
+        return "implicit_packed"                  # the pixel-pair stem post-processes the packed form
+    if HALO_CONV and not ctx.logical[2]:
+        # layer 1 of ResNet-18 (and, in 64-channel groups of dz, of R(2+1)D-18: 64 -> 144): input patch and gradient tile
+        # staged once per R rows, the nine taps read from LDS
+        if _is_c64_halo(Cin, Cout, k, stride, pad, (64, 144)) and ops.conv3x3_c64_wgrad_supported(xc, dz, N, H, W, Cout):
+            return "halo"
+        # the temporal half of R(2+1)D-18's layer-1 pairs (144 mid planes -> 64): a segment of pixels over all frames staged
+        # once, the three taps read from LDS (the implicit form gathered x once per tap)
+        if is_3x1_temporal(k, stride, pad) and ops.conv3x1_wgrad_supported(xc, dz, N, H, W, Cin, Cout):
+            return "window"
+    # the forward kept the BatchNorm in front virtual, and the window kernel refuses what it is handed now (a switch flipped
+    # between forward and backward, a gradient the kernel cannot take): relu(bn(z)) is materialised for the implicit kernel
+    return "implicit_bn" if ctx.in_affine is not None else "implicit"
+
+
+def _dgrad_route(ctx, dz, wd, geom, Cout, pd, alias_pending: bool):
+    """-> (one of DGRAD_ROUTES, parity classes of the "strided" route or None).  wd: the data-gradient pack of a stride-1
+    implicit layer, whose data gradient is the stride-1 convolution of dz padded by ``pd`` (None otherwise); alias_pending:
+    the full-size gradient of a fork="alias" shortcut waits to be joined."""
+    N, Cin, H, W, k, stride, pad, nchw = geom
+    Ho, Wo = ops.conv_out_hw(H, W, k, stride, pad)
+    if not ctx.x_needs:
+        return "none", None
+    if wd is not None:
+        if HALO_CONV:
+            if _is_c64_halo(Cin, Cout, k, stride, pad) and ops.conv3x3_c64_supported(dz, wd, N, Ho, Wo):
+                return "halo", None
+            if is_3x3_same(k, stride, pad) and ops.conv3x3_stream_supported(dz, wd, N, Ho, Wo, Cout, Cin):
+                return "stream", None
+            if (is_3x1_temporal(k, stride, pad) and not alias_pending
+                    and ops.conv3x1_stream_supported(dz, wd, N, Ho, Wo, Cout, Cin)):
+                # the temporal half of layer 1's Conv2Plus1D (64 -> 144); with the spatial half's z under a virtual
+                # BatchNorm in front, that BatchNorm's backward runs inside this data gradient
+                lk = ctx.in_affine[6] if (ctx.in_affine is not None and len(ctx.in_affine) > 6) else None
+                fused = FUSED_MID_BN_BWD and lk is not None and lk.get("sinks") is not None and not ctx.in_affine[4]
+                return ("stream3x1_bn" if fused else "stream3x1"), None
+            # the stem's temporal half: the window kernel on the data-gradient pack
+            if (is_3x1_temporal(k, stride, pad) and Cin == 64 and Cout == 64 and not alias_pending
+                    and ops.conv3x1_fwd_supported(dz, wd, N, Ho, Wo, Cout, Cin)):
+                return "window", None
+        return ("implicit" if ops.conv2d_implicit_supported(dz, wd, N, Cout, Ho, Wo, Cin, k, 1, pd) else "gemm"), None
+    if (ctx.implicit and ctx.geom0 is None and not nchw and ops._pair(stride) != (1, 1) and ctx.w_ref is not None
+            and STRIDED_IMPLICIT_MIN_PIXELS <= N * H * W < (1 << 31)):
+        # strided layer (custom_resnet.py:19-22 with stride 2; R(2+1)D's strided halves): the input pixels fall into sh x sw
+        # parity classes, each the stride-1 convolution of dz with its own taps, scattered into dx by a row table
+        classes = ops.strided_dgrad_classes(k, stride, pad, H, W)
+        if classes is not None and all(ops.conv2d_implicit_k(Cout, Cin, nt) == nt[0] * nt[1] * Cout
+                                       for (_, _, nt, _, _, _) in classes):
+            return "strided", classes
+    return ("frames" if (nchw or ctx.geom0 is not None) and ctx.dx_frames else "gemm"), None
+
 
 class _ConvBnAct(torch.autograd.Function):
     """y = relu?( BN(conv(x)) (+ residual) ).  x: NHWC matrix [N*H*W, Cin], or the raw NCHW
@@ -1358,7 +1491,10 @@ class _ConvBnAct(torch.autograd.Function):
     Channel padding (``cpad`` > 0): Cout is rounded up to a multiple of ``cpad`` and x may carry more channels
     than ``w`` has input planes (a padded predecessor); weights / BatchNorm vectors are zero-extended on the fly, so
     the padded output channels are exactly zero and every kernel sees MFMA-friendly widths (R(2+1)D mid planes
-    45 / 230 / 460 / 921).  Parameters and their gradients keep the reference shapes."""
+    45 / 230 / 460 / 921).  Parameters and their gradients keep the reference shapes.
+
+    Routing: each product takes one kernel family, named by a resolver that launches nothing -- _fwd_route (on the geometry of
+    _fwd_layout), and in backward _wgrad_route and _dgrad_route -- and forward / backward dispatch on the name."""
 
     @staticmethod
     def forward(ctx, x, w, gamma, beta, residual, run_mean, run_var, geom, relu, training, momentum, eps, dtype,
@@ -1388,140 +1524,63 @@ class _ConvBnAct(torch.autograd.Function):
         N, Cin, H, W, k, stride, pad, nchw = geom
         Cout_l, Cin_l = w.shape[0], w.shape[1]
         Cout = (Cout_l + cpad - 1) // cpad * cpad if cpad else Cout_l
-        (kh, kw), (sh, sw) = ops._pair(k), ops._pair(stride)
         Ho, Wo = ops.conv_out_hw(H, W, k, stride, pad)
+        lay = _fwd_layout(x, geom, Cin_l, Cout, dtype)
+        pair = ctx.pair = lay.pair
+        ctx.trim = lay.trim
         xc = x.contiguous()
-        ctx.pair = pair = None
-        ctx.trim = 0
-        # (frames that need a gradient: theirs is an explicit dcol GEMM + NCHW col2im over the rows of the dx_frames hint --
-        # all frames without one -- and everything else about the layer stays implicit)
-        stem8 = (IMPLICIT_CONV and nchw and Cin <= 8 and dtype in (torch.bfloat16, torch.float16) and Cout % 8 == 0
-                 and (N * Ho * Wo) % 32 == 0)
-        ctx.geom0 = None
-        if stem8:
-            ctx.geom0 = (N, Cin, H, W, k, stride, pad)
+        ctx.geom0 = geom[:7] if lay.stem8 else None
+        if lay.stem8:
             ctx.w_stem = w if x.requires_grad else None
             if x.requires_grad and not dx_frames:
                 ctx.dx_frames = [(0, N)]
-            # The stem (custom_resnet.py:100: 7x7 / 2 on the 3-channel frames) as an implicit GEMM: the frames become an
-            # NHWC map with the channels zero-extended to 8 (one 16-byte chunk per pixel and tap), the weights carry the
-            # matching zero planes, and from here on it is an ordinary NHWC convolution with Cin = 8 -- no column matrix
-            # (0.94 GB at 256 frames of 224^2) in forward or in the weight gradient.
-            (ph, pw) = ops._pair(pad)
-            off = pw & 1
-            kwp = (kw + off + 1) // 2                      # pairs that cover the taps: (-1,0) (1,2) (3,4) (5,6) for 7 / pad 3
-            trim = (W // 2 + (pw + off) - kwp + 1) - Wo if (sw == 2 and W % 2 == 0) else -1
-            if Cin <= 4 and Cin == Cin_l and trim >= 0:
-                # Stride 2 and <= 4 channels: two horizontally adjacent pixels share a 16-byte chunk (Cpad = 4), and in that
-                # [N, H, W/2, 8] view the stem is a (kh, kwp) convolution of stride (sh, 1) over pixel pairs whose weights
-                # are the stem's, re-laid by dvt_conv_weight_pairs (zero taps where a pair sticks out of the kernel): 28
-                # gathered chunks per output pixel instead of 49, K = 224 instead of 392 (one tile column of the weight
-                # gradient instead of two).  Its symmetric padding of (pw + off) / 2 pair columns yields `trim` output
-                # columns too many on the right (dvt_conv_desc.trim_w).  From here on it IS that convolution.
-                ctx.pair = pair = (kh, kw, pw, kwp)
-                ctx.trim = trim
-                xc = ops.nchw_to_nhwc_pad(xc.view(N, Cin, H, W), dtype, 4)
-                W, k, stride, pad = W // 2, (kh, kwp), (sh, 1), (ph, (pw + off) // 2)
-                (kh, kw), (sh, sw) = k, stride
-            else:
-                xc = ops.nchw_to_nhwc_pad(xc.view(N, Cin, H, W), dtype, 8)
-            Cin, nchw = 8, False
-            geom = (N, Cin, H, W, k, stride, pad, nchw)
+            xc = ops.nchw_to_nhwc_pad(xc.view(N, Cin, H, W), dtype, 4 if pair is not None else 8)
+        N, Cin, H, W, k, stride, pad, nchw = geom = lay.geom
+        (kh, kw) = ops._pair(k)
         padded = Cout != Cout_l or Cin != Cin_l
         if Cin < Cin_l:
             raise ValueError("input has fewer channels than the convolution weight")
-        K = kh * kw * Cin
-        direct = (kh == 1 and kw == 1 and sh == 1 and sw == 1 and not nchw and K % 8 == 0 and x.dtype == dtype)
-        # (a 1x1 / stride-1 layer the implicit kernels accept goes through them as well: the BatchNorm statistics come out of
-        # their epilogue and the weight gradient's reduce rides in the data gradient, like every other layer)
-        if direct and IMPLICIT_CONV and dtype in (torch.bfloat16, torch.float16) and Cout % 8 == 0 and \
-                Cin % (32 if Cout <= 128 else 64) == 0 and (N * H * W) % 64 == 0:
-            direct = False
-        # C % 8 == 0 but not a whole number of k-tiles per filter tap (144 mid planes of R(2+1)D-18): the implicit kernels
-        # derive every lane's tap themselves and take K rounded up to THEIR k-tile (zero weight columns behind kh*kw*C)
-        # (and K itself, not K rounded up to 64, where the taps are whole k-tiles: 288 mid planes x 3 temporal taps = 864)
-        gen = (IMPLICIT_CONV and GENERAL_TAPS and not direct and not nchw and not stem8 and dtype in (torch.bfloat16, torch.float16)
-               and xc.dtype == dtype and xc.is_cuda and Cin % 8 == 0 and Cout % 8 == 0)
-        ld = K if direct else (ops.conv2d_implicit_k(Cin, Cout, k) if (stem8 or gen) else _kpad(K, dtype))
         if pair is not None:
-            kh_o, kw_o, pw_o, _ = pair
+            kh_o, kw_o, pw_o, kwp = pair
             w4 = w.reshape(Cout_l, Cin_l, kh_o * kw_o)
             if Cout != Cout_l:
                 w4 = ops.pad3_f32(w4, Cout_l, Cin_l, kh_o * kw_o, Cout, Cin_l)
             w4 = ops.conv_weight_pairs(w4, Cout, Cin_l, kh_o, kw_o, pw_o, kwp)          # [Cout, 8, kh, kwp]
-            wp = ops.conv_weight_pack(w4, ld, dtype)
+            wp = ops.conv_weight_pack(w4, lay.ld, dtype)
         else:                                      # packed once per optimizer step for all layers (zero extension included)
+            wp = _packed_weight(w, 0, Cout_l, Cin_l, kh, kw, Cout, Cin, lay.ld, dtype)
+        route, ld = _fwd_route(xc, wp, lay, Cout, Cout_l, Cin_l, dtype)
+        if route == "gemm" and lay.gen:
             wp = _packed_weight(w, 0, Cout_l, Cin_l, kh, kw, Cout, Cin, ld, dtype)
-        implicit = (IMPLICIT_CONV and not direct and not nchw and (ld == K or stem8 or gen) and xc.dtype == dtype and
-                    ops.conv2d_implicit_supported(xc, wp, N, Cin, H, W, Cout, k, stride, pad, ctx.trim))
-        if gen and not implicit:                   # (misaligned operands: the explicit path and its 64-padded columns)
-            ld = _kpad(K, dtype)
-            wp = _packed_weight(w, 0, Cout_l, Cin_l, kh, kw, Cout, Cin, ld, dtype)
-        if ctx.trim and not implicit:
+        if ctx.trim and route == "gemm":
             raise RuntimeError("the pixel-pair stem needs the implicit convolution kernels")
-        stats_partial = None
-        halo = (HALO_CONV and implicit and Cin == 64 and Cout == 64 and (kh, kw) == (3, 3) and (sh, sw) == (1, 1)
-                and ops._pair(pad) == (1, 1) and ops.conv3x3_c64_supported(xc, wp, N, H, W))
-        stream = (HALO_CONV and implicit and not halo and ld == K and (kh, kw) == (3, 3) and (sh, sw) == (1, 1)
-                  and ops._pair(pad) == (1, 1) and ops.conv3x3_stream_supported(xc, wp, N, H, W, Cin, Cout))
-        # (the 64 -> 64 form also takes a zero-extended input: the stem's 45 mid planes stored as 64)
-        window = (WINDOW_FWD and HALO_CONV and implicit and (not padded or (Cin == 64 and Cout == Cout_l == 64))
-                  and (kh, kw) == (3, 1) and (sh, sw) == (1, 1)
-                  and ops._pair(pad) == (1, 0) and ops.conv3x1_fwd_supported(xc, wp, N, H, W, Cin, Cout))
-        if in_affine is not None and not window:
+        if in_affine is not None and route != "window":
             raise RuntimeError("in_affine (virtual BatchNorm in front of the layer) needs the window kernels of the (3, 1) "
                                "temporal 144 -> 64 convolution")
-        # the pixel-pair stem (7x7 / 2 / 3 on 3-channel frames, 64 output channels incl. zero extension) from an LDS halo patch
-        stem_halo = (STEM_HALO and HALO_CONV and implicit and pair is not None and Cout == 64 and (kh, kw) == (7, 4)
-                     and (sh, sw) == (2, 1) and ops._pair(pad) == (3, 2) and ctx.trim == 1
-                     and ops.conv_stem7_supported(xc, wp, N, H, W))
-        if stem_halo:
-            col = None
-            halo = stream = window = False
-            if training and FUSE_BN_STATS:
-                z, stats_partial, stats_parts = ops.conv_stem7(xc, wp, N, H, W, want_stats=True)
-            else:
-                z = ops.conv_stem7(xc, wp, N, H, W)
-        elif window:                                # temporal half of R(2+1)D-18's layer-1 pairs: a pixel segment over all frames in LDS
-            col = None
-            halo = stream = False
-            if training and FUSE_BN_STATS:
-                z, stats_partial, stats_parts = ops.conv3x1_fwd(xc, wp, N, H, W, want_stats=True, affine=in_affine)
-            else:
-                z = ops.conv3x1_fwd(xc, wp, N, H, W, affine=in_affine)
-        elif stream:                              # layer 1 of R(2+1)D-18, 64 -> 144: halo patch, weights streamed through LDS
-            col = None
-            if training and FUSE_BN_STATS:
-                z, stats_partial, stats_parts = ops.conv3x3_stream(xc, wp, N, H, W, Cin, Cout, want_stats=True)
-            else:
-                z = ops.conv3x3_stream(xc, wp, N, H, W, Cin, Cout)
-        elif halo:                                # layer 1 of ResNet-18: LDS-resident halo patch instead of nine gathers
-            col = None
-            if training and FUSE_BN_STATS:
-                z, stats_partial, stats_parts = ops.conv3x3_c64(xc, wp, N, H, W, want_stats=True)
-            else:
-                z = ops.conv3x3_c64(xc, wp, N, H, W)
-        elif implicit:
-            col = None
-            if training and FUSE_BN_STATS:       # column sums for the BatchNorm come out of the GEMM epilogue
-                z, stats_partial, stats_parts = ops.conv2d_implicit(xc, wp, N, Cin, H, W, Cout, k, stride, pad, want_stats=True,
-                                                                    trim_w=ctx.trim)
-            else:
-                z = ops.conv2d_implicit(xc, wp, N, Cin, H, W, Cout, k, stride, pad, trim_w=ctx.trim)
-        else:
-            col = xc if direct else ops.im2col(xc, nchw, N, Cin, H, W, k, stride, pad, ld, dtype)
-            z = ops.linear_fwd(col, wp)                                 # [N*Ho*Wo, Cout]
+        col = None
+        if route == "gemm":
+            col = xc if lay.direct else ops.im2col(xc, nchw, N, Cin, H, W, k, stride, pad, ld, dtype)
+            out = ops.linear_fwd(col, wp)                                 # [N*Ho*Wo, Cout]
+        elif route == "stem_halo":
+            out = ops.conv_stem7(xc, wp, N, H, W, want_stats=training)
+        elif route == "window":
+            out = ops.conv3x1_fwd(xc, wp, N, H, W, want_stats=training, affine=in_affine)
+        elif route == "stream":
+            out = ops.conv3x3_stream(xc, wp, N, H, W, Cin, Cout, want_stats=training)
+        elif route == "halo":
+            out = ops.conv3x3_c64(xc, wp, N, H, W, want_stats=training)
+        else:                                     # column sums for the BatchNorm come out of the GEMM epilogue
+            out = ops.conv2d_implicit(xc, wp, N, Cin, H, W, Cout, k, stride, pad, want_stats=training, trim_w=ctx.trim)
+        z, stats = (out[0], out[1:]) if (training and route != "gemm") else (out, None)
         # BatchNorm vectors keep the parameter's own length; the kernels take it as c_valid and treat the padded channels as
         # gamma = beta = 0 (no padded copies, no slices of the statistics or of dgamma / dbeta)
         g32, b32 = _f32(gamma), _f32(beta)
         rm, rv = run_mean, run_var
         cval = Cout_l if Cout != Cout_l else 0
-        if training:
-            if stats_partial is not None:
-                mean, invstd = ops.bn_stats_from_partials(stats_partial, stats_parts, z.shape[0], Cout, rm, rv, eps, momentum,
-                                                          c_valid=cval)
-            else:
-                mean, invstd = ops.bn_stats(z, rm, rv, eps, momentum, c_valid=cval)
+        if training and stats is not None:
+            mean, invstd = ops.bn_stats_from_partials(*stats, z.shape[0], Cout, rm, rv, eps, momentum, c_valid=cval)
+        elif training:
+            mean, invstd = ops.bn_stats(z, rm, rv, eps, momentum, c_valid=cval)
         else:
             mean, invstd = rm.detach().float(), ops.bn_eval_invstd(rv.detach().float(), eps)
             if cval:                               # (mean / invstd are internal arrays of the padded width)
@@ -1550,24 +1609,26 @@ class _ConvBnAct(torch.autograd.Function):
         else:
             y = ops.bn_apply_fwd(z, mean, invstd, g32, b32, res, relu, c_valid=cval)
         # weight gradient straight from x (column matrix gathered inside the GEMM): nothing to keep but x
-        wg_implicit = (IMPLICIT_CONV and not direct and not nchw and xc.dtype == dtype and
+        wg_implicit = (IMPLICIT_CONV and not lay.direct and not nchw and xc.dtype == dtype and
                        ops.conv2d_implicit_wgrad_supported(xc, z, N, Cin, H, W, Cout, k, stride, pad, ctx.trim))
         if ctx.trim and not wg_implicit:
             raise RuntimeError("the pixel-pair stem needs the implicit weight-gradient kernel")
-        keep_col = SAVE_CONV_COLUMNS and not direct and col is not None and not wg_implicit
+        # otherwise the explicit forward's column matrix is kept for the weight-gradient GEMM instead of re-gathering it in
+        # backward: ~9x the activation bytes per 3x3 layer -- affordable in 288 GB of HBM and one gather pass per layer cheaper
+        keep_col = not lay.direct and col is not None and not wg_implicit
         # a ReLU layer without a residual branch recomputes its mask from z in backward (saves two passes over y)
         keep_y = relu and residual is not None
         ctx.save_for_backward(None if keep_col else xc, wp, z, y if (keep_y and rmask is None) else None, mean, invstd, g32,
                               col if keep_col else None, b32 if ((relu and not keep_y) or pooled) else None, pidx, rmask)
-        ctx.cfg = (geom, Cout, ld, direct, relu, training, residual is not None, tuple(w.shape), dtype)
+        ctx.cfg = (geom, Cout, ld, lay.direct, relu, training, residual is not None, tuple(w.shape), dtype)
         ctx.sinks = (_sink(w), _sink(gamma), _sink(beta))
         if link is not None:
             link["sinks"], link["training"], link["done"], link["grads"] = (ctx.sinks[1], ctx.sinks[2]), training, False, (None, None)
         ctx.x_needs = x.requires_grad
         ctx.x_shape, ctx.x_dtype = tuple(x.shape), x.dtype
-        ctx.implicit = implicit
+        ctx.implicit = route != "gemm"
         ctx.w_ref = w if pair is None else None           # the parameter itself: backward asks for its data-gradient form
-        ctx.w4 = w4.detach() if (implicit and pair is not None) else None
+        ctx.w4 = w4.detach() if (ctx.implicit and pair is not None) else None
         ctx.wg_implicit = wg_implicit
         ctx.logical = (Cout_l, Cin_l, padded)
         ctx.defer_apply = bool(defer_apply)
@@ -1579,7 +1640,7 @@ class _ConvBnAct(torch.autograd.Function):
             y, tail = y.view(y.shape), (mean, invstd)
         if fork is None:
             return (y,) + tail if tail else y
-        if nchw or stem8:
+        if nchw or lay.stem8:
             raise ValueError("fork is for NHWC feature maps (residual blocks), not the stem")
         if fork == "alias":
             return (y, x.view(x.shape)) + tail
@@ -1604,13 +1665,12 @@ class _ConvBnAct(torch.autograd.Function):
         sw, sg, sb = ctx.sinks
         dy = _as(dy.contiguous(), z.dtype)
         Ho, Wo = ops.conv_out_hw(H, W, k, stride, pad)
-        Wo -= ctx.trim
 
         cval = Cout_l if Cout != Cout_l else 0           # channel-padded layer: dgamma / dbeta have the parameter's own length
 
         def bn_backward(**kw):
             if pidx is not None:       # dy is the pooled gradient
-                dz_, dg_, db_ = ops.bn_bwd_pooled(dy, pidx, z, mean, invstd, g32, b32, N, Ho, Wo, relu, training, **kw)
+                dz_, dg_, db_ = ops.bn_bwd_pooled(dy, pidx, z, mean, invstd, g32, b32, N, Ho, Wo - ctx.trim, relu, training, **kw)
                 return dz_, None, dg_, db_
             return ops.bn_bwd(dy, z, y, mean, invstd, g32, relu, training, has_res, beta=b32, mask=rmask, c_valid=cval, **kw)
 
@@ -1631,36 +1691,26 @@ class _ConvBnAct(torch.autograd.Function):
             dz, dres, dgam, dbet = bn_backward()
         (kh, kw) = ops._pair(k)
         w4 = (Cout, Cin, kh, kw)
+        wg = _wgrad_route(ctx, xc, dz, geom, Cout)
         # the common case: the split-K reduce scatters straight into the parameter's own gradient layout (no packed dWt, no
         # scatter launch; channel-padded layers: only the entries the parameter has); the pixel-pair stem post-processes the
         # packed form instead
-        direct_dw = ctx.wg_implicit and ctx.pair is None
+        direct_dw = wg in ("halo", "window", "implicit_bn", "implicit")
         if direct_dw:
             dw_master = sw.buf.view(wshape) if sw is not None else torch.empty(wshape, dtype=torch.float32, device=dz.device)
             acc_w = (not sw.fresh) if sw is not None else False
-            if (HALO_WGRAD and HALO_CONV and Cin == 64 and Cout in HALO_WGRAD_COUT and not padded and (kh, kw) == (3, 3)
-                    and ops._pair(stride) == (1, 1) and ops._pair(pad) == (1, 1)
-                    and ops.conv3x3_c64_wgrad_supported(xc, dz, N, H, W, Cout)):
-                # layer 1 of ResNet-18 (and, in 64-channel groups of dz, of R(2+1)D-18: 64 -> 144): input patch and gradient
-                # tile staged once per R rows, the nine taps read from LDS
+            if wg == "halo":
                 pend = ops.conv3x3_c64_wgrad(xc, dz, N, H, W, dw_master, accumulate=acc_w, defer_reduce=True, Cout=Cout)
-            elif ((WINDOW_WGRAD or ctx.in_affine is not None) and HALO_CONV and (kh, kw) == (3, 1) and not padded and ops._pair(stride) == (1, 1)
-                    and ops._pair(pad) == (1, 0) and ops.conv3x1_wgrad_supported(xc, dz, N, H, W, Cin, Cout)):
-                # the temporal half of R(2+1)D-18's layer-1 pairs (144 mid planes -> 64): a segment of pixels over all frames
-                # staged once, the three taps read from LDS (the implicit form gathered x once per tap)
+            elif wg == "window":
                 pend = ops.conv3x1_wgrad(xc, dz, N, H, W, dw_master, accumulate=acc_w, defer_reduce=True, affine=ctx.in_affine)
             else:
                 xw = xc
-                if ctx.in_affine is not None:
-                    # the forward kept the BatchNorm in front virtual, and the window weight-gradient kernel refuses what it
-                    # is handed now (a switch flipped between forward and backward, a gradient the kernel cannot take):
-                    # materialise relu(bn(z)) once -- what the forward skipped -- and take the implicit kernel
+                if wg == "implicit_bn":           # relu(bn(z)) once -- what the forward skipped
                     am, ai, ag, ab, acv, arelu = ctx.in_affine[:6]
                     xw = ops.bn_apply_fwd(xc.contiguous(), am, ai, ag, ab, None, bool(arelu), c_valid=int(acv))
                 _, pend = ops.conv2d_implicit_wgrad(xw, dz, N, Cin, H, W, Cout, k, stride, pad, ctx.trim, defer_reduce=True,
                                                     master=dw_master, accumulate=acc_w, logical=(Cout_l, Cin_l))
-            unpack = dwp = None
-        elif ctx.wg_implicit:
+        elif wg == "implicit_packed":
             dwt, pend = ops.conv2d_implicit_wgrad(xc, dz, N, Cin, H, W, Cout, k, stride, pad, ctx.trim,
                                                   defer_reduce=True)                        # [kh*kw*Cin, Cout] fp32
             unpack, dwp = ops.conv_weight_unpack_grad_t, dwt
@@ -1669,49 +1719,8 @@ class _ConvBnAct(torch.autograd.Function):
                 col = xc if direct else ops.im2col(xc, nchw, N, Cin, H, W, k, stride, pad, ld, dtype)   # recomputed gather
             dwp, pend = ops.linear_wgrad(dz, col, defer_reduce=True)                         # [Cout, ld] fp32
             unpack = ops.conv_weight_unpack_grad
-        dw_box = [None]
-
-        def emit_dw():
-            """Unpack / scatter the reduced weight gradient into the parameter layout (and the sink).  Runs BEHIND the data
-            gradient: the implicit weight gradient leaves its split-K reduce to that launch's grid tail (``pend``)."""
-            if direct_dw:                                                    # the reduce wrote it in place
-                if sw is not None:
-                    sw.mark_written()
-                else:
-                    dw_box[0] = dw_master
-            elif ctx.pair is not None:                                         # pixel-pair stem: adjoint of dvt_conv_weight_pairs
-                kh_o, kw_o, pw_o, kwp = ctx.pair
-                dw_pairs = unpack(dwp, w4)                                   # [Cout, 8, kh, kwp]
-                if sw is not None and Cout == Cout_l:
-                    ops.conv_weight_pairs_bwd(dw_pairs, Cout, Cin_l, kh_o, kw_o, pw_o, kwp, out=sw.buf, accumulate=not sw.fresh)
-                    sw.mark_written()
-                    dw_box[0] = None
-                else:
-                    dwo = ops.conv_weight_pairs_bwd(dw_pairs, Cout, Cin_l, kh_o, kw_o, pw_o, kwp)
-                    if sw is not None:
-                        ops.unpad3_f32(dwo, Cout_l, Cin_l, kh_o * kw_o, Cin_l, out=sw.buf, accumulate=not sw.fresh)
-                        sw.mark_written()
-                        dw_box[0] = None
-                    else:
-                        dw_box[0] = ops.unpad3_f32(dwo, Cout_l, Cin_l, kh_o * kw_o, Cin_l).view(wshape)
-            elif padded:                                                     # full-width gradient, then the reference slice
-                dw_full = unpack(dwp, w4)
-                if sw is not None:
-                    ops.unpad3_f32(dw_full, Cout_l, Cin_l, kh * kw, Cin, out=sw.buf, accumulate=not sw.fresh)
-                    sw.mark_written()
-                    dw_box[0] = None
-                else:
-                    dw_box[0] = ops.unpad3_f32(dw_full, Cout_l, Cin_l, kh * kw, Cin).view(wshape)
-            elif sw is not None:
-                unpack(dwp, w4, out=sw.buf, accumulate=not sw.fresh)
-                sw.mark_written()
-                dw_box[0] = None
-            else:
-                dw_box[0] = unpack(dwp, w4).view(wshape)
-
         dx = None
         (sh_, sw_), (ph_, pw_) = ops._pair(stride), ops._pair(pad)
-        Ho, Wo = ops.conv_out_hw(H, W, k, stride, pad)
         # the shortcut's gradient (ctx.fork): joins the data gradient inside the kernel that writes it, where that kernel can
         joined = [dshort is None or not ctx.x_needs]
         if dshort is not None:
@@ -1723,71 +1732,59 @@ class _ConvBnAct(torch.autograd.Function):
                 return None
             joined[0] = True
             return dshort.view(N * H * W, Cin)
-        if (ctx.x_needs and ctx.implicit and ctx.geom0 is None and sh_ == 1 and sw_ == 1 and kh - 1 - ph_ >= 0
-                and kw - 1 - pw_ >= 0
-                and (Ho, Wo) == (H + 2 * ph_ - kh + 1, W + 2 * pw_ - kw + 1)):
+        wd = None
+        pd = (kh - 1 - ph_, kw - 1 - pw_)
+        if ctx.x_needs and ctx.implicit and ctx.geom0 is None and sh_ == 1 and sw_ == 1 and min(pd) >= 0:
             if ctx.w_ref is not None:                                    # [Cin, kh*kw*Cout], refreshed once per optimizer step
                 wd = _packed_weight(ctx.w_ref, 1, Cout_l, Cin_l, kh, kw, Cout, Cin, 0, dtype)
             else:
                 wd = ops.conv_weight_pack_dgrad(ctx.w4, dtype)
-            pd = (kh - 1 - ph_, kw - 1 - pw_)
-            if (HALO_CONV and Cin == 64 and Cout == 64 and (kh, kw) == (3, 3) and pd == (1, 1)
-                    and ops.conv3x3_c64_supported(dz, wd, N, Ho, Wo)):
-                dx = ops.conv3x3_c64(dz, wd, N, Ho, Wo, residual=join_alias())
-            elif (HALO_CONV and (kh, kw) == (3, 3) and pd == (1, 1)
-                    and ops.conv3x3_stream_supported(dz, wd, N, Ho, Wo, Cout, Cin)):
-                dx = ops.conv3x3_stream(dz, wd, N, Ho, Wo, Cout, Cin, residual=join_alias())
-            elif (HALO_CONV and (kh, kw) == (3, 1) and pd == (1, 0) and (joined[0] or ctx.fork != "alias")
-                    and ops.conv3x1_stream_supported(dz, wd, N, Ho, Wo, Cout, Cin)):
-                lk = ctx.in_affine[6] if (ctx.in_affine is not None and len(ctx.in_affine) > 6) else None
-                if FUSED_MID_BN_BWD and lk is not None and lk.get("sinks") is not None and not ctx.in_affine[4]:
-                    # the input is the spatial half's z under a virtual BatchNorm: its backward runs inside this data gradient
-                    sgm, sbm = lk["sinks"]
-                    if sgm is not None and sbm is not None and sgm.fresh == sbm.fresh:
-                        dx, _, _ = ops.conv3x1_stream_bn_bwd(dz, wd, xc, ctx.in_affine[:6], N, Ho, Wo, lk["training"],
-                                                             dgamma=sgm.buf.view(-1), dbeta=sbm.buf.view(-1),
-                                                             accumulate=not sgm.fresh)
-                        sgm.mark_written(); sbm.mark_written()
-                        lk["grads"] = (None, None)
-                    else:
-                        dx, dgm, dbm = ops.conv3x1_stream_bn_bwd(dz, wd, xc, ctx.in_affine[:6], N, Ho, Wo, lk["training"])
-                        if sgm is not None and sbm is not None:
-                            _emit_into(sgm, dgm); _emit_into(sbm, dbm)
-                            dgm = dbm = None
-                        lk["grads"] = (dgm, dbm)
-                    lk["done"] = True
-                else:
-                    dx = ops.conv3x1_stream(dz, wd, N, Ho, Wo, Cout, Cin)  # temporal half of layer 1's Conv2Plus1D: 64 -> 144
-            elif (WINDOW_FWD and HALO_CONV and (kh, kw) == (3, 1) and pd == (1, 0) and Cin == 64 and Cout == 64
-                    and (joined[0] or ctx.fork != "alias") and ops.conv3x1_fwd_supported(dz, wd, N, Ho, Wo, Cout, Cin)):
-                dx = ops.conv3x1_fwd(dz, wd, N, Ho, Wo)           # the stem's temporal half: the window kernel on the data-gradient pack
-            elif ops.conv2d_implicit_supported(dz, wd, N, Cout, Ho, Wo, Cin, k, 1, pd):
-                dx = ops.conv2d_implicit(dz, wd, N, Cout, Ho, Wo, Cin, k, 1, pd, carry=pend,
-                                         residual=join_alias())   # [N*H*W, Cin], no dcol / col2im
-        if (ctx.x_needs and dx is None and STRIDED_IMPLICIT and ctx.implicit and ctx.geom0 is None and not nchw
-                and (sh_, sw_) != (1, 1) and ctx.w_ref is not None and STRIDED_IMPLICIT_MIN_PIXELS <= N * H * W < (1 << 31)):
-            # strided layer (custom_resnet.py:19-22 with stride 2; R(2+1)D's strided halves): the input pixels fall into
-            # sh x sw parity classes, each the stride-1 convolution of dz with its own taps, scattered into dx by a row table
-            classes = ops.strided_dgrad_classes(k, stride, pad, H, W)
-            if classes is not None and all(ops.conv2d_implicit_k(Cout, Cin, nt) == nt[0] * nt[1] * Cout
-                                           for (_, _, nt, _, _, _) in classes):
-                full = compact = None
-                if not joined[0]:                # the shortcut's gradient joins in the residual epilogue of the class launches
-                    if ctx.fork == "alias":
-                        full = dshort.view(N * H * W, Cin)
-                    elif (int(ctx.fork), int(ctx.fork)) == (sh_, sw_):
-                        compact = dshort.view(-1, Cin)      # a strided 1 x 1 shortcut touches class (0, 0) only
-                    joined[0] = full is not None or compact is not None
-                dx = torch.empty((N * H * W, Cin), dtype=dz.dtype, device=dz.device)
-                order = sorted(classes, key=lambda c: c[2][0] * c[2][1])       # the class with the most taps carries the reduce
-                for i, (a, b, nt, pq, (rh, rw), hq) in enumerate(order):
-                    wc = _packed_class_weight(ctx.w_ref, Cout_l, Cin_l, kh, kw, Cout, Cin, (sh_, sw_, rh, rw), dtype)
-                    res, rc = (full, False) if full is not None else ((compact, True) if (compact is not None and a == 0 and b == 0)
-                                                                      else (None, False))
-                    ops.conv2d_implicit(dz, wc, N, Cout, Ho, Wo, Cin, nt, 1, pq, out=dx, out_hw=hq,
-                                        out_rows=ops.strided_class_rows(N, H, W, sh_, sw_, a, b, dz.device), residual=res,
-                                        residual_compact=rc, carry=pend if i == len(order) - 1 else None)
-        if ctx.x_needs and dx is None and (nchw or ctx.geom0 is not None) and ctx.dx_frames:
+        dg, classes = _dgrad_route(ctx, dz, wd, geom, Cout, pd, not joined[0] and ctx.fork == "alias")
+        if dg == "halo":
+            dx = ops.conv3x3_c64(dz, wd, N, Ho, Wo, residual=join_alias())
+        elif dg == "stream":
+            dx = ops.conv3x3_stream(dz, wd, N, Ho, Wo, Cout, Cin, residual=join_alias())
+        elif dg == "stream3x1_bn":
+            # the input is the spatial half's z under a virtual BatchNorm: its backward runs inside this data gradient
+            lk = ctx.in_affine[6]
+            sgm, sbm = lk["sinks"]
+            if sgm is not None and sbm is not None and sgm.fresh == sbm.fresh:
+                dx, _, _ = ops.conv3x1_stream_bn_bwd(dz, wd, xc, ctx.in_affine[:6], N, Ho, Wo, lk["training"],
+                                                     dgamma=sgm.buf.view(-1), dbeta=sbm.buf.view(-1), accumulate=not sgm.fresh)
+                sgm.mark_written(); sbm.mark_written()
+                lk["grads"] = (None, None)
+            else:
+                dx, dgm, dbm = ops.conv3x1_stream_bn_bwd(dz, wd, xc, ctx.in_affine[:6], N, Ho, Wo, lk["training"])
+                if sgm is not None and sbm is not None:
+                    _emit_into(sgm, dgm); _emit_into(sbm, dbm)
+                    dgm = dbm = None
+                lk["grads"] = (dgm, dbm)
+            lk["done"] = True
+        elif dg == "stream3x1":
+            dx = ops.conv3x1_stream(dz, wd, N, Ho, Wo, Cout, Cin)
+        elif dg == "window":
+            dx = ops.conv3x1_fwd(dz, wd, N, Ho, Wo)
+        elif dg == "implicit":
+            dx = ops.conv2d_implicit(dz, wd, N, Cout, Ho, Wo, Cin, k, 1, pd, carry=pend,
+                                     residual=join_alias())   # [N*H*W, Cin], no dcol / col2im
+        elif dg == "strided":
+            full = compact = None
+            if not joined[0]:                # the shortcut's gradient joins in the residual epilogue of the class launches
+                if ctx.fork == "alias":
+                    full = dshort.view(N * H * W, Cin)
+                elif (int(ctx.fork), int(ctx.fork)) == (sh_, sw_):
+                    compact = dshort.view(-1, Cin)      # a strided 1 x 1 shortcut touches class (0, 0) only
+                joined[0] = full is not None or compact is not None
+            dx = torch.empty((N * H * W, Cin), dtype=dz.dtype, device=dz.device)
+            order = sorted(classes, key=lambda c: c[2][0] * c[2][1])       # the class with the most taps carries the reduce
+            for i, (a, b, nt, pq, (rh, rw), hq) in enumerate(order):
+                wc = _packed_class_weight(ctx.w_ref, Cout_l, Cin_l, kh, kw, Cout, Cin, (sh_, sw_, rh, rw), dtype)
+                res, rc = (full, False) if full is not None else ((compact, True) if (compact is not None and a == 0 and b == 0)
+                                                                  else (None, False))
+                ops.conv2d_implicit(dz, wc, N, Cout, Ho, Wo, Cin, nt, 1, pq, out=dx, out_hw=hq,
+                                    out_rows=ops.strided_class_rows(N, H, W, sh_, sw_, a, b, dz.device), residual=res,
+                                    residual_compact=rc, carry=pend if i == len(order) - 1 else None)
+        elif dg == "frames":
             if ctx.geom0 is not None:            # implicit stem: the frames' own geometry and the plain [Cout, taps * Cin] pack
                 N0, C0, H0, W0, k0, s0, p0 = ctx.geom0
                 (kh0, kw0) = ops._pair(k0)
@@ -1801,7 +1798,7 @@ class _ConvBnAct(torch.autograd.Function):
                 dcol = ops.linear_dgrad(dz[f0 * hw:(f0 + cnt) * hw], wq)
                 ops.copy_(dx[f0:f0 + cnt], ops.col2im_nchw(dcol, cnt, C0, H0, W0, k0, s0, p0, ctx.x_dtype))
             dx = dx.view(ctx.x_shape)
-        if ctx.x_needs and dx is None:
+        elif dg == "gemm":
             dcol = ops.linear_dgrad(dz, wp, carry=pend)                  # [rows, ld]
             if direct:
                 dx = dcol
@@ -1819,8 +1816,26 @@ class _ConvBnAct(torch.autograd.Function):
             dfull = dshort.view(dx.shape) if ctx.fork == "alias" else ops.col2im(dshort, N, Cin, H, W, 1, int(ctx.fork), 0)
             dx = ops.add(dx.contiguous(), dfull.view(dx.shape))
         ops.splitk_reduce_pending(pend)          # nobody carried it (no data gradient wanted, or the halo kernel computed it)
-        emit_dw()
-        dw = dw_box[0]
+        # the reduced weight gradient into the parameter layout (into the sink when there is one): BEHIND the data gradient,
+        # whose launch carries the implicit weight gradient's split-K reduce in its grid tail (``pend``)
+        into = dict(out=sw.buf, accumulate=not sw.fresh) if sw is not None else {}
+        if direct_dw:                                                      # the reduce wrote it in place
+            dw = dw_master
+        elif ctx.pair is not None:                                         # pixel-pair stem: adjoint of dvt_conv_weight_pairs
+            kh_o, kw_o, pw_o, kwp = ctx.pair
+            dw_pairs = unpack(dwp, w4)                                     # [Cout, 8, kh, kwp]
+            if sw is not None and Cout == Cout_l:
+                dw = ops.conv_weight_pairs_bwd(dw_pairs, Cout, Cin_l, kh_o, kw_o, pw_o, kwp, **into)
+            else:
+                dwo = ops.conv_weight_pairs_bwd(dw_pairs, Cout, Cin_l, kh_o, kw_o, pw_o, kwp)
+                dw = ops.unpad3_f32(dwo, Cout_l, Cin_l, kh_o * kw_o, Cin_l, **into)
+        elif padded:                                                       # full-width gradient, then the reference slice
+            dw = ops.unpad3_f32(unpack(dwp, w4), Cout_l, Cin_l, kh * kw, Cin, **into)
+        else:
+            dw = unpack(dwp, w4, **into)
+        if sw is not None:
+            sw.mark_written()
+        dw = None if sw is not None else dw.view(wshape)
         return dx, dw, dgam, dbet, dres, None, None, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -1844,28 +1859,18 @@ def conv_bn_act_raw(x, weight, bn, geom, k, stride, pad, *, relu: bool, residual
     N, Cin, H, W, nchw = geom
     training = bn.training or bn.running_mean is None
     momentum = 0.1 if bn.momentum is None else bn.momentum
-    if defer_apply:
-        joins = fork is not None and torch.is_grad_enabled() and x.requires_grad
-        link = {}
-        outs = _ConvBnAct.apply(x, weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
-                                (N, Cin, H, W, k, stride, pad, nchw), relu, training, momentum, bn.eps, dtype, cpad,
-                                dx_frames, pool, fork if joins else None, in_affine, True, link)
-        z, (mean, invstd) = outs[0], outs[-2:]
-        cout_l = weight.shape[0]
-        affine = (mean, invstd, _f32(bn.weight), _f32(bn.bias), cout_l if z.shape[1] != cout_l else 0, relu, link)
-        if fork is None:
-            return z, affine
-        second = outs[1] if joins else (x if fork == "alias" else subsample_nhwc(x, N, Cin, H, W, int(fork)))
-        return (z, second), affine
-    if fork is not None and not (torch.is_grad_enabled() and x.requires_grad):       # nothing to join: hand the shortcut its input
-        y = _ConvBnAct.apply(x, weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
-                             (N, Cin, H, W, k, stride, pad, nchw), relu, training, momentum, bn.eps, dtype, cpad, dx_frames, pool,
-                             None, in_affine)
-        return y, (x if fork == "alias" else subsample_nhwc(x, N, Cin, H, W, int(fork)))
-    return _ConvBnAct.apply(x, weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
+    joins = fork is not None and torch.is_grad_enabled() and x.requires_grad      # else: hand the shortcut its input
+    link = {} if defer_apply else None
+    outs = _ConvBnAct.apply(x, weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
                             (N, Cin, H, W, k, stride, pad, nchw), relu, training, momentum, bn.eps, dtype, cpad, dx_frames, pool,
-                            fork, in_affine)
-
+                            fork if joins else None, in_affine, bool(defer_apply), link)
+    if defer_apply:
+        (mean, invstd), cout_l = outs[-2:], weight.shape[0]
+        affine = (mean, invstd, _f32(bn.weight), _f32(bn.bias), cout_l if outs[0].shape[1] != cout_l else 0, relu, link)
+    y = outs[0] if (joins or defer_apply) else outs
+    if fork is not None:
+        y = (y, outs[1] if joins else (x if fork == "alias" else subsample_nhwc(x, N, Cin, H, W, int(fork))))
+    return (y, affine) if defer_apply else y
 
 class _Subsample(torch.autograd.Function):
     """Strided spatial subsampling of an NHWC matrix (the gather of a strided 1x1 convolution)."""

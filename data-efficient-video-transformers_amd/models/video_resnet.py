@@ -50,9 +50,8 @@ def _mid_cpad(conv, frames, H, W, dtype):
         return CPAD
     if c % 32 == 0:
         return 32
-    if (c == 144 and conv.in_channels == 64 and tuple(conv.kernel_size[1:]) == (3, 3) and tuple(conv.stride[1:]) == (1, 1)
-            and tuple(conv.padding[1:]) == (1, 1) and ops.conv3x3_stream_geometry(frames, H, W, 144, 64, dtype)
-            and ops.conv3x3_stream_geometry(frames, H, W, 64, 144, dtype)):
+    if (c == 144 and conv.in_channels == 64 and F.is_3x3_same(conv.kernel_size[1:], conv.stride[1:], conv.padding[1:])
+            and ops.conv3x3_stream_geometry(frames, H, W, 144, 64, dtype) and ops.conv3x3_stream_geometry(frames, H, W, 64, 144, dtype)):
         return 16
     return CPAD
 
@@ -62,7 +61,7 @@ def _spatial(fm, conv, bn, relu, dtype, fork=None, defer=False):
     (the block's shortcut); the layer hands it out as a second result so that the shortcut's gradient joins this layer's
     data gradient inside the kernel that writes it (F._ConvBnAct) -> (fm, alias).  defer: the BatchNorm (+ ReLU) is NOT
     applied here -- the map returned is the convolution's output z and the third result the affine the temporal half behind
-    applies inside its window kernels (F.WINDOW_VIRTUAL_BN) -> (fm, alias or None, affine)."""
+    applies inside its window kernels (see _virtual_bn_pair) -> (fm, alias or None, affine)."""
     y, N, T, H, W = fm
     k, s, p = conv.kernel_size[1:], conv.stride[1:], conv.padding[1:]
     Ho, Wo = (H + 2 * p[0] - k[0]) // s[0] + 1, (W + 2 * p[1] - k[1]) // s[1] + 1
@@ -95,14 +94,10 @@ def _virtual_bn_pair(pair, N, T, H, W, dtype) -> bool:
     """Can the BatchNorm + ReLU between the two halves of this Conv2Plus1D stay virtual?  Needs the window kernels of the
     temporal half (144 mid planes -> 64, (3, 1, 1) / 1 / pad 1, a segment length that fits) and un-padded mid planes."""
     sp, tm = pair[0], pair[3]
-    if not (F.WINDOW_VIRTUAL_BN and F.WINDOW_FWD and F.HALO_CONV and dtype in (torch.bfloat16, torch.float16)):
-        return False
-    if not (sp.out_channels == 144 and tm.in_channels == 144 and tm.out_channels == 64 and tuple(tm.kernel_size) == (3, 1, 1)
-            and tuple(tm.stride) == (1, 1, 1) and tuple(tm.padding) == (1, 0, 0) and tuple(sp.stride) == (1, 1, 1)):
-        return False
-    if _mid_cpad(sp, N * T, H, W, dtype) != 16:           # (144 stays 144 only on the streamed-weight path)
-        return False
-    return ops.conv3x1_window_geometry(N, T, H * W, 144, 64, dtype)
+    return bool(F.HALO_CONV and sp.out_channels == 144 and tm.in_channels == 144 and tm.out_channels == 64
+                and tuple(sp.stride) == (1, 1, 1) and F.is_3x1_temporal((tm.kernel_size[0], 1), (tm.stride[0], 1), (tm.padding[0], 0))
+                and _mid_cpad(sp, N * T, H, W, dtype) == 16            # (144 stays 144 only on the streamed-weight path)
+                and ops.conv3x1_window_geometry(N, T, H * W, 144, 64, dtype))
 
 
 class Conv3DSimple(nn.Conv3d):

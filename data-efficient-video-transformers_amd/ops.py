@@ -7,7 +7,6 @@ falls back to torch arithmetic.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import NamedTuple, Optional, Tuple
 
 import torch
@@ -1470,8 +1469,7 @@ def conv3x3_c64(x: Tensor, wp: Tensor, N: int, H: int, W: int, want_stats: bool 
     return (y, partial, parts) if want_stats else y
 
 
-# (DVT_STREAM_LAYER2=0: layer 2's 128 <-> 288 pairs stay on the implicit GEMM -- the same-box A/B switch of round 6)
-_STREAM_PAIRS = ((64, 144), (144, 64)) + (((128, 288), (288, 128)) if os.environ.get("DVT_STREAM_LAYER2", "1") != "0" else ())
+_STREAM_PAIRS = ((64, 144), (144, 64), (128, 288), (288, 128))
 
 
 def conv3x3_stream_supported(x: Tensor, wp: Tensor, N: int, H: int, W: int, Cin: int, Cout: int) -> bool:

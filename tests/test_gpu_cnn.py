@@ -6,7 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-from tests.util import assert_within_reference_lowprec, golden, rel_l2, fill_resnet_from_numpy
+from tests.util import assert_within_reference_lowprec, golden, rel_l2, fill_resnet_from_numpy, record_conv_routes
 
 pytestmark = pytest.mark.gpu
 T = lambda a: torch.from_numpy(np.asarray(a))
@@ -70,7 +70,7 @@ def test_conv_bn_relu_block(dvt, device, dtype, tol, k, stride, pad, Cin, Cout, 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("Cout,H,W", [(64, 32, 32), (16, 64, 48)])
-def test_stem_as_implicit_gemm_matches_conv2d(dvt, device, dtype, Cout, H, W):
+def test_stem_as_implicit_gemm_matches_conv2d(dvt, device, monkeypatch, dtype, Cout, H, W):
     """The 7x7 / 2 stem on raw NCHW frames (custom_resnet.py:100) through the implicit-GEMM form -- frames zero-extended to
     8 channels (dvt_nchw_to_nhwc_pad), K rounded up to the k-tile, no column matrix -- against torch's conv2d + batch_norm
     on the same rounded operands: output, running statistics, weight / BatchNorm gradients; and against the explicit
@@ -92,8 +92,10 @@ def test_stem_as_implicit_gemm_matches_conv2d(dvt, device, dtype, Cout, H, W):
     gy = torch.randn(ref.shape, generator=g).to(dtype)
     ref.backward(gy.float())
     outs = {}
+    calls = record_conv_routes(monkeypatch, F)
     for implicit in (True, False):
         F.IMPLICIT_CONV = implicit
+        calls.clear()
         try:
             c2, b2 = torch.nn.Conv2d(3, Cout, 7, 2, 3, bias=False), torch.nn.BatchNorm2d(Cout)
             c2.load_state_dict(conv.state_dict()); b2.load_state_dict(bn.state_dict())
@@ -103,6 +105,11 @@ def test_stem_as_implicit_gemm_matches_conv2d(dvt, device, dtype, Cout, H, W):
             outs[implicit] = (y.detach(), c2.weight.grad.clone(), b2.weight.grad.clone(), b2.bias.grad.clone(), b2.running_var.clone())
         finally:
             F.IMPLICIT_CONV = True
+        (r,) = calls                                   # the form each pass meant to take
+        if implicit:
+            assert r["fwd"] in ("stem_halo", "implicit") and r["wgrad"] in ("implicit", "implicit_packed"), r
+        else:
+            assert r["fwd"] == "gemm" and r["wgrad"] == "gemm", r
     tol = 1.5e-2 if dtype == torch.bfloat16 else 3e-3
     y, dw, dg, db, rvar = outs[True]
     assert rel_l2(y, ref.permute(0, 2, 3, 1).reshape(-1, Cout)) < tol
@@ -1112,15 +1119,19 @@ def test_r2plus1d_block_backward_with_and_without_the_fused_mid_batchnorm(dvt, d
     x0 = torch.randn(N * T * H * W, 64).to(torch.bfloat16).cuda()
     gy = (torch.randn(N * T * H * W, 64) / 50).to(torch.bfloat16).cuda()
     assert vr._virtual_bn_pair(blk.conv1[0], N, T, H, W, torch.bfloat16)
+    calls = record_conv_routes(monkeypatch, F)
     res = []
     for fused in (False, True):
         monkeypatch.setattr(F, "FUSED_MID_BN_BWD", fused)
+        calls.clear()
         for p_ in blk.parameters():
             p_.grad = None
         x = x0.clone().requires_grad_(True)
         out = blk.forward_ndhwc((x, N, T, H, W), torch.bfloat16)[0]
         out.backward(gy)
         res.append((x.grad.float().clone(), {n: p_.grad.clone() for n, p_ in blk.named_parameters()}))
+        dgrads = [c["dgrad"] for c in calls]
+        assert dgrads.count("stream3x1_bn") == (2 if fused else 0) and dgrads.count("stream3x1") == (0 if fused else 2), dgrads
     (dx0, g0), (dx1, g1) = res
     assert rel_l2(dx1, dx0) < 1e-2
     assert set(g0) == set(g1) and len(g0) == 12
@@ -1132,9 +1143,11 @@ def test_r2plus1d_block_backward_with_and_without_the_fused_mid_batchnorm(dvt, d
     for p_ in blk.parameters():
         p_.grad = None
     x = x0.clone().requires_grad_(True)
+    calls.clear()
     out = blk.forward_ndhwc((x, N, T, H, W), torch.bfloat16)[0]
     monkeypatch.setattr(F, "HALO_CONV", False)
     out.backward(gy)
+    assert [c["wgrad"] for c in calls].count("implicit_bn") == 2, calls
     assert rel_l2(x.grad, dx0) < 1e-2
     for n, p_ in blk.named_parameters():
         assert rel_l2(p_.grad, g0[n]) < (1e-2 if n.endswith("weight") and g0[n].dim() > 1 else 2e-2), n
@@ -1230,7 +1243,7 @@ def test_strided_data_gradient_by_parity_classes(dvt, device, dtype, geom):
 @pytest.mark.parametrize("short", ["none", "alias", "compact"])
 def test_conv_block_backward_with_and_without_strided_class_launches(dvt, device, monkeypatch, short):
     """functional._ConvBnAct.backward routes the data gradient of a strided layer through the parity-class launches
-    (STRIDED_IMPLICIT, maps of at least STRIDED_IMPLICIT_MIN_PIXELS) or through dcol GEMM + col2im: same input gradient (the
+    (maps of at least STRIDED_IMPLICIT_MIN_PIXELS) or through dcol GEMM + col2im: same input gradient (the
     shortcut's gradient joined: none / the full-size one of fork="alias" / the compact one of a strided 1x1 shortcut), same
     parameter gradients -- the weight gradient's split-K reduce is carried by the last class launch."""
     F = dvt.functional
@@ -1245,8 +1258,10 @@ def test_conv_block_backward_with_and_without_strided_class_launches(dvt, device
     gy = torch.randn(N * Ho * Wo, Cout, generator=g).to(torch.bfloat16).cuda()
     gs = torch.randn(N * (H * W if short == "alias" else Ho * Wo), Cin, generator=g).to(torch.bfloat16).cuda()
     res = []
+    calls = record_conv_routes(monkeypatch, F)
     for floor in (1 << 40, 0):                       # class launches off (nothing is large enough) / on for every size
         monkeypatch.setattr(F, "STRIDED_IMPLICIT_MIN_PIXELS", floor)
+        calls.clear()
         x = x0.clone().requires_grad_(True)
         conv.weight.grad = bn.weight.grad = bn.bias.grad = None
         fork = {"none": None, "alias": "alias", "compact": 2}[short]
@@ -1257,6 +1272,7 @@ def test_conv_block_backward_with_and_without_strided_class_launches(dvt, device
             y, second = out
             torch.autograd.backward([y, second], [gy, gs])
         res.append((x.grad.float().clone(), conv.weight.grad.clone(), bn.weight.grad.clone()))
+        assert [c["dgrad"] for c in calls] == ["strided" if floor == 0 else "gemm"], calls
     (dx0, dw0, dg0), (dx1, dw1, dg1) = res
     assert rel_l2(dx1, dx0) < 8e-3                   # (the explicit path rounds dcol to bf16 before it sums the taps)
     assert torch.equal(dw1, dw0) and torch.equal(dg1, dg0)

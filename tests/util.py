@@ -220,3 +220,35 @@ def assert_within_reference_lowprec(tag, e_out, errs, ref_out, ref_errs, factor=
         if grad_cap is not None:
             assert e <= grad_cap, (tag, k, "absolute cap", e, grad_cap)
     return worst, med / (med_ref + 1e-30)
+
+
+def record_conv_routes(monkeypatch, F):
+    """Wrap functional._ConvBnAct's three route resolvers: -> a list that receives one {"fwd", "wgrad", "dgrad"} dict per
+    _ConvBnAct forward call, in call order (wgrad / dgrad stay None until that call's backward has run)."""
+    calls = []
+    forward, fwd_route, wgrad_route, dgrad_route = F._ConvBnAct.forward, F._fwd_route, F._wgrad_route, F._dgrad_route
+
+    def fwd(ctx, *a, **k):
+        ctx.route_record = {"fwd": None, "wgrad": None, "dgrad": None}
+        calls.append(ctx.route_record)
+        return forward(ctx, *a, **k)
+
+    def fwd_r(*a, **k):
+        r = fwd_route(*a, **k)
+        calls[-1]["fwd"] = r[0]
+        return r
+
+    def wgrad_r(ctx, *a, **k):
+        ctx.route_record["wgrad"] = wgrad_route(ctx, *a, **k)
+        return ctx.route_record["wgrad"]
+
+    def dgrad_r(ctx, *a, **k):
+        r = dgrad_route(ctx, *a, **k)
+        ctx.route_record["dgrad"] = r[0]
+        return r
+
+    monkeypatch.setattr(F._ConvBnAct, "forward", staticmethod(fwd))
+    monkeypatch.setattr(F, "_fwd_route", fwd_r)
+    monkeypatch.setattr(F, "_wgrad_route", wgrad_r)
+    monkeypatch.setattr(F, "_dgrad_route", dgrad_r)
+    return calls
