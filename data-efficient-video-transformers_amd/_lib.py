@@ -229,6 +229,8 @@ SIGNATURES = {
     "dvt_f1_samples": (c_int, [c_p, c_p, c_i64, c_int, c_p, c_int, c_p, c_p, c_p]),
     "dvt_average_precision_workspace_bytes": (C.c_size_t, [c_i64, c_int]),
     "dvt_average_precision": (c_int, [c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p]),
+    "dvt_multilabel_report_workspace_bytes": (C.c_size_t, [c_i64]),
+    "dvt_multilabel_report": (c_int, [c_p, c_p, c_i64, c_int, c_f, c_p, c_p, c_p, c_p]),
     "dvt_l2norm_rows_fwd": (c_int, [c_p, c_p, c_p, c_i64, c_int, c_f, c_int, c_p]),
     "dvt_l2norm_rows_bwd": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_int, c_f, c_int, c_p]),
     "dvt_cosine_rows": (c_int, [c_p, c_p, c_p, c_i64, c_int, c_f, c_int, c_p]),
@@ -296,6 +298,8 @@ SIGNATURES = {
     "dvt_conv3d_implicit_k": (c_i64, [C.POINTER(Conv3dDesc)]),
     "dvt_conv3d_implicit_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc)]),
     "dvt_conv3d_implicit": (c_int, [C.POINTER(Conv3dDesc), c_p]),
+    "dvt_conv2p1d_l1_supported": (c_int, [C.POINTER(Conv3dDesc)]),
+    "dvt_conv2p1d_l1": (c_int, [C.POINTER(Conv3dDesc), c_p]),
     "dvt_conv3d_weight_pack": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_p]),
     "dvt_bn1d_relu_fwd": (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_int, c_f, c_f,
                                   c_int, c_int, c_p]),

@@ -2255,31 +2255,47 @@ def sigmoid_bce(z: Tensor, target: Tensor) -> Tensor:
 
 
 # ------------------------------------------------------------------ 3-D convolution + eval BatchNorm (inference only)
-def _conv3d_pack(conv: torch.nn.Conv3d, bn, Cp: int, dtype: torch.dtype, K: int):
-    """Packed weights [Cout, K] and the folded BatchNorm (scale, shift) of a Conv3d -> BatchNorm3d pair, made once and cached
+def _conv3d_pack(conv: torch.nn.Conv3d, bn, Cp: int, dtype: torch.dtype, K: int, Cop: Optional[int] = None):
+    """Packed weights [Cop, K] and the folded BatchNorm (scale, shift) of a Conv3d -> BatchNorm3d pair, made once and cached
     on the module; the cache is dropped when a parameter or running statistic changes version (load_state_dict, an optimiser
-    step, in-place edits) or moves (``.to``)."""
+    step, in-place edits) or moves (``.to``).  Cop > Cout (the output planes carried to a multiple of 8): the rows and the
+    affine beyond Cout are zero, so those planes come out as zeros."""
     ts = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
     stamp = tuple((t.data_ptr(), t._version) for t in ts if t is not None) + ((bn.eps,) if bn is not None else ())
     cache = conv.__dict__.setdefault("_dvt_conv3d_cache", {})
-    key = (dtype, Cp, K)
+    Cout = conv.out_channels
+    Cop = Cout if Cop is None else Cop
+    key = (dtype, Cp, K) if Cop == Cout else (dtype, Cp, K, Cop)
     hit = cache.get(key)
     if hit is not None and hit[0] == stamp:
         return hit[1]
-    w = ops.conv3d_weight_pack(conv.weight, Cp, K, dtype)
+    wsrc = conv.weight
+    if Cop != Cout:                                   # (weight plumbing, once per cache fill)
+        wsrc = torch.zeros((Cop,) + tuple(conv.weight.shape[1:]), dtype=torch.float32, device=conv.weight.device)
+        wsrc[:Cout] = conv.weight.detach()
+    w = ops.conv3d_weight_pack(wsrc, Cp, K, dtype)
     scale = shift = None
     if bn is not None:
         scale, shift = ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+        if Cop != Cout:
+            scale = torch.cat((scale, scale.new_zeros(Cop - Cout)))
+            shift = torch.cat((shift, shift.new_zeros(Cop - Cout)))
     cache.clear()
     cache[key] = (stamp, (w, scale, shift))
     return w, scale, shift
 
 
+CONV3D_ROUTES = ("implicit", "l1")         # dvt_conv3d_implicit / dvt_conv2p1d_l1 (R(2+1)D layer-1 halves, 16-bit)
+
+
 def conv3d_bn_act(x: Tensor, conv: torch.nn.Conv3d, bn, geom, *, relu: bool, residual: Optional[Tensor] = None,
-                  dtype: torch.dtype = torch.bfloat16):
+                  dtype: torch.dtype = torch.bfloat16, cout_multiple: int = 1, route: str = "implicit"):
     """Inference-only conv3d -> eval BatchNorm3d (-> + residual) (-> ReLU) in ONE launch (dvt_conv3d_implicit with the
     BatchNorm folded into its epilogue).  geom = (N, T, H, W); x NDHWC [N*T*H*W, Cp] in ``dtype`` (Cp >= conv.in_channels,
-    a multiple of 8, channels past in_channels zero).  -> (y [N*To*Ho*Wo, Cout], To, Ho, Wo).  ``bn`` may be None."""
+    a multiple of 8, channels past in_channels zero).  -> (y [N*To*Ho*Wo, Cop], To, Ho, Wo) with Cop = Cout rounded up to
+    ``cout_multiple`` (the planes past Cout zero, ready to be the next convolution's input).  ``bn`` may be None.
+    route: one of CONV3D_ROUTES, the kernel that runs it ("l1" only where ops.conv2p1d_l1_supported; both read the same
+    packed weights and folded BatchNorm)."""
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in conv.parameters())
                                     or (bn is not None and any(p.requires_grad for p in bn.parameters()))):
         raise RuntimeError("conv3d_bn_act is inference-only (no backward): call it under torch.no_grad() / "
@@ -2290,10 +2306,15 @@ def conv3d_bn_act(x: Tensor, conv: torch.nn.Conv3d, bn, geom, *, relu: bool, res
     if x.dtype != dtype:
         raise TypeError(f"conv3d_bn_act: map is {x.dtype}, compute dtype {dtype}")
     k, s, p = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding)
-    Cout = conv.out_channels
+    Cout = -(-conv.out_channels // cout_multiple) * cout_multiple
     K = ops.conv3d_implicit_k(x, geom, Cout, k, s, p)
-    w, scale, shift = _conv3d_pack(conv, bn, x.shape[1], dtype, K)
-    y = ops.conv3d_implicit(x, w, geom, Cout, k, s, p, scale=scale, shift=shift, residual=residual, relu=relu)
+    w, scale, shift = _conv3d_pack(conv, bn, x.shape[1], dtype, K, Cout)
+    if route == "l1":
+        y = ops.conv2p1d_l1(x, w, geom, Cout, k, s, p, scale=scale, shift=shift, residual=residual, relu=relu)
+    elif route == "implicit":
+        y = ops.conv3d_implicit(x, w, geom, Cout, k, s, p, scale=scale, shift=shift, residual=residual, relu=relu)
+    else:
+        raise ValueError(f"conv3d_bn_act: route {route!r} not in {CONV3D_ROUTES}")
     return (y,) + ops.conv3d_out(geom, k, s, p)
 
 

@@ -394,3 +394,21 @@ class FrameTransformer(LightningModule):
         loss, data = self._loss(batch)
         self._accumulate(data, batch[0])
         return loss
+
+    def test_epoch(self, batches, callback=None):
+        """The reference's ``trainer.test(model, ...)`` (main.py:111) in one call: ``test_step`` over ``batches`` with the
+        module in eval() under torch.inference_mode() (as Lightning runs it: the R(2+1)D encoder takes its folded inference
+        route where that is the faster one, video_resnet.inference_route), then ``callback.on_test_epoch_end`` (default: a
+        ``metrics.TransformerEval()``), whose result is returned.  The module's train / eval mode is restored afterwards."""
+        if callback is None:
+            from ..metrics import TransformerEval
+            callback = TransformerEval()
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.inference_mode():
+                for i, batch in enumerate(batches):
+                    self.test_step(batch, i)
+                return callback.on_test_epoch_end(None, self)
+        finally:
+            self.train(was_training)

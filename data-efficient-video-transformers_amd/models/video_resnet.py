@@ -111,11 +111,53 @@ class Conv3DSimple(nn.Conv3d):
         return stride, stride, stride
 
 
-def _conv3d(fm, conv, bn, relu, dtype, residual=None):
+# Kernel of each layer-1 half on the folded route where both dvt_conv2p1d_l1 and dvt_conv3d_implicit take it (16-bit), the
+# faster one as measured on the MI355X at the reference test step: "spatial" = 64 -> 144 (1,3,3),
+# "temporal" = 144 -> 64 (3,1,1).
+L1_ROUTES = {"spatial": "l1", "temporal": "l1"}
+
+
+def _route(fm, conv, dtype):
+    """One of F.CONV3D_ROUTES for this convolution of the folded route."""
+    if dtype not in (torch.bfloat16, torch.float16) or conv.in_channels not in (64, 144):
+        return "implicit"
+    y, N, T, H, W = fm
+    k, s, p = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding)
+    if y.shape[1] != conv.in_channels or not ops.conv2p1d_l1_supported(y, (N, T, H, W), conv.out_channels, k, s, p):
+        return "implicit"
+    return L1_ROUTES["spatial" if k[0] == 1 else "temporal"]
+
+
+def _conv3d(fm, conv, bn, relu, dtype, residual=None, cout_multiple=1, route="implicit"):
     """conv3d -> eval BN (-> + residual) (-> ReLU) on an NDHWC matrix, one launch (F.conv3d_bn_act)."""
     y, N, T, H, W = fm
-    out, To, Ho, Wo = F.conv3d_bn_act(y, conv, bn, (N, T, H, W), relu=relu, residual=residual, dtype=dtype)
+    out, To, Ho, Wo = F.conv3d_bn_act(y, conv, bn, (N, T, H, W), relu=relu, residual=residual, dtype=dtype,
+                                      cout_multiple=cout_multiple, route=route)
     return (out, N, To, Ho, Wo)
+
+
+def _folded_pair(fm, pair, bn, relu, dtype, residual=None):
+    """Conv2Plus1D -> BN (-> + residual) (-> ReLU) of the inference route: the spatial half with the mid BatchNorm + ReLU
+    folded (mid planes 45 / 230 / 460 / 921 carried as 48 / 232 / 464 / 928, the extra planes zero), then the temporal half
+    with the block's BatchNorm, shortcut and ReLU folded -- two launches."""
+    mid = _conv3d(fm, pair[0], pair[1], True, dtype, cout_multiple=8, route=_route(fm, pair[0], dtype))
+    return _conv3d(mid, pair[3], bn, relu, dtype, residual=residual, route=_route(mid, pair[3], dtype))
+
+
+# Compute dtypes in which eval() under torch.inference_mode() takes the folded route.  Measured on the MI355X at the reference
+# test step (28 clips of 12 x 112^2, DESIGN 4.13), encoder alone: fp32 24.5 ms folded vs 78.4 ms on the eval() + no_grad
+# route; bf16 5.26 ms folded (layer 1 on dvt_conv2p1d_l1) vs 3.69 ms -- in 16 bits the training route's layer-specialised
+# halo / window / streamed-weight kernels still win layer 1 and the stem, so 16-bit inference keeps that route
+# (VideoResNet.features_folded runs the folded one in any dtype).
+FOLDED_ROUTE_DTYPES = (torch.float32,)
+
+
+def inference_route(module: nn.Module) -> bool:
+    """The folded inference route of an R(2+1)D VideoResNet runs in eval() under torch.inference_mode() (Lightning's
+    test / predict) where it is the faster one (FOLDED_ROUTE_DTYPES); eval() under torch.no_grad() and training keep the
+    training kernels' route."""
+    return (not module.training and torch.is_inference_mode_enabled()
+            and getattr(module, "compute_dtype", None) in FOLDED_ROUTE_DTYPES)
 
 
 class BasicBlock(nn.Module):
@@ -160,6 +202,15 @@ class BasicBlock(nn.Module):
         out = _spatial(out, c2[0], c2[1], True, dtype)
         return _temporal(out, c2[3], self.conv2[1], True, dtype, residual=residual)     # out += residual; relu
 
+    def forward_folded(self, fm, dtype):
+        """Inference route of an R(2+1)D block: every convolution one dvt_conv3d_implicit launch with its BatchNorm (and
+        the shortcut add and ReLU of the block's end) in the epilogue."""
+        out = _folded_pair(fm, self.conv1[0], self.conv1[1], True, dtype)
+        residual = fm[0]
+        if self.downsample is not None:
+            residual = _conv3d(fm, self.downsample[0], self.downsample[1], False, dtype)[0]
+        return _folded_pair(out, self.conv2[0], self.conv2[1], True, dtype, residual=residual)     # out += residual; relu
+
     def _forward_3d(self, fm, dtype):
         out = _conv3d(fm, self.conv1[0], self.conv1[1], True, dtype)
         residual = fm[0]
@@ -184,6 +235,22 @@ class R2Plus1dStem(nn.Sequential):
             nn.BatchNorm3d(45), nn.ReLU(inplace=True),
             nn.Conv3d(45, 64, kernel_size=(3, 1, 1), stride=(1, 1, 1), padding=(1, 0, 0), bias=False),
             nn.BatchNorm3d(64), nn.ReLU(inplace=True))
+
+
+def _clip_ndhwc8(x, dt):
+    """[N, 3, T, H, W] -> NDHWC [N*T*H*W, 8] in the compute dtype, planes 3..7 zero (the kernel's 16-byte channel chunks).
+    x may also be the [N, T, 3, H, W] clip stack permuted (FrameTransformer.vid_step): its per-frame planes are read as
+    they lie."""
+    N, _, T, H, W = x.shape
+    frames = x.permute(0, 2, 1, 3, 4)
+    src = frames.reshape(N * T, 3, H, W) if frames.is_contiguous() and not x.is_contiguous() else x.reshape(N, 3, T * H, W)
+    if dt in (torch.bfloat16, torch.float16):
+        return ops.nchw_to_nhwc_pad(src, dt, 8)
+    src = src.reshape(src.shape[0], 3, -1)                       # (the one-pass form writes 16-bit maps only)
+    xt = ops.transpose_last2(src if src.dtype == dt else ops.cast(src, dt))
+    y = ops.zeros((N * T * H * W, 8), dt, x.device)
+    ops.copy2d(xt, y, N * T * H * W, 3, 3, 8)
+    return y
 
 
 class VideoResNet(nn.Module):
@@ -231,6 +298,8 @@ class VideoResNet(nn.Module):
             raise ValueError("VideoResNet expects clips [N, 3, T, H, W]")
         if isinstance(self.stem, BasicStem):
             return self._features_3d(x)
+        if inference_route(self):
+            return self.features_folded(x)
         dt = self.compute_dtype
         N, _, T, H, W = x.shape
         frames = x.permute(0, 2, 1, 3, 4)                  # [N, T, 3, H, W]: per-frame NCHW
@@ -259,17 +328,29 @@ class VideoResNet(nn.Module):
                                       "call .eval() and run it under torch.no_grad()")
         dt = self.compute_dtype
         N, _, T, H, W = x.shape
-        # [N, 3, T, H, W] -> NDHWC [N*T*H*W, 8] in the compute dtype, planes 3..7 zero (the kernel's 16-byte channel chunks)
-        if dt in (torch.bfloat16, torch.float16):
-            y = ops.nchw_to_nhwc_pad(x.reshape(N, 3, T * H, W), dt, 8)
-        else:                                                   # (the one-pass form writes 16-bit maps only)
-            xt = ops.transpose_last2((x if x.dtype == dt else ops.cast(x, dt)).reshape(N, 3, T * H * W))
-            y = ops.zeros((N * T * H * W, 8), dt, x.device)
-            ops.copy2d(xt, y, N * T * H * W, 3, 3, 8)
+        y = _clip_ndhwc8(x, dt)
         fm = _conv3d((y, N, T, H, W), self.stem[0], self.stem[1], True, dt)
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for blk in layer:
                 fm = blk.forward_ndhwc(fm, dt)
+        y, N, T, H, W = fm
+        return F.mean_rows(y.view(N, T * H * W, y.shape[1]))          # AdaptiveAvgPool3d(1)
+
+    def features_folded(self, x):
+        """R(2+1)D folded inference route (what ``features`` runs in eval() under torch.inference_mode(), see
+        inference_route; callable directly in any compute dtype, eval mode, no autograd): every Conv3d -> BatchNorm3d
+        (-> + shortcut) (-> ReLU) of the stem, the four layers and the downsamples is one dvt_conv3d_implicit launch with
+        the running statistics folded into its epilogue; weights are packed and BatchNorm folded once per module
+        (F._conv3d_pack)."""
+        if self.training:
+            raise RuntimeError("features_folded folds the running statistics: put the module in eval()")
+        dt = self.compute_dtype
+        N, _, T, H, W = x.shape
+        fm = (_clip_ndhwc8(x, dt), N, T, H, W)
+        fm = _folded_pair(fm, self.stem, self.stem[4], True, dt)
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in layer:
+                fm = blk.forward_folded(fm, dt)
         y, N, T, H, W = fm
         return F.mean_rows(y.view(N, T * H * W, y.shape[1]))          # AdaptiveAvgPool3d(1)
 

@@ -1129,6 +1129,26 @@ def average_precision(probs: Tensor, labels: Tensor):
     return out[0:1], out[1:2], out[2:]
 
 
+def multilabel_report_counts(probs: Tensor, labels: Tensor, threshold: float):
+    """``classification_report(labels, probs > threshold)`` as exact counts (dvt_multilabel_report) -> (counts int64 [4, C]:
+    TP / FP / FN / support per class, row_sums f64 [3]: the sums over rows of the per-row precision / recall / F1)."""
+    _need_cuda(probs, labels)
+    probs = probs.contiguous() if probs.dtype == torch.float32 else cast(probs.contiguous(), torch.float32)
+    lab = labels.contiguous()
+    if lab.dtype != torch.uint8:
+        lab = (lab != 0).to(torch.uint8)          # dtype plumbing of a label mask
+    N, Cn = probs.shape
+    if tuple(lab.shape) != (N, Cn):
+        raise ValueError(f"multilabel_report_counts: labels {tuple(lab.shape)} != probs {(N, Cn)}")
+    lib = L.load()
+    ws = workspace(lib.dvt_multilabel_report_workspace_bytes(N), probs.device)
+    counts = torch.empty((4, Cn), dtype=torch.int64, device=probs.device)
+    sums = torch.empty((3,), dtype=torch.float64, device=probs.device)
+    L.check(lib.dvt_multilabel_report(probs.data_ptr(), lab.data_ptr(), N, Cn, float(threshold), counts.data_ptr(),
+                                      sums.data_ptr(), _p(ws), _stream()), "dvt_multilabel_report")
+    return counts, sums
+
+
 def l2norm_rows_fwd(x: Tensor, eps: float):
     _need_cuda(x)
     x = x.contiguous()
@@ -2175,6 +2195,40 @@ def conv3d_implicit(x: Tensor, w: Tensor, geom, Cout: int, k, stride, pad, *, sc
     d.workspace = _p(ws)
     with _timed("conv3d_implicit", 2 * M * Cout * x.shape[1] * k[0] * k[1] * k[2]):
         L.check(lib.dvt_conv3d_implicit(C.byref(d), _stream()), "dvt_conv3d_implicit")
+    return y
+
+
+def conv2p1d_l1_supported(x: Tensor, geom, Cout: int, k, stride, pad) -> bool:
+    """Is this convolution one of the layer-1 halves dvt_conv2p1d_l1 takes?"""
+    d = conv3d_desc(x, None, geom, Cout, k, stride, pad)
+    return bool(L.load().dvt_conv2p1d_l1_supported(C.byref(d)))
+
+
+def conv2p1d_l1(x: Tensor, w: Tensor, geom, Cout: int, k, stride, pad, *, scale: Optional[Tensor] = None,
+                shift: Optional[Tensor] = None, residual: Optional[Tensor] = None, relu: bool = False) -> Tensor:
+    """conv3d_implicit's contract for the layer-1 halves of R(2+1)D-18 (csrc/conv2p1d_l1.hip): x NDHWC [N*T*H*W, C], w packed
+    [Cout, conv3d_implicit_k(..)] (conv3d_weight_pack) -> y [N*T*H*W, Cout] = relu?(conv3d(x, w) * scale + shift + residual)."""
+    _need_cuda(x, w, scale, shift, residual)
+    x = x.contiguous()
+    if w.dtype != x.dtype:
+        raise TypeError(f"conv2p1d_l1: weights {w.dtype} != map {x.dtype}")
+    M = geom[0] * geom[1] * geom[2] * geom[3]
+    if residual is not None:
+        residual = residual.contiguous()
+        if residual.dtype != x.dtype or residual.numel() != M * Cout:
+            raise ValueError("conv2p1d_l1: residual must be [N*T*H*W, Cout] in the map's dtype")
+    for t in (scale, shift):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != Cout):
+            raise ValueError("conv2p1d_l1: scale / shift must be f32 [Cout]")
+    y = torch.empty((M, Cout), dtype=x.dtype, device=x.device)
+    d = conv3d_desc(x, w, geom, Cout, k, stride, pad, y=y)
+    lib = L.load()
+    K = lib.dvt_conv3d_implicit_k(C.byref(d))
+    if tuple(w.shape) != (Cout, K) or x.shape[0] != M:
+        raise ValueError(f"conv2p1d_l1: packed weights {tuple(w.shape)} != ({Cout}, {K}) or map rows {x.shape[0]} != {M}")
+    d.scale, d.shift, d.residual, d.relu = _p(scale), _p(shift), _p(residual), int(relu)
+    with _timed("conv2p1d_l1", 2 * M * Cout * x.shape[1] * k[0] * k[1] * k[2]):
+        L.check(lib.dvt_conv2p1d_l1(C.byref(d), _stream()), "dvt_conv2p1d_l1")
     return y
 
 

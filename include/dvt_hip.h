@@ -580,6 +580,14 @@ int dvt_f1_samples(const float* probs, const unsigned char* labels, int64_t N, i
 size_t dvt_average_precision_workspace_bytes(int64_t N, int C);
 int dvt_average_precision(const float* probs, const unsigned char* labels, int64_t N, int C, float* out_samples,
                           float* out_weighted, float* out_per_class, void* workspace, dvt_stream_t stream);
+/* Addition within ABI v5: classification_report(labels, probs > threshold) of callbacks.py:67-82 (the test epoch), as
+ * exact counts.  counts int64 [4, C] (device): rows TP, FP, FN, support per class.  row_sums f64 [3] (device): the sums
+ * over the N rows of the per-row precision, recall and F1 (each 0 where its denominator is 0, zero_division=0), in a
+ * fixed order.  Integer counts and fixed-order f64 sums, no atomics: two identical calls are bitwise equal.
+ * workspace >= dvt_multilabel_report_workspace_bytes(N). */
+size_t dvt_multilabel_report_workspace_bytes(int64_t N);
+int dvt_multilabel_report(const float* probs, const unsigned char* labels, int64_t N, int C, float threshold,
+                          int64_t* counts, double* row_sums, void* workspace, dvt_stream_t stream);
 
 /* ---------------------------------------------------------------- per-frame CNN encoder
  * src/models/custom_resnet.py:19-153 (conv3x3 / 7x7 stem / 1x1 downsample, BatchNorm2d, ReLU,
@@ -1027,6 +1035,11 @@ int dvt_conv3d_implicit_supported(const dvt_conv3d_desc* desc);   /* 1: dvt_conv
 int64_t dvt_conv3d_implicit_k(const dvt_conv3d_desc* desc);         /* row length of the packed weights; -1: unsupported */
 size_t dvt_conv3d_implicit_workspace_bytes(const dvt_conv3d_desc* desc);
 int dvt_conv3d_implicit(const dvt_conv3d_desc* desc, dvt_stream_t stream);
+/* Addition within ABI v5: the layer-1 halves of R(2+1)D-18 at inference, with the same descriptor, packed weights and
+ * epilogue as dvt_conv3d_implicit: 64 -> 144 (1,3,3) / 1 / (0,1,1) and 144 -> 64 (3,1,1) / 1 / (1,0,0), bf16 / fp16, any
+ * N, T, H, W whose map stays below 2 GiB.  No workspace, no atomics.  _supported: 1 if the descriptor is one of them. */
+int dvt_conv2p1d_l1_supported(const dvt_conv3d_desc* desc);
+int dvt_conv2p1d_l1(const dvt_conv3d_desc* desc, dvt_stream_t stream);
 /* w f32 [Cout][Cin][kt][kh][kw] (nn.Conv3d.weight) -> dst [Cout][ld] in dst_dtype, column ((dt*kh + dh)*kw + dw)*Cp + c,
  * zero for c >= Cin and for columns >= kt*kh*kw*Cp.  Cp >= Cin, ld >= kt*kh*kw*Cp. */
 int dvt_conv3d_weight_pack(const float* w, void* dst, int dst_dtype, int Cout, int Cin, int kt, int kh, int kw, int Cp,
