@@ -3,7 +3,7 @@ ed-fish/data-efficient-video-transformers.
 
 Layout
   csrc/          hand-written HIP kernels (gfx950) + the C ABI  -> libdvt_hip.so
-  _lib.py        ctypes binding of include/dvt_hip.h
+  _lib.py        ctypes binding, derived at import from include/dvt_hip.h
   ops.py         raw operator wrappers (no autograd)
   functional.py  torch.autograd.Function layer (fused residual blocks)
   models/        mirror of the reference's src/models surface (vit.py, ...)

@@ -7,6 +7,7 @@ falls back to torch arithmetic.
 from __future__ import annotations
 
 import ctypes as C
+import re
 from typing import NamedTuple, Optional, Tuple
 
 import torch
@@ -366,7 +367,7 @@ def layernorm_flush() -> None:
         return
     todo, _ln_deferred = _ln_deferred, []
     arr = (L.LnPending * len(todo))(*[pn for pn, _ in todo])
-    L.check(L.load().dvt_layernorm_reduce_group(C.cast(arr, C.c_void_p), len(todo), _stream()), "dvt_layernorm_reduce_group")
+    L.check(L.load().dvt_layernorm_reduce_group(arr, len(todo), _stream()), "dvt_layernorm_reduce_group")
     for pn, done in todo:
         pn.valid = 0
         if done is not None:
@@ -543,11 +544,17 @@ class GemmPlan(NamedTuple):
     out: str = "in"
 
 
-GEMM_OUTS = ("in", "f32", "slab")
-GEMM_KERNELS = ("none", "small", "small_pair", "dma", "dma224", "mfma128", "generic64", "tiny_wave", "tiny_thread")
-GEMM_REDUCES = ("none", "plain", "epilogue", "deferred")
-GEMM_COLSUMS = ("none", "fused", "alone")
-GEMM_CARRIES = ("none", "tail", "alone", "wide", "conv")
+def _enum_names(enum: str, prefix: str) -> Tuple[str, ...]:
+    """The enumerators of a dvt_hip.h enum as lower-cased names without ``prefix`` (a regular expression), indexed by value."""
+    names = {v: re.fullmatch(prefix + r"(\w+)", k).group(1).lower() for k, v in L.ENUMS[enum].items()}
+    return tuple(names[i] for i in range(len(names)))
+
+
+GEMM_OUTS = ("in", "f32", "slab")                     # dvt_gemm_plan_info.out_form (no enum in the header)
+GEMM_KERNELS = _enum_names("dvt_gemm_kernel", "DVT_GEMM_K_")
+GEMM_REDUCES = _enum_names("dvt_gemm_reduce", "DVT_GEMM_R_")
+GEMM_COLSUMS = _enum_names("dvt_gemm_colsum", "DVT_GEMM_CS_")
+GEMM_CARRIES = _enum_names("dvt_gemm_carry", "DVT_GEMM_CARRY_")
 
 
 def _plan_tuple(q) -> GemmPlan:
@@ -777,7 +784,7 @@ class AttnPlan(NamedTuple):
     lds2: int = 0
 
 
-ATTN_FAMILIES = ("none", "q1", "res", "online", "small", "generic", "q1", "fused", "pair", "small", "generic")
+ATTN_FAMILIES = _enum_names("dvt_attn_family", "DVT_ATTN_[FB]_")
 
 
 def attention_plan(q: Tensor, k: Tensor, v: Tensor, o: Tensor, *, bwd: bool = False, do: Optional[Tensor] = None,
@@ -1010,7 +1017,7 @@ def scaled_emit_group(scale: Tensor, entries) -> None:
         e = arr[i]
         e.src, e.dst, e.dst_lp = src.data_ptr(), (dst.data_ptr() if dst is not None else None), (lp.data_ptr() if lp is not None else None)
         e.n, e.accumulate, e.lp_dtype = src.numel(), int(bool(acc)), (dt(lp) if lp is not None else 0)
-    L.check(L.load().dvt_scaled_emit_group(scale.data_ptr(), C.cast(arr, C.c_void_p), len(entries), _stream()),
+    L.check(L.load().dvt_scaled_emit_group(scale.data_ptr(), arr, len(entries), _stream()),
             "dvt_scaled_emit_group")
 
 
@@ -1750,7 +1757,7 @@ def conv2d_implicit(x: Tensor, wp: Tensor, N: int, Cc: int, H: int, W: int, Cout
     rows = N * Ho * Wo
     nb = (x.numel() + wp.numel() + rows * Cout * (2 if residual is not None else 1)) * x.element_size()    # implicit GEMM: the image is read once, not kh*kw times
     if carry is not None and carry.valid:             # the layer's weight-gradient reduce rides in this launch's grid tail
-        d.carry = C.addressof(carry)
+        d.carry = C.pointer(carry)
     wsb = int(lib.dvt_conv2d_implicit_workspace_bytes(C.byref(d)))
     if wsb:                                           # few output rows x deep K: split-K slabs (dvt_conv2d_implicit_workspace_bytes)
         d.workspace = workspace(wsb, x.device, slot="conv_split").data_ptr()
@@ -1856,7 +1863,7 @@ def conv2d_implicit_wgrad(x: Tensor, dz: Tensor, N: int, Cc: int, H: int, W: int
     if defer_reduce:
         pending._keep = (out, ws)
         d.defer_reduce = 1
-        d.pending = C.addressof(pending)
+        d.pending = C.pointer(pending)
     rows = dz.shape[0]
     nb = (x.numel() + dz.numel()) * x.element_size() + out.numel() * out.element_size()
     with _timed(("conv", "wgrad", kh * kw * Cc, Cout, rows, nb), 2.0 * rows * Cout * kh * kw * Cc):
@@ -1915,7 +1922,7 @@ def conv_weight_pack_group(entries) -> None:
         assert dst.is_contiguous() and dst.numel() == (cout_p * ld if kind == 0 else cin_p * ntaps * cout_p)
         e.src, e.dst = src.data_ptr(), dst.data_ptr()
         e.cout_l, e.cin_l, e.kh, e.kw, e.cout_p, e.cin_p, e.ld, e.kind, e.dtype = cout_l, cin_l, kh, kw, cout_p, cin_p, ld, kind, dt(dst)
-    L.check(L.load().dvt_conv_weight_pack_group(C.cast(arr, C.c_void_p), len(entries), _stream()), "dvt_conv_weight_pack_group")
+    L.check(L.load().dvt_conv_weight_pack_group(arr, len(entries), _stream()), "dvt_conv_weight_pack_group")
 
 
 def conv_weight_pack(w: Tensor, ld: int, dtype: torch.dtype) -> Tensor:

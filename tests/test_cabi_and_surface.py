@@ -4,6 +4,8 @@ reference's surface; the product path refuses to run without a GPU."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -12,9 +14,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _header():
+    return open(os.path.join(ROOT, "include", "dvt_hip.h")).read()
+
+
 def _declared():
-    text = open(os.path.join(ROOT, "include", "dvt_hip.h")).read()
-    return sorted(set(re.findall(r"\b(dvt_[a-z0-9_]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(dvt_[a-z0-9_]+)\s*\(", _header())))
 
 
 def test_library_exports_every_declared_symbol():
@@ -27,6 +32,38 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), f"{n} declared in include/dvt_hip.h but not exported"
     # the ctypes table covers exactly the header
     assert sorted(dvt_amd._lib.SIGNATURES) == names
+    # ... with one argument type per parameter, counted here (commas of the prototype) and not by the binding's parser
+    code = re.sub(r"/\*.*?\*/", " ", _header(), flags=re.S)
+    for n in names:
+        (params,) = re.findall(rf"\b{n}\s*\(([^()]*)\)\s*;", code)
+        argtypes = dvt_amd._lib.SIGNATURES[n][1]
+        assert len(argtypes) == (0 if params.strip() == "void" else params.count(",") + 1), n
+        assert None not in argtypes, n
+
+
+def test_descriptor_layouts_match_the_c_compiler(tmp_path):
+    """sizeof of every descriptor struct and offsetof / size of every field, as the host C compiler lays out
+    include/dvt_hip.h, against the ctypes Structures the binding derives from the same header."""
+    from dvt_amd import _lib
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    if cc is None:
+        pytest.skip("no host C compiler (cc / gcc / clang) on PATH")
+    assert len(_lib.STRUCTS) == len(re.findall(r"\btypedef\s+struct\b", _header())) >= 14
+    lines = ['#include <stdio.h>', '#include "dvt_hip.h"', 'int main(void) {']
+    for name, st in _lib.STRUCTS.items():
+        lines.append(f'  printf("{name} - %zu\\n", sizeof({name}));')
+        lines += [f'  printf("{name} {f} %zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f, _ in st._fields_]
+    lines += ['  return 0;', '}']
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"), str(tmp_path / "layout.c")],
+                   check=True, capture_output=True, text=True)
+    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
+    compiled = [tuple(line.split()) for line in out.splitlines()]
+    derived = []
+    for name, st in _lib.STRUCTS.items():
+        derived.append((name, "-", str(ctypes.sizeof(st))))
+        derived += [(name, f, str(getattr(st, f).offset), str(getattr(st, f).size)) for f, _ in st._fields_]
+    assert len(compiled) > 14 and compiled == derived
 
 
 def test_no_kernel_of_the_library_lost_an_address_space():
