@@ -10,6 +10,12 @@ The test epoch (``on_test_epoch_end``, callbacks.py:67-82) prints scikit-learn's
 threshold 0.3: here the counts behind it (per-class TP / FP / FN / support, the per-row ratio sums of the "samples"
 average) come from one device reduction (``ops.multilabel_report_counts``) and the ratios of those few integers are
 formed in float64 on the host.
+
+``SSLOnlineEval`` (callbacks.py:147-300) is the online probe of the contrastive model: after every training batch it trains
+an ``SSLEvaluator`` on the detached embedding (three launches, csrc/probe.hip), after every validation batch it accumulates
+the probe's probabilities, and at the end of the validation epoch it logs weighted F1 / recall / precision / average
+precision of the binarised predictions at six thresholds, from one launch of integer counts
+(``ops.multilabel_sweep_counts``) and float64 ratios on the host.
 """
 from __future__ import annotations
 
@@ -28,6 +34,13 @@ TARGET_NAMES = ("Action", "Animation", "Adventure", "Comedy", "Crime", "Document
                 "History", "Horror", "Music", "Romance", "Mystery", "TVMovie", "ScienceFiction", "Thriller", "War",
                 "Western")                                        # callbacks.py:70-71
 _REPORT_FIELDS = ("precision", "recall", "f1-score", "support")
+ONLINE_THRESHOLDS = (0.0, 0.1, 0.2, 0.3, 0.4, 0.5)                # callbacks.py:256
+ONLINE_TABLE_THRESHOLD = 0.3                                      # callbacks.py:277
+ONLINE_TABLE_ROWS = 20                                            # callbacks.py:287
+ONLINE_TARGET_NAMES = ("Action", "Adventure", "Comedy", "Crime", "Documentary", "Drama", "Family", "Fantasy", "History",
+                       "Horror", "Music", "Mystery", "Science Fiction", "Thriller", "War")     # callbacks.py:251-252
+ONLINE_LR = 0.005                                                 # callbacks.py:167
+_ONLINE_FIELDS = ("f1", "recall", "precision", "avg_precision")
 
 
 def gather_rows(t: torch.Tensor, group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
@@ -111,6 +124,61 @@ def format_report(report: Dict[str, Dict[str, float]], digits: int = 2) -> str:
     return text
 
 
+def _ratio1(num: int, den: int) -> float:
+    return num / den if den > 0 else 1.0                          # zero_division=1
+
+
+def online_scores_from_counts(tp, fp, fn, support, n_rows: int) -> Dict[str, float]:
+    """Per-class TP / FP / FN / support of one threshold (integer sequences) over n_rows samples -> what the reference
+    logs for it (callbacks.py:258-265): ``f1_score`` / ``recall_score`` / ``precision_score(average="weighted",
+    zero_division=1)`` and ``average_precision_score(average="weighted")`` of the BINARISED predictions, in float64.
+
+    A class ratio with a zero denominator is 1; the weights are support / sum(support).  A 0/1 score has one operating
+    point besides "everything predicted", so per class with P = support:
+        AP = (TP / P) * TP / (TP + FP) + (1 - TP / P) * P / n_rows,
+    the first term 0 when nothing is predicted, and AP = 0 for a class without support (its weight is 0 as well)."""
+    tp, fp, fn, support = ([int(v) for v in a] for a in (tp, fp, fn, support))
+    total = sum(support)
+    f1 = rec = prec = ap = 0.0
+    for k, P in enumerate(support):
+        if P == 0:
+            continue                                              # weight 0 (the class's own ratios do not matter)
+        w = P / total
+        f1 += w * _ratio1(2 * tp[k], 2 * tp[k] + fp[k] + fn[k])
+        rec += w * _ratio1(tp[k], tp[k] + fn[k])
+        prec += w * _ratio1(tp[k], tp[k] + fp[k])
+        r = tp[k] / P
+        first = r * tp[k] / (tp[k] + fp[k]) if tp[k] + fp[k] > 0 else 0.0
+        ap += w * (first + (1.0 - r) * P / n_rows)
+    if total == 0:                                                # no positive label at all: every class ratio is 1 / 0
+        return dict(zip(_ONLINE_FIELDS, (float("nan"),) * 4))
+    return dict(zip(_ONLINE_FIELDS, (f1, rec, prec, ap)))
+
+
+def online_scalars_from_counts(counts, support, n_rows: int, thresholds=ONLINE_THRESHOLDS, state: str = "val"
+                               ) -> Dict[str, float]:
+    """counts [T, 3, C] (TP, FP, FN per class per threshold) and support [C] -> the 4 T scalars under the reference's keys
+    ``{state}/online/{f1,recall,precision,avg_precision}@{str(t)}``."""
+    c, sup = counts.tolist(), support.tolist()
+    if len(c) != len(thresholds):
+        raise ValueError(f"{len(c)} count blocks for {len(thresholds)} thresholds")
+    out: Dict[str, float] = {}
+    for (tp, fp, fn), t in zip(c, thresholds):
+        for name, v in online_scores_from_counts(tp, fp, fn, sup, n_rows).items():
+            out[f"{state}/online/{name}@{str(t)}"] = v
+    return out
+
+
+def online_scalars(probs: torch.Tensor, labels: torch.Tensor, thresholds=ONLINE_THRESHOLDS, state: str = "val"
+                   ) -> Dict[str, float]:
+    """probs / labels [N, C] on the device -> the scalars of ``online_scalars_from_counts``: one sweep launch, one
+    device->host copy."""
+    counts, support = ops.multilabel_sweep_counts(probs, labels, thresholds)
+    host = torch.cat((counts.reshape(-1), support)).cpu()
+    T, C = counts.shape[0], counts.shape[2]
+    return online_scalars_from_counts(host[: T * 3 * C].view(T, 3, C), host[T * 3 * C:], probs.shape[0], thresholds, state)
+
+
 class TransformerEval:
     """callbacks.py:27-82: ``on_validation_epoch_end`` (same log keys, same accumulator reset) and ``on_test_epoch_end``.
 
@@ -155,6 +223,115 @@ class TransformerEval:
         pl_module.running_labels = []
         pl_module.running_logits = []
         return report
+
+
+class SSLOnlineEval:
+    """callbacks.py:147-300: the MLP probe trained online on the contrastive model's embedding.
+
+    Same constructor as the reference (``drop_p``, ``z_dim``, ``num_classes``, ``model``) plus ``group`` (data parallelism:
+    the validation rows of every rank are gathered before the scores are formed) and ``zero_grad``.
+
+    Deliberate deviations and notes:
+      - Kept: ``on_train_batch_end`` runs the model's forward in whatever mode the model is in, so in training the
+        encoder's BatchNorm running statistics move once more per batch and ``num_batches_tracked`` grows by 1.
+      - Kept: the reference never zeroes the probe's gradients, so ``loss.backward()`` accumulates them from step to step
+        and every SGD update uses the running sum.  That is the default here (``zero_grad=False``); ``zero_grad=True``
+        gives the conventional probe (each update uses its own batch's gradient).
+      - The probe step is three HIP launches (forward, loss, backward + SGD); the callback touches no parameter or
+        gradient of the model itself.
+      - ``running_logits`` / ``running_labels`` stay on the device (the reference moves them to the host), as in
+        ``TransformerEval``; the scores come from integer counts of one launch, the ratios are float64 on the host.
+      - The truth / guess table covers the first ``min(20, N)`` rows (the reference's fixed ``range(0, 20)`` fails on a
+        shorter epoch) and is handed to ``pl_module.logger.experiment.log`` only if such a logger exists (wandb is not
+        part of this tree); ``on_shared_end`` returns the scalars and the rows.
+      - ``get_representations`` does not ``squeeze()``: ``to_device`` already builds [B, D] rows (and a batch of one row
+        keeps its batch dimension)."""
+
+    def __init__(self, drop_p=0.1, z_dim=None, num_classes=None, model="MIT", group: Optional[dist.ProcessGroup] = None,
+                 zero_grad: bool = False):
+        self.drop_p = drop_p
+        self.z_dim = z_dim
+        self.num_classes = num_classes
+        self.model = model
+        self.group = group
+        self.zero_grad = zero_grad
+        self.lr = ONLINE_LR
+        self.optimizer = None
+
+    def on_pretrain_routine_start(self, trainer, pl_module):
+        from .models.evaluator import SSLEvaluator
+        device = next(pl_module.parameters()).device
+        probe = SSLEvaluator(n_input=self.z_dim, n_classes=self.num_classes, p=self.drop_p).to(device)
+        probe.compute_dtype = getattr(pl_module, "compute_dtype", torch.float32)
+        pl_module.non_linear_evaluator = probe
+        # torch.optim.SGD(lr=0.005) holds no state (no momentum, no decay): its step is the tail of the probe's third launch
+        self.optimizer = {"lr": self.lr, "momentum": 0.0, "weight_decay": 0.0, "params": list(probe.parameters())}
+
+    def get_representations(self, pl_module, x):
+        representations, _ = pl_module(x)
+        return representations
+
+    def to_device(self, batch, device):
+        """The contrastive collate's ``x_i_experts`` (per sample a list of expert tensors) -> [B, input] rows in one gather
+        launch (``rows_input``), labels stacked."""
+        from .models.contrastivemodel import rows_input
+        rows = [[t.reshape(-1) for t in experts] for experts in batch["x_i_experts"]]
+        D = sum(t.numel() for t in rows[0])
+        dtype = getattr(self, "_input_dtype", None) or torch.float32
+        x = rows_input(rows, D, dtype, device)
+        labels = torch.stack([torch.as_tensor(l) for l in batch["label"]]).to(device)
+        return x, labels
+
+    def _inputs(self, pl_module, batch):
+        device = next(pl_module.parameters()).device
+        self._input_dtype = getattr(pl_module, "compute_dtype", torch.float32)
+        x, labels = self.to_device(batch, device)
+        with torch.no_grad():
+            representations = self.get_representations(pl_module, x)
+        return representations.detach(), labels
+
+    def on_train_batch_end(self, trainer, pl_module, outputs, batch, batch_idx, data_loader_idx=0):
+        representations, labels = self._inputs(pl_module, batch)
+        probe = pl_module.non_linear_evaluator
+        mlp_loss, _ = probe.step(representations, labels, self.optimizer["lr"], accumulate=not self.zero_grad)
+        pl_module.log("train/online/loss", mlp_loss)
+        return mlp_loss
+
+    def on_validation_batch_end(self, trainer, pl_module, outputs, batch, batch_idx, data_loader_idx=0):
+        representations, labels = self._inputs(pl_module, batch)
+        with torch.no_grad():
+            mlp_loss, probs = pl_module.non_linear_evaluator.evaluate(representations, labels)
+        pl_module.log("val/online/loss", mlp_loss)
+        pl_module.running_logits.append(probs)
+        pl_module.running_labels.append(labels)
+        return mlp_loss
+
+    def on_validation_epoch_end(self, trainer, pl_module):
+        return self.on_shared_end(pl_module, "val")
+
+    def on_shared_end(self, pl_module, state):
+        labels = gather_rows(torch.cat(pl_module.running_labels), self.group)
+        probs = gather_rows(torch.cat(pl_module.running_logits), self.group)
+        scalars, rows = self._scores(probs, labels, state)
+        for k, v in scalars.items():
+            pl_module.log(k, v, on_epoch=True)
+        pl_module.running_labels = []
+        pl_module.running_logits = []
+        experiment = getattr(getattr(pl_module, "logger", None), "experiment", None)
+        if experiment is not None and callable(getattr(experiment, "log", None)):
+            experiment.log({"table": rows})
+        return scalars, rows
+
+    def _scores(self, probs, labels, state):
+        """-> (the 24 scalars, the truth / guess rows of the first min(20, N) samples at threshold 0.3)."""
+        scalars = online_scalars(probs, labels, ONLINE_THRESHOLDS, state)
+        n = min(ONLINE_TABLE_ROWS, probs.shape[0])
+        head = torch.cat(((labels[:n] != 0).to(torch.uint8), (probs[:n].float() > ONLINE_TABLE_THRESHOLD).to(torch.uint8))).cpu()
+        rows = [(self.translate_labels(head[i].tolist()), self.translate_labels(head[n + i].tolist())) for i in range(n)]
+        return scalars, rows
+
+    def translate_labels(self, label_vec):
+        return [ONLINE_TARGET_NAMES[i] if i < len(ONLINE_TARGET_NAMES) else str(i) for i, l in enumerate(label_vec) if l]
 
 
 class AveragePrecision:

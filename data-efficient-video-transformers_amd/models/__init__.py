@@ -11,3 +11,5 @@ from .LSTM import LSTMRegressor  # noqa: F401,E402
 from . import contrastivemodel, basicmlp  # noqa: F401,E402
 from .contrastivemodel import SpatioTemporalContrastiveModel  # noqa: F401,E402
 from .basicmlp import BasicMLP  # noqa: F401,E402
+from . import evaluator  # noqa: F401,E402
+from .evaluator import SSLEvaluator  # noqa: F401,E402

@@ -2349,3 +2349,114 @@ def gather_rows_ptr(rows, D: int, dtype: torch.dtype, device) -> Tensor:
     L.check(L.load().dvt_gather_rows_ptr(table.data_ptr(), R, P, out.data_ptr(), D, D, _DT[dtype], _stream()),
             "dvt_gather_rows_ptr")
     return out
+
+
+# ------------------------------------------------------------------ the online probe (csrc/probe.hip)
+ProbeDesc = L.STRUCTS["dvt_probe_desc"]
+PROBE_LIMITS = "2 <= B <= 1024 in training (1 <= B in eval), D <= 4096, H a multiple of 16 up to 2048, C <= 32, fp32 / bf16 / fp16"
+
+
+def probe_supported(B: int, D: int, H: int, Cn: int, dtype: torch.dtype, training: bool = True) -> bool:
+    """The range of the probe-step kernels (dvt_probe_supported; B = 1 is refused in training as torch's BatchNorm1d does)."""
+    if dtype not in _DT or (training and B < 2):
+        return False
+    return bool(L.load().dvt_probe_supported(B, D, H, Cn, _DT[dtype]))
+
+
+def probe_desc(x: Tensor, w1: Tensor, gamma: Tensor, beta: Tensor, running_mean: Tensor, running_var: Tensor,
+               num_batches_tracked: Optional[Tensor], w2: Tensor, b2: Tensor, *, training: bool, p: float = 0.0,
+               eps: float = 1e-5, momentum: float = 0.1, rng_state: Optional[Tensor] = None, rng_offset: int = 0):
+    """-> (descriptor, the tensors it points to) for one pass of the probe on x [B, D]: the forward's outputs h / z /
+    save_mean / save_invstd and the partial-logit workspace are allocated here; target, prob, loss, dlogits, logits, the
+    gradient buffers, lr and accumulate are filled in by ``probe_loss`` / ``probe_bwd_step``."""
+    _need_cuda(x, w1, gamma, beta, running_mean, running_var, num_batches_tracked, w2, b2, rng_state)
+    B, D = x.shape
+    H, Cn = w1.shape[0], w2.shape[0]
+    if not probe_supported(B, D, H, Cn, x.dtype, training):
+        raise NotImplementedError(f"probe step: B={B} D={D} H={H} C={Cn} {x.dtype} is outside the kernels' range "
+                                  f"({PROBE_LIMITS})")
+    assert x.is_contiguous() and tuple(w1.shape) == (H, D) and tuple(w2.shape) == (Cn, H) and b2.numel() == Cn
+    for t in (w1, gamma, beta, running_mean, running_var, w2, b2):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert gamma.numel() == beta.numel() == running_mean.numel() == running_var.numel() == H
+    assert num_batches_tracked is None or num_batches_tracked.dtype == torch.int64
+    dev = x.device
+    lib = L.load()
+    keep = dict(x=x, h=torch.empty((B, H), dtype=x.dtype, device=dev),
+                ws=torch.empty((lib.dvt_probe_workspace_bytes(B, H, Cn),), dtype=torch.uint8, device=dev))
+    d = ProbeDesc()
+    d.x, d.w1, d.gamma, d.beta, d.w2, d.b2 = (t.data_ptr() for t in (x, w1, gamma, beta, w2, b2))
+    d.running_mean, d.running_var, d.num_batches_tracked = running_mean.data_ptr(), running_var.data_ptr(), _p(num_batches_tracked)
+    d.h, d.workspace = keep["h"].data_ptr(), keep["ws"].data_ptr()
+    if training:
+        keep.update(z=torch.empty((B, H), dtype=torch.float32, device=dev),
+                    stats=torch.empty((2, H), dtype=torch.float32, device=dev))
+        d.z, d.save_mean, d.save_invstd = keep["z"].data_ptr(), keep["stats"][0].data_ptr(), keep["stats"][1].data_ptr()
+        if p > 0.0:
+            assert rng_state is not None and rng_state.dtype == torch.int64
+            keep["rng"] = rng_state
+            d.rng_state, d.rng_offset = rng_state.data_ptr(), int(rng_offset)
+    d.B, d.D, d.H, d.C, d.dtype, d.training = B, D, H, Cn, dt(x), int(training)
+    d.p, d.eps, d.momentum = (float(p) if training else 0.0), float(eps), float(momentum)
+    return d, keep
+
+
+def probe_fwd(d, keep) -> Tensor:
+    """Launch 1: Dropout -> Linear -> BatchNorm1d -> ReLU -> Dropout and the slabs' partial logits -> h [B, H]."""
+    L.check(L.load().dvt_probe_fwd(C.byref(d), _stream()), "dvt_probe_fwd")
+    return keep["h"]
+
+
+def probe_logits(d, keep) -> Tensor:
+    """Launch 2 without a target: the logits [B, C] f32 of the forward just run."""
+    out = torch.empty((d.B, d.C), dtype=torch.float32, device=keep["x"].device)
+    e = ProbeDesc.from_buffer_copy(d)
+    e.logits, e.training, e.target = out.data_ptr(), 0, None
+    L.check(L.load().dvt_probe_loss(C.byref(e), _stream()), "dvt_probe_loss")
+    return out
+
+
+def probe_loss(d, keep, target: Tensor, g_b2: Optional[Tensor] = None, *, lr: float = 0.0, accumulate: bool = False):
+    """Launch 2: sigmoid + nn.BCELoss() -> (loss 0-dim f32, prob [B, C] f32); in a training descriptor also dlogits and the
+    SGD update of the bias through its gradient buffer g_b2."""
+    _need_cuda(target, g_b2)
+    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (d.B, d.C)
+    dev = target.device
+    keep.update(target=target, prob=torch.empty((d.B, d.C), dtype=torch.float32, device=dev),
+                loss=torch.empty((1,), dtype=torch.float32, device=dev))
+    d.target, d.prob, d.loss = target.data_ptr(), keep["prob"].data_ptr(), keep["loss"].data_ptr()
+    if d.training:
+        assert g_b2 is not None and g_b2.dtype == torch.float32 and g_b2.numel() == d.C
+        keep["dlogits"] = torch.empty((d.B, d.C), dtype=torch.float32, device=dev)
+        d.dlogits, d.g_b2, d.lr, d.accumulate = keep["dlogits"].data_ptr(), g_b2.data_ptr(), float(lr), int(accumulate)
+    L.check(L.load().dvt_probe_loss(C.byref(d), _stream()), "dvt_probe_loss")
+    return keep["loss"].view(()), keep["prob"]
+
+
+def probe_bwd_step(d, keep, g_w1: Tensor, g_gamma: Tensor, g_beta: Tensor, g_w2: Tensor) -> None:
+    """Launch 3: the gradients of W1, gamma, beta, W2 into their buffers (added when the descriptor accumulates) and SGD."""
+    _need_cuda(g_w1, g_gamma, g_beta, g_w2)
+    for g, n in ((g_w1, d.H * d.D), (g_gamma, d.H), (g_beta, d.H), (g_w2, d.C * d.H)):
+        assert g.dtype == torch.float32 and g.is_contiguous() and g.numel() == n
+    d.g_w1, d.g_gamma, d.g_beta, d.g_w2 = (g.data_ptr() for g in (g_w1, g_gamma, g_beta, g_w2))
+    L.check(L.load().dvt_probe_bwd_step(C.byref(d), _stream()), "dvt_probe_bwd_step")
+
+
+def multilabel_sweep_counts(probs: Tensor, labels: Tensor, thresholds) -> Tuple[Tensor, Tensor]:
+    """TP / FP / FN per class of ``probs > t`` for every t of ``thresholds`` in one launch (dvt_multilabel_sweep_counts)
+    -> (counts int64 [T, 3, C], support int64 [C])."""
+    _need_cuda(probs, labels)
+    probs = probs.contiguous() if probs.dtype == torch.float32 else cast(probs.contiguous(), torch.float32)
+    lab = labels.contiguous()
+    if lab.dtype != torch.uint8:
+        lab = (lab != 0).to(torch.uint8)          # dtype plumbing of a label mask
+    N, Cn = probs.shape
+    if tuple(lab.shape) != (N, Cn):
+        raise ValueError(f"multilabel_sweep_counts: labels {tuple(lab.shape)} != probs {(N, Cn)}")
+    th = torch.tensor([float(t) for t in thresholds], dtype=torch.float32).to(probs.device)
+    counts = torch.empty((th.numel(), 3, Cn), dtype=torch.int64, device=probs.device)
+    support = torch.empty((Cn,), dtype=torch.int64, device=probs.device)
+    L.check(L.load().dvt_multilabel_sweep_counts(probs.data_ptr(), lab.data_ptr(), N, Cn, th.data_ptr(), th.numel(),
+                                                 counts.data_ptr(), support.data_ptr(), _stream()),
+            "dvt_multilabel_sweep_counts")
+    return counts, support

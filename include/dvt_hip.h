@@ -1092,6 +1092,72 @@ int dvt_ce_labels_bwd(const void* logits, int64_t ld, const int64_t* labels, con
 int dvt_gather_rows_ptr(const int64_t* table, int64_t rows, int parts, void* out, int64_t ldo, int64_t D, int dtype,
                         dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- the online probe of the contrastive model
+ * Additions within ABI v5: new entry points and one new descriptor, no existing layout or meaning changed.
+ * SSLOnlineEval (src/callbacks/callbacks.py:147-300) trains pl_bolts' SSLEvaluator after every training batch:
+ *   Dropout(p) -> Linear(D, H, no bias) -> BatchNorm1d(H) -> ReLU -> Dropout(p) -> Linear(H, C) -> sigmoid -> nn.BCELoss()
+ * followed by torch.optim.SGD(lr, no momentum, no decay).  One step is three launches, in this order:
+ *   dvt_probe_fwd       per slab of 16 hidden columns: z = drop(x) W1^T, BatchNorm (training: batch statistics, the running
+ *                       statistics and *num_batches_tracked moved exactly as nn.BatchNorm1d moves them; eval: the running
+ *                       statistics), ReLU, second dropout; writes h, z (training), save_mean / save_invstd (training) and
+ *                       the slab's partial logits into `workspace` (f32 [H / 16][B][C], dvt_probe_workspace_bytes).
+ *   dvt_probe_loss      sums the partials in slab order, adds the bias; prob = sigmoid (f32), loss[0] = the mean BCE with
+ *                       each log clamped at -100; training: dlogits, the bias gradient and its SGD update.  Without a
+ *                       target (training = 0 in this call's descriptor) it only writes `logits`.
+ *   dvt_probe_bwd_step  (training) per slab: the gradients of W2[:, slab] (from W2 before its update), gamma, beta and
+ *                       W1[slab, :] with the dropout masks of the forward (the first regenerated from the Philox stream, the
+ *                       second and the ReLU read from h != 0), then SGD on those parameters.
+ * Gradients live in the persistent f32 buffers g_*: overwritten, or added to when `accumulate` (a probe whose gradients
+ * are never zeroed).  The SGD update is p - lr * g with both operations rounded in fp32, g the buffer's new content.
+ * Parameters are f32 masters, rounded to `dtype` where a matrix instruction reads them; fp32 is exact fp32 arithmetic.
+ * Dropout (training, p > 0): rng_state {seed, step base} on the device as for dvt_dropout; the first mask takes the
+ * (B D + 3) / 4 Philox blocks from call offset rng_offset on, the second the (B H + 3) / 4 blocks after them.
+ * No atomics, no host synchronisation, every reduction in a fixed order: two identical calls from the same state give
+ * bitwise-equal results, and the three calls may be captured in a hipGraph (lr is a plain argument).
+ * _supported: 1 <= B <= 1024 (B = 1 refused in training, as torch does), 1 <= D <= 4096, H a multiple of 16 up to 2048,
+ * 1 <= C <= 32, dtype F32 / BF16 / F16. */
+typedef struct dvt_probe_desc {
+  const void* x;                 /* [B][D] dtype */
+  const float* target;           /* [B][C] f32 (loss) */
+  float* w1;                     /* [H][D] block_forward.2.weight */
+  float* gamma;                  /* [H] block_forward.3.weight */
+  float* beta;                   /* [H] block_forward.3.bias */
+  float* running_mean;           /* [H] (training: NULL = not tracked) */
+  float* running_var;            /* [H] */
+  int64_t* num_batches_tracked;  /* [1] or NULL */
+  float* w2;                     /* [C][H] block_forward.6.weight */
+  float* b2;                     /* [C] block_forward.6.bias */
+  float* g_w1;                   /* gradient buffers, the parameters' shapes (training) */
+  float* g_gamma;
+  float* g_beta;
+  float* g_w2;
+  float* g_b2;
+  void* h;                       /* [B][H] dtype: the second Linear's input */
+  float* z;                      /* [B][H] f32: the first Linear's output (training) */
+  float* save_mean;              /* [H] (training) */
+  float* save_invstd;            /* [H] (training) */
+  float* logits;                 /* [B][C] f32, optional: the pre-sigmoid output (target NULL: the only output) */
+  float* prob;                   /* [B][C] f32 */
+  float* loss;                   /* [1] f32 */
+  float* dlogits;                /* [B][C] f32 (training) */
+  void* workspace;               /* dvt_probe_workspace_bytes */
+  const uint64_t* rng_state;     /* {seed, step base} on the device (training, p > 0) */
+  uint64_t rng_offset;
+  int64_t B;
+  int32_t D, H, C, dtype, training, accumulate;
+  float p, eps, momentum, lr;
+} dvt_probe_desc;
+int dvt_probe_supported(int64_t B, int D, int H, int C, int dtype);
+size_t dvt_probe_workspace_bytes(int64_t B, int H, int C);
+int dvt_probe_fwd(const dvt_probe_desc* desc, dvt_stream_t stream);
+int dvt_probe_loss(const dvt_probe_desc* desc, dvt_stream_t stream);
+int dvt_probe_bwd_step(const dvt_probe_desc* desc, dvt_stream_t stream);
+/* SSLOnlineEval.on_shared_end: per class and per threshold the TP / FP / FN counts of `probs > thresholds[t]` (strict,
+ * compared in fp32) against multilabel targets, in ONE launch: counts int64 [T][3][C], support int64 [C].  probs f32 [N][C],
+ * labels u8 [N][C], thresholds f32 [T] on the device, 1 <= T <= 64.  Integer counts, fixed-order sums, no atomics. */
+int dvt_multilabel_sweep_counts(const float* probs, const unsigned char* labels, int64_t N, int C, const float* thresholds,
+                                int T, int64_t* counts, int64_t* support, dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- data-parallel gradient exchange
  * The reference is single-GPU (pl.Trainer(gpus=1), src/main.py:87); north_star partitions the clips of the global
  * batch over the 8 GPUs of a node, and the only exchange of the path is the SUM of the parameter gradients.  RCCL over
