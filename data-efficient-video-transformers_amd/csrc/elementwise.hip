@@ -1,9 +1,8 @@
 // elementwise.hip -- HBM-bound data-movement kernels of the clip path:
 // casts, residual add, patchify gather, token assembly (CLS + positional add),
-// CLS row gather, losses, AdamW.  All are streaming kernels: 16-byte accesses
+// CLS row gather, losses, dropout.  All are streaming kernels: 16-byte accesses
 // per lane, grid-stride over at most 256 CUs x 8 blocks.
 #include "common.h"
-#include <type_traits>
 
 namespace {
 
@@ -587,23 +586,120 @@ __global__ void ce_argmax_kernel(const T* __restrict__ st, const T* __restrict__
   }
 }
 
-// ------------------------------------------------------------------ AdamW
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                             float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                             float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const float step_size = lr / bc1;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gi = g[i];
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = fmaf(b1, m[i], (1.0f - b1) * gi);
-    const float vi = fmaf(b2, v[i], (1.0f - b2) * gi * gi);
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= step_size * (mi / denom);
-    p[i] = pi; m[i] = mi; v[i] = vi;
+// ---- dropout (nn.Dropout in training mode: frame_transformer.py:22,41-44; TPN.py:92,95; vit.py:23,25,43,104)
+// Counter-based Philox4x32-10: element i draws word (i & 3) of block (offset + i / 4) under the key (seed).  No mask
+// is stored: backward re-draws the same words.  state[0] = seed, state[1] = per-step base offset live on the device
+// (advanced by dvt_rng_advance once per step), so a captured hipGraph draws fresh masks on every replay.
+template <typename T>
+__global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, uint32_t threshold, float scale,
+                               const uint64_t* __restrict__ state, uint64_t call_offset) {
+  const uint64_t seed = state[0], base = state[1] + call_offset;
+  const int64_t nblk = (n + 3) >> 2;
+  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nblk; b += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t ctr = base + (uint64_t)b;
+    uint32_t r[4];
+    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int64_t i = b * 4 + e;
+      if (i < n) y[i] = from_f32<T>(r[e] >= threshold ? to_f32<T>(x[i]) * scale : 0.f);
+    }
   }
 }
 
+// The same mask around its neighbours (dvt_dropout_fused): y = residual? + keep * scale * relu?(x), or -- state == nullptr,
+// the backward of the ReLU form -- y = gate != 0 ? scale * x : 0 with the forward's OUTPUT as gate (an element the mask
+// dropped and one the ReLU zeroed both pass no gradient).
+template <typename T>
+__global__ void dropout_fused_kernel(const T* __restrict__ x, const T* __restrict__ res, const T* __restrict__ gate,
+                                     T* __restrict__ y, int64_t n, uint32_t threshold, float scale,
+                                     const uint64_t* __restrict__ state, uint64_t call_offset, int relu) {
+  const uint64_t seed = state ? state[0] : 0, base = state ? state[1] + call_offset : 0;
+  const int64_t nblk = (n + 3) >> 2;
+  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nblk; b += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t r[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    if (state) {
+      const uint64_t ctr = base + (uint64_t)b;
+      philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int64_t i = b * 4 + e;
+      if (i < n) {
+        float v = to_f32<T>(x[i]);
+        if (relu) v = fmaxf(v, 0.f);
+        bool keep = r[e] >= threshold;
+        if (gate) keep = to_f32<T>(gate[i]) != 0.f;
+        v = keep ? v * scale : 0.f;
+        if (res) v += to_f32<T>(res[i]);
+        y[i] = from_f32<T>(v);
+      }
+    }
+  }
+}
+
+__global__ void rng_advance_kernel(uint64_t* state, uint64_t delta) { state[1] += delta; }
+
+template <typename S, typename D, bool FWD>
+int patchify_dispatch(const void* x, void* out, void* dx, const void* dout, int64_t frames, int C,
+                      int H, int W, int P, hipStream_t st, const char* name) {
+  const int nh = H / P, nw = W / P;
+  const int64_t items = frames * nh * P * nw;
+  const void* pix = FWD ? x : (const void*)dx;
+  const void* vecp = FWD ? (const void*)out : dout;
+  const bool vec_ok = (W % 8 == 0) && (P % 8 == 0) && ((P * C) % 8 == 0) && dvt_aligned16(pix) &&
+                      dvt_aligned16(vecp) && ((int64_t)H * W % 8 == 0);
+  if constexpr (FWD && sizeof(D) == 2) {
+    if (vec_ok && P == 16 && C == 3) {
+      const int64_t npatches = frames * nh * nw;
+      int64_t blocks = dvt_cdiv(dvt_cdiv(npatches, 4), 4);
+      const int64_t cap = (int64_t)dvt_num_cus() * 16;
+      if (blocks > cap) blocks = cap;
+      hipLaunchKernelGGL((patchify16_fwd_kernel<S, D>), dim3((unsigned)blocks), dim3(256), 0, st, (const S*)x, (D*)out,
+                         npatches, H, W, nh, nw);
+      DVT_LAUNCH_CHECK(name);
+      return DVT_OK;
+    }
+  }
+  if (vec_ok && P == 16 && C == 3) {
+    hipLaunchKernelGGL((patchify_vec_kernel<16, 3, S, D, FWD>), dim3(grid_for(items)), dim3(kBlock),
+                       0, st, (const S*)x, (D*)out, (S*)dx, (const D*)dout, frames, H, W);
+  } else if (vec_ok && P == 8 && C == 3) {
+    hipLaunchKernelGGL((patchify_vec_kernel<8, 3, S, D, FWD>), dim3(grid_for(items)), dim3(kBlock),
+                       0, st, (const S*)x, (D*)out, (S*)dx, (const D*)dout, frames, H, W);
+  } else {
+    const int64_t total = frames * nh * nw * (int64_t)P * P * C;
+    hipLaunchKernelGGL((patchify_generic_kernel<S, D, FWD>), dim3(grid_for(total)), dim3(kBlock), 0,
+                       st, (const S*)x, (D*)out, (S*)dx, (const D*)dout, frames, C, H, W, P);
+  }
+  DVT_LAUNCH_CHECK(name);
+  return DVT_OK;
+}
+
+template <bool FWD>
+int patchify_entry(const void* pix, int pix_dtype, const void* vec, int vec_dtype, int64_t frames,
+                   int C, int H, int W, int P, dvt_stream_t stream, const char* name) {
+  DVT_REQUIRE(pix && vec, "%s: null pointer", name);
+  DVT_REQUIRE(frames >= 0 && C > 0 && H > 0 && W > 0 && P > 0, "%s: bad sizes", name);
+  DVT_REQUIRE(H % P == 0 && W % P == 0, "%s: image %dx%d not divisible by patch %d", name, H, W, P);
+  if (frames == 0) return DVT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // pixel tensor: x (fwd, const) / dx (bwd, written); vector tensor: out (fwd) / dout (bwd)
+#define DVT_PATCH_CASE(PD, S, VD, D)                                                            \
+  if (pix_dtype == PD && vec_dtype == VD)                                                       \
+    return patchify_dispatch<S, D, FWD>(FWD ? pix : nullptr, FWD ? (void*)vec : nullptr,        \
+                                        FWD ? nullptr : (void*)pix, FWD ? nullptr : vec, frames, \
+                                        C, H, W, P, st, name);
+  DVT_PATCH_CASE(DVT_F32, float, DVT_F32, float)
+  DVT_PATCH_CASE(DVT_F32, float, DVT_BF16, bf16)
+  DVT_PATCH_CASE(DVT_F32, float, DVT_F16, f16)
+  DVT_PATCH_CASE(DVT_BF16, bf16, DVT_BF16, bf16)
+  DVT_PATCH_CASE(DVT_F16, f16, DVT_F16, f16)
+  DVT_PATCH_CASE(DVT_BF16, bf16, DVT_F32, float)
+  DVT_PATCH_CASE(DVT_F16, f16, DVT_F32, float)
+#undef DVT_PATCH_CASE
+  DVT_UNSUPPORTED("%s: dtype pair (%d, %d) not supported", name, pix_dtype, vec_dtype);
+}
 }  // namespace
 
 extern "C" {
@@ -738,292 +834,6 @@ int dvt_axpby_f32(const void* src, int src_dtype, float alpha, float* dst, float
   DVT_LAUNCH_CHECK("dvt_axpby_f32");
   return DVT_OK;
 }
-
-}  // extern "C"
-
-namespace {
-__global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                 float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                 float b1, float b2, float eps, float wd,
-                                 const int64_t* __restrict__ step_dev, const uint8_t* __restrict__ skip) {
-  const float t = (float)(step_dev[0] + 1);
-  const float bc1 = 1.0f - powf(b1, t);
-  const float bc2_sqrt = sqrtf(1.0f - powf(b2, t));
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const float step_size = lr / bc1;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    if (skip && skip[i >> 6]) continue;               // parameter without a gradient this step: untouched (torch: grad None)
-    const float gi = g[i];
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = fmaf(b1, m[i], (1.0f - b1) * gi);
-    const float vi = fmaf(b2, v[i], (1.0f - b2) * gi * gi);
-    pi -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-
-__global__ void inc_step_kernel(int64_t* step_dev) { step_dev[0] += 1; }
-
-// The flat-buffer step of the training loop in ONE launch: AdamW on four elements per thread (16-byte accesses), the
-// 16-bit mirror of the updated weights that the next step's GEMMs read (M = bf16 / f16; float: no mirror), and the step
-// counter: every block reads step_dev[0] before it takes a ticket in step_dev[1], the last ticket stores the increment.
-template <typename M>
-__global__ __launch_bounds__(256) void adamw_fused_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                          float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                                          float b1, float b2, float eps, float wd, int64_t* step_dev,
-                                                          const uint8_t* __restrict__ skip, M* __restrict__ mirror) {
-  const int64_t steps = step_dev[0];
-  const float t = (float)(steps + 1);
-  const float bc1 = 1.0f - powf(b1, t);
-  const float bc2_sqrt = sqrtf(1.0f - powf(b2, t));
-  const float step_size = lr / bc1, decay = 1.0f - lr * wd;
-  const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const int64_t e = i << 2;
-    f32x4 pv = *reinterpret_cast<const f32x4*>(p + e);
-    if (!(skip && skip[e >> 6])) {                     // parameter without a gradient this step: untouched (torch: grad None)
-      const f32x4 gv = *reinterpret_cast<const f32x4*>(g + e);
-      f32x4 mv = *reinterpret_cast<const f32x4*>(m + e), vv = *reinterpret_cast<const f32x4*>(v + e);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float pi = pv[k] * decay;
-        mv[k] = fmaf(b1, mv[k], (1.0f - b1) * gv[k]);
-        vv[k] = fmaf(b2, vv[k], (1.0f - b2) * gv[k] * gv[k]);
-        pi -= step_size * (mv[k] / (sqrtf(vv[k]) / bc2_sqrt + eps));
-        pv[k] = pi;
-      }
-      *reinterpret_cast<f32x4*>(p + e) = pv;
-      *reinterpret_cast<f32x4*>(m + e) = mv;
-      *reinterpret_cast<f32x4*>(v + e) = vv;
-    }
-    if (!std::is_same<M, float>::value) {
-      typedef M m4 __attribute__((ext_vector_type(4)));
-      m4 o;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = (M)pv[k];
-      *reinterpret_cast<m4*>(mirror + e) = o;
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {       // tail of a buffer whose length is not a multiple of 4
-    const int64_t i = (n4 << 2) + threadIdx.x;
-    float pi = p[i];
-    if (!(skip && skip[i >> 6])) {
-      const float gi = g[i];
-      pi *= decay;
-      const float mi = fmaf(b1, m[i], (1.0f - b1) * gi);
-      const float vi = fmaf(b2, v[i], (1.0f - b2) * gi * gi);
-      pi -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-      p[i] = pi; m[i] = mi; v[i] = vi;
-    }
-    if (!std::is_same<M, float>::value) mirror[i] = (M)pi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    // every thread of this block has read step_dev[0]; relaxed device-scope ticket: the last block publishes the increment
-    const unsigned long long ticket = __hip_atomic_fetch_add((unsigned long long*)(step_dev + 1), 1ull, __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_AGENT);
-    if (ticket == (unsigned long long)gridDim.x - 1) {
-      step_dev[0] = steps + 1;
-      step_dev[1] = 0;
-    }
-  }
-}
-
-// ---- dropout (nn.Dropout in training mode: frame_transformer.py:22,41-44; TPN.py:92,95; vit.py:23,25,43,104)
-// Counter-based Philox4x32-10: element i draws word (i & 3) of block (offset + i / 4) under the key (seed).  No mask
-// is stored: backward re-draws the same words.  state[0] = seed, state[1] = per-step base offset live on the device
-// (advanced by dvt_rng_advance once per step), so a captured hipGraph draws fresh masks on every replay.
-template <typename T>
-__global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, uint32_t threshold, float scale,
-                               const uint64_t* __restrict__ state, uint64_t call_offset) {
-  const uint64_t seed = state[0], base = state[1] + call_offset;
-  const int64_t nblk = (n + 3) >> 2;
-  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nblk; b += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t ctr = base + (uint64_t)b;
-    uint32_t r[4];
-    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t i = b * 4 + e;
-      if (i < n) y[i] = from_f32<T>(r[e] >= threshold ? to_f32<T>(x[i]) * scale : 0.f);
-    }
-  }
-}
-
-// The same mask around its neighbours (dvt_dropout_fused): y = residual? + keep * scale * relu?(x), or -- state == nullptr,
-// the backward of the ReLU form -- y = gate != 0 ? scale * x : 0 with the forward's OUTPUT as gate (an element the mask
-// dropped and one the ReLU zeroed both pass no gradient).
-template <typename T>
-__global__ void dropout_fused_kernel(const T* __restrict__ x, const T* __restrict__ res, const T* __restrict__ gate,
-                                     T* __restrict__ y, int64_t n, uint32_t threshold, float scale,
-                                     const uint64_t* __restrict__ state, uint64_t call_offset, int relu) {
-  const uint64_t seed = state ? state[0] : 0, base = state ? state[1] + call_offset : 0;
-  const int64_t nblk = (n + 3) >> 2;
-  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nblk; b += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t r[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    if (state) {
-      const uint64_t ctr = base + (uint64_t)b;
-      philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t i = b * 4 + e;
-      if (i < n) {
-        float v = to_f32<T>(x[i]);
-        if (relu) v = fmaxf(v, 0.f);
-        bool keep = r[e] >= threshold;
-        if (gate) keep = to_f32<T>(gate[i]) != 0.f;
-        v = keep ? v * scale : 0.f;
-        if (res) v += to_f32<T>(res[i]);
-        y[i] = from_f32<T>(v);
-      }
-    }
-  }
-}
-
-__global__ void rng_advance_kernel(uint64_t* state, uint64_t delta) { state[1] += delta; }
-
-// ---- fp16 loss scaling (BASELINE configs[4]: "fp16 + loss scaling"), all state on the device so the step stays
-// hipGraph-capturable: scale[0], found_inf[0] (int32), good_steps[0] (int32), loss_grad[0] = scale * base.
-__global__ void check_finite_kernel(const float* __restrict__ g, int64_t n, int* __restrict__ found_inf) {
-  bool bad = false;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float v = g[i];
-    bad |= !(fabsf(v) <= 3.402823466e38f);          // inf or nan
-  }
-  if (bad) atomicOr(found_inf, 1);
-}
-
-__global__ void adamw_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                    float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-                                    const int64_t* __restrict__ step_dev, const float* __restrict__ scale,
-                                    const int* __restrict__ found_inf, const uint8_t* __restrict__ skip) {
-  if (found_inf[0]) return;                           // overflow: skip the whole update
-  const float inv_scale = 1.0f / scale[0];
-  const float t = (float)(step_dev[0] + 1);
-  const float bc1 = 1.0f - powf(b1, t);
-  const float bc2_sqrt = sqrtf(1.0f - powf(b2, t));
-  const float step_size = lr / bc1;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    if (skip && skip[i >> 6]) continue;
-    const float gi = g[i] * inv_scale;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = fmaf(b1, m[i], (1.0f - b1) * gi);
-    const float vi = fmaf(b2, v[i], (1.0f - b2) * gi * gi);
-    pi -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-
-// after the step: step counter, dynamic scale (torch.cuda.amp.GradScaler rule), flag reset, next loss gradient
-__global__ void loss_scale_update_kernel(int64_t* step_dev, float* scale, int* found_inf, int* good_steps,
-                                         int growth_interval, float growth, float backoff, float* loss_grad,
-                                         float base) {
-  if (found_inf[0]) {
-    scale[0] *= backoff;
-    good_steps[0] = 0;
-  } else {
-    step_dev[0] += 1;
-    if (++good_steps[0] >= growth_interval) { scale[0] *= growth; good_steps[0] = 0; }
-  }
-  found_inf[0] = 0;
-  loss_grad[0] = scale[0] * base;
-}
-
-// torch.optim.SGD (dampening 0, no nesterov): d = g + wd p; buf = mu buf + d; p -= lr buf   (buf starts at 0,
-// which reproduces torch's "first step: buf = d" rule).  mu == 0: plain p -= lr d, buf untouched.
-__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                           int64_t n, float lr, float mu, float wd, const uint8_t* __restrict__ skip) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    if (skip && skip[i >> 6]) continue;
-    const float pi = p[i];
-    float d = fmaf(wd, pi, g[i]);
-    if (mu != 0.f) {
-      d = fmaf(mu, buf[i], d);
-      buf[i] = d;
-    }
-    p[i] = pi - lr * d;
-  }
-}
-
-// torch.optim.Adagrad: d = g + wd p; sum += d^2; p -= clr d / (sqrt(sum) + eps)
-__global__ void adagrad_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sum,
-                               int64_t n, float clr, float eps, float wd, const uint8_t* __restrict__ skip) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    if (skip && skip[i >> 6]) continue;
-    const float pi = p[i];
-    const float d = fmaf(wd, pi, g[i]);
-    const float si = fmaf(d, d, sum[i]);
-    sum[i] = si;
-    p[i] = pi - clr * (d / (sqrtf(si) + eps));
-  }
-}
-
-template <typename S, typename D, bool FWD>
-int patchify_dispatch(const void* x, void* out, void* dx, const void* dout, int64_t frames, int C,
-                      int H, int W, int P, hipStream_t st, const char* name) {
-  const int nh = H / P, nw = W / P;
-  const int64_t items = frames * nh * P * nw;
-  const void* pix = FWD ? x : (const void*)dx;
-  const void* vecp = FWD ? (const void*)out : dout;
-  const bool vec_ok = (W % 8 == 0) && (P % 8 == 0) && ((P * C) % 8 == 0) && dvt_aligned16(pix) &&
-                      dvt_aligned16(vecp) && ((int64_t)H * W % 8 == 0);
-  if constexpr (FWD && sizeof(D) == 2) {
-    if (vec_ok && P == 16 && C == 3) {
-      const int64_t npatches = frames * nh * nw;
-      int64_t blocks = dvt_cdiv(dvt_cdiv(npatches, 4), 4);
-      const int64_t cap = (int64_t)dvt_num_cus() * 16;
-      if (blocks > cap) blocks = cap;
-      hipLaunchKernelGGL((patchify16_fwd_kernel<S, D>), dim3((unsigned)blocks), dim3(256), 0, st, (const S*)x, (D*)out,
-                         npatches, H, W, nh, nw);
-      DVT_LAUNCH_CHECK(name);
-      return DVT_OK;
-    }
-  }
-  if (vec_ok && P == 16 && C == 3) {
-    hipLaunchKernelGGL((patchify_vec_kernel<16, 3, S, D, FWD>), dim3(grid_for(items)), dim3(kBlock),
-                       0, st, (const S*)x, (D*)out, (S*)dx, (const D*)dout, frames, H, W);
-  } else if (vec_ok && P == 8 && C == 3) {
-    hipLaunchKernelGGL((patchify_vec_kernel<8, 3, S, D, FWD>), dim3(grid_for(items)), dim3(kBlock),
-                       0, st, (const S*)x, (D*)out, (S*)dx, (const D*)dout, frames, H, W);
-  } else {
-    const int64_t total = frames * nh * nw * (int64_t)P * P * C;
-    hipLaunchKernelGGL((patchify_generic_kernel<S, D, FWD>), dim3(grid_for(total)), dim3(kBlock), 0,
-                       st, (const S*)x, (D*)out, (S*)dx, (const D*)dout, frames, C, H, W, P);
-  }
-  DVT_LAUNCH_CHECK(name);
-  return DVT_OK;
-}
-
-template <bool FWD>
-int patchify_entry(const void* pix, int pix_dtype, const void* vec, int vec_dtype, int64_t frames,
-                   int C, int H, int W, int P, dvt_stream_t stream, const char* name) {
-  DVT_REQUIRE(pix && vec, "%s: null pointer", name);
-  DVT_REQUIRE(frames >= 0 && C > 0 && H > 0 && W > 0 && P > 0, "%s: bad sizes", name);
-  DVT_REQUIRE(H % P == 0 && W % P == 0, "%s: image %dx%d not divisible by patch %d", name, H, W, P);
-  if (frames == 0) return DVT_OK;
-  hipStream_t st = (hipStream_t)stream;
-  // pixel tensor: x (fwd, const) / dx (bwd, written); vector tensor: out (fwd) / dout (bwd)
-#define DVT_PATCH_CASE(PD, S, VD, D)                                                            \
-  if (pix_dtype == PD && vec_dtype == VD)                                                       \
-    return patchify_dispatch<S, D, FWD>(FWD ? pix : nullptr, FWD ? (void*)vec : nullptr,        \
-                                        FWD ? nullptr : (void*)pix, FWD ? nullptr : vec, frames, \
-                                        C, H, W, P, st, name);
-  DVT_PATCH_CASE(DVT_F32, float, DVT_F32, float)
-  DVT_PATCH_CASE(DVT_F32, float, DVT_BF16, bf16)
-  DVT_PATCH_CASE(DVT_F32, float, DVT_F16, f16)
-  DVT_PATCH_CASE(DVT_BF16, bf16, DVT_BF16, bf16)
-  DVT_PATCH_CASE(DVT_F16, f16, DVT_F16, f16)
-  DVT_PATCH_CASE(DVT_BF16, bf16, DVT_F32, float)
-  DVT_PATCH_CASE(DVT_F16, f16, DVT_F32, float)
-#undef DVT_PATCH_CASE
-  DVT_UNSUPPORTED("%s: dtype pair (%d, %d) not supported", name, pix_dtype, vec_dtype);
-}
-}  // namespace
-
-extern "C" {
 
 int dvt_patchify(const void* x, int x_dtype, void* out, int out_dtype, int64_t frames, int C, int H,
                  int W, int P, dvt_stream_t stream) {
@@ -1198,22 +1008,6 @@ int dvt_ce_argmax_bwd(const void* student, const void* teacher, const float* glo
   return DVT_OK;
 }
 
-int dvt_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                   float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
-                   dvt_stream_t stream) {
-  if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
-  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1,
-              "dvt_adamw_step: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, param, grad, exp_avg,
-                     exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, (float)bc1,
-                     (float)sqrt(bc2));
-  DVT_LAUNCH_CHECK("dvt_adamw_step");
-  return DVT_OK;
-}
-
 int dvt_dropout(const void* x, void* y, int64_t n, float p, const uint64_t* rng_state, uint64_t call_offset, int dtype,
                 dvt_stream_t stream) {
   if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
@@ -1248,84 +1042,6 @@ int dvt_rng_advance(uint64_t* rng_state, uint64_t delta, dvt_stream_t stream) {
   DVT_REQUIRE(rng_state, "dvt_rng_advance: null state");
   hipLaunchKernelGGL(rng_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, rng_state, delta);
   DVT_LAUNCH_CHECK("dvt_rng_advance");
-  return DVT_OK;
-}
-
-int dvt_adamw_step_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                          float beta1, float beta2, float eps, float weight_decay, int64_t* step_dev, float* scale,
-                          int32_t* found_inf, int32_t* good_steps, int growth_interval, float growth, float backoff,
-                          float* loss_grad, float loss_grad_base, const uint8_t* skip64, dvt_stream_t stream) {
-  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && step_dev && scale && found_inf && good_steps && loss_grad &&
-                  n >= 0 && growth_interval > 0 && growth >= 1.f && backoff > 0.f && backoff <= 1.f,
-              "dvt_adamw_step_scaled: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  if (n > 0) {
-    hipLaunchKernelGGL(check_finite_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, grad, n, (int*)found_inf);
-    hipLaunchKernelGGL(adamw_scaled_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, param, grad, exp_avg, exp_avg_sq, n,
-                       lr, beta1, beta2, eps, weight_decay, (const int64_t*)step_dev, (const float*)scale,
-                       (const int*)found_inf, skip64);
-  }
-  hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(1), 0, st, step_dev, scale, (int*)found_inf,
-                     (int*)good_steps, growth_interval, growth, backoff, loss_grad, loss_grad_base);
-  DVT_LAUNCH_CHECK("dvt_adamw_step_scaled");
-  return DVT_OK;
-}
-
-int dvt_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum,
-                 float weight_decay, const uint8_t* skip64, dvt_stream_t stream) {
-  if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
-  DVT_REQUIRE(param && grad && n >= 0 && (momentum == 0.f || momentum_buf), "dvt_sgd_step: bad arguments");
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, param, grad, momentum_buf,
-                     n, lr, momentum, weight_decay, skip64);
-  DVT_LAUNCH_CHECK("dvt_sgd_step");
-  return DVT_OK;
-}
-
-int dvt_adagrad_step(float* param, const float* grad, float* state_sum, int64_t n, float lr, float lr_decay,
-                     float eps, float weight_decay, int64_t step, const uint8_t* skip64, dvt_stream_t stream) {
-  if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
-  DVT_REQUIRE(param && grad && state_sum && n >= 0 && step >= 1, "dvt_adagrad_step: bad arguments");
-  const float clr = (float)((double)lr / (1.0 + (double)(step - 1) * (double)lr_decay));
-  hipLaunchKernelGGL(adagrad_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, param, grad, state_sum,
-                     n, clr, eps, weight_decay, skip64);
-  DVT_LAUNCH_CHECK("dvt_adagrad_step");
-  return DVT_OK;
-}
-
-int dvt_adamw_step_fused(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                         float beta1, float beta2, float eps, float weight_decay, int64_t* step_dev2,
-                         const uint8_t* skip64, void* mirror, int mirror_dtype, dvt_stream_t stream) {
-  if (n == 0) return DVT_OK;
-  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && step_dev2 && n >= 0, "dvt_adamw_step_fused: bad arguments");
-  DVT_REQUIRE(dvt_aligned16(param) && dvt_aligned16(grad) && dvt_aligned16(exp_avg) && dvt_aligned16(exp_avg_sq),
-              "dvt_adamw_step_fused: buffers must be 16-byte aligned");
-  DVT_REQUIRE(!mirror || (dvt_is_16bit(mirror_dtype) && ((uintptr_t)mirror & 7u) == 0),
-              "dvt_adamw_step_fused: mirror must be bf16 / f16 and 8-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(grid_for((n >> 2) + 1)), block(256);
-  if (!mirror)
-    hipLaunchKernelGGL((adamw_fused_kernel<float>), grid, block, 0, st, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
-                       beta2, eps, weight_decay, step_dev2, skip64, (float*)nullptr);
-  else if (mirror_dtype == DVT_BF16)
-    hipLaunchKernelGGL((adamw_fused_kernel<bf16>), grid, block, 0, st, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
-                       beta2, eps, weight_decay, step_dev2, skip64, (bf16*)mirror);
-  else
-    hipLaunchKernelGGL((adamw_fused_kernel<f16>), grid, block, 0, st, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
-                       beta2, eps, weight_decay, step_dev2, skip64, (f16*)mirror);
-  DVT_LAUNCH_CHECK("dvt_adamw_step_fused");
-  return DVT_OK;
-}
-
-int dvt_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                       float lr, float beta1, float beta2, float eps, float weight_decay,
-                       int64_t* step_dev, const uint8_t* skip64, dvt_stream_t stream) {
-  if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
-  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && step_dev && n >= 0, "dvt_adamw_step_dev: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(adamw_dev_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, param, grad, exp_avg,
-                     exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, (const int64_t*)step_dev, skip64);
-  hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, st, step_dev);
-  DVT_LAUNCH_CHECK("dvt_adamw_step_dev");
   return DVT_OK;
 }
 

@@ -4,14 +4,11 @@
 // The GEMMs of both stay on dvt_gemm (bias and ReLU in its epilogues, ReLU' in the data-gradient epilogue); what is here:
 //   - BatchNorm1d that READS A RECTIFIED TENSOR (Linear -> ReLU -> BatchNorm1d, contrastivemodel.py:28-30 and
 //     basicmlp.py:35), forward and backward, over S = 1 or 2 row segments ("views") that keep their own batch statistics;
-//   - torch.optim.Adam (coupled L2 decay) over a flat buffer, with the learning rate read from a device scalar;
 //   - log-softmax + NLL over integer labels (nn.CrossEntropyLoss(), basicmlp.py:38);
 //   - the gather that turns a list-of-lists expert batch into one [rows, D] input.
 //
 // Reductions run in a fixed order with no atomics: two identical calls give bitwise-equal results.
 #include "common.h"
-
-#include <type_traits>
 
 namespace {
 
@@ -134,43 +131,6 @@ __global__ __launch_bounds__(kBnThreads) void bn1d_relu_bwd_kernel(
   if (ok && wv == 0) {
     if (dgamma) dgamma[c] = accumulate ? dgamma[c] + dg : dg;
     if (dbeta) dbeta[c] = accumulate ? dbeta[c] + db : db;
-  }
-}
-
-// torch.optim.Adam (amsgrad off): g += wd p; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
-// p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps).  lr from the device; step counter and mirror as
-// adamw_fused_kernel (elementwise.hip).
-template <typename M>
-__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                       const float* __restrict__ lr_dev, float b1, float b2, float eps,
-                                                       float wd, int64_t* step_dev, const uint8_t* __restrict__ skip,
-                                                       M* __restrict__ mirror) {
-  const int64_t steps = step_dev[0];
-  const float t = (float)(steps + 1);
-  const float bc1 = 1.0f - powf(b1, t);
-  const float bc2_sqrt = sqrtf(1.0f - powf(b2, t));
-  const float step_size = lr_dev[0] / bc1;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float pi = p[i];
-    if (!(skip && skip[i >> 6])) {                     // parameter without a gradient this step: untouched (torch: grad None)
-      const float gi = fmaf(wd, pi, g[i]);
-      const float mi = fmaf(b1, m[i], (1.0f - b1) * gi);
-      const float vi = fmaf(b2, v[i], (1.0f - b2) * gi * gi);
-      pi -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-      p[i] = pi; m[i] = mi; v[i] = vi;
-    }
-    if (!std::is_same<M, float>::value) mirror[i] = (M)pi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long ticket = __hip_atomic_fetch_add((unsigned long long*)(step_dev + 1), 1ull, __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_AGENT);
-    if (ticket == (unsigned long long)gridDim.x - 1) {
-      step_dev[0] = steps + 1;
-      step_dev[1] = 0;
-    }
   }
 }
 
@@ -322,28 +282,6 @@ int dvt_bn1d_relu_bwd(const void* dy, int64_t lddy, const void* z, int64_t ldz, 
                                         ldz, gamma, save_mean, save_invstd, (T*)dz, lddz, dgamma, dbeta, accumulate, B, C,
                                         S, training));
   DVT_LAUNCH_CHECK("dvt_bn1d_relu_bwd");
-  return DVT_OK;
-}
-
-int dvt_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
-                      float beta1, float beta2, float eps, float weight_decay, int64_t* step_dev2, const uint8_t* skip64,
-                      void* mirror, int mirror_dtype, dvt_stream_t stream) {
-  DVT_REQUIRE(n >= 0, "dvt_adam_step_dev: negative size");
-  if (n == 0) return DVT_OK;
-  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && lr_dev && step_dev2, "dvt_adam_step_dev: bad arguments");
-  DVT_REQUIRE(!mirror || dvt_is_16bit(mirror_dtype), "dvt_adam_step_dev: mirror must be bf16 / f16");
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(dvt_cdiv(n, 256) < 4096 ? dvt_cdiv(n, 256) : 4096)), block(256);
-  if (!mirror)
-    hipLaunchKernelGGL((adam_dev_kernel<float>), grid, block, 0, st, param, grad, exp_avg, exp_avg_sq, n, lr_dev, beta1,
-                       beta2, eps, weight_decay, step_dev2, skip64, (float*)nullptr);
-  else if (mirror_dtype == DVT_BF16)
-    hipLaunchKernelGGL((adam_dev_kernel<bf16>), grid, block, 0, st, param, grad, exp_avg, exp_avg_sq, n, lr_dev, beta1,
-                       beta2, eps, weight_decay, step_dev2, skip64, (bf16*)mirror);
-  else
-    hipLaunchKernelGGL((adam_dev_kernel<f16>), grid, block, 0, st, param, grad, exp_avg, exp_avg_sq, n, lr_dev, beta1,
-                       beta2, eps, weight_decay, step_dev2, skip64, (f16*)mirror);
-  DVT_LAUNCH_CHECK("dvt_adam_step_dev");
   return DVT_OK;
 }
 

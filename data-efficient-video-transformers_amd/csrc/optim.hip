@@ -1,0 +1,356 @@
+// optim.hip -- every optimizer step: AdamW (host step, device step, fused flat-buffer step with mirror, loss-scaled),
+// torch.optim.Adam with coupled decay, SGD, Adagrad.  All are streaming kernels over fp32 master weights.
+//
+// The Adam update, its bias correction, the step-counter ticket and the mirror dispatch are each stated once, below;
+// the kernels differ only in their launch contract (scalar grid-stride or four elements per thread, mirror, ticket,
+// the found_inf early-out).
+#include "common.h"
+#include <type_traits>
+
+namespace {
+
+constexpr int kBlock = 256;
+
+inline int grid_for(int64_t work_items) {
+  int64_t blocks = dvt_cdiv(work_items, kBlock);
+  int64_t cap = (int64_t)dvt_num_cus() * 8;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  return (int)blocks;
+}
+
+// 1 - b1^t and sqrt(1 - b2^t).  Two ways to fill it that round differently and stay apart: dvt_adamw_step computes the
+// pair from its host step in double, every device-counter kernel with bias_corr_dev in float.
+struct BiasCorr {
+  float bc1, bc2_sqrt;
+};
+
+__device__ __forceinline__ BiasCorr bias_corr_dev(float b1, float b2, int64_t steps_taken) {
+  const float t = (float)(steps_taken + 1);
+  return {1.0f - powf(b1, t), sqrtf(1.0f - powf(b2, t))};
+}
+
+struct AdamCoef {
+  float b1, b2, eps, wd, step_size, decay, bc2_sqrt;
+};
+
+__device__ __forceinline__ AdamCoef adam_coef(float lr, float b1, float b2, float eps, float wd, BiasCorr bc) {
+  return {b1, b2, eps, wd, lr / bc.bc1, 1.0f - lr * wd, bc.bc2_sqrt};
+}
+
+// One element of Adam: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// with the weight decay either decoupled (AdamW: p *= 1 - lr wd first) or coupled (torch.optim.Adam: g += wd p first).
+template <bool kCoupled>
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, const AdamCoef& c) {
+  if (kCoupled) g = fmaf(c.wd, p, g);
+  else p *= c.decay;
+  m = fmaf(c.b1, m, (1.0f - c.b1) * g);
+  v = fmaf(c.b2, v, (1.0f - c.b2) * g * g);
+  p -= c.step_size * (m / (sqrtf(v) / c.bc2_sqrt + c.eps));
+}
+
+// The step counter of the one-launch steps, step_dev = int64[2]: steps taken, launch ticket.  Every block reads
+// step_dev[0] (`steps`) before it comes here; relaxed device-scope ticket: the last block publishes the increment.
+__device__ __forceinline__ void publish_step(int64_t* step_dev, int64_t steps) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long ticket = __hip_atomic_fetch_add((unsigned long long*)(step_dev + 1), 1ull, __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_AGENT);
+    if (ticket == (unsigned long long)gridDim.x - 1) {
+      step_dev[0] = steps + 1;
+      step_dev[1] = 0;
+    }
+  }
+}
+
+// KERNEL<M>(..., M* mirror) for the 16-bit mirror of the updated weights: M = float and a null pointer for none.
+#define DVT_LAUNCH_MIRRORED(KERNEL, mirror, mirror_dtype, grid, block, st, ...)                            \
+  do {                                                                                                     \
+    if (!(mirror))                                                                                         \
+      hipLaunchKernelGGL((KERNEL<float>), grid, block, 0, st, __VA_ARGS__, (float*)nullptr);               \
+    else if ((mirror_dtype) == DVT_BF16)                                                                   \
+      hipLaunchKernelGGL((KERNEL<bf16>), grid, block, 0, st, __VA_ARGS__, (bf16*)(mirror));                \
+    else                                                                                                   \
+      hipLaunchKernelGGL((KERNEL<f16>), grid, block, 0, st, __VA_ARGS__, (f16*)(mirror));                  \
+  } while (0)
+
+// ------------------------------------------------------------------ AdamW
+__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                             float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
+                             float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
+  const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, BiasCorr{bc1, bc2_sqrt});
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_update<false>(pi, g[i], mi, vi, c);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+  }
+}
+
+__global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                 float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
+                                 float b1, float b2, float eps, float wd,
+                                 const int64_t* __restrict__ step_dev, const uint8_t* __restrict__ skip) {
+  const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bias_corr_dev(b1, b2, step_dev[0]));
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    if (skip && skip[i >> 6]) continue;               // parameter without a gradient this step: untouched (torch: grad None)
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_update<false>(pi, g[i], mi, vi, c);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+  }
+}
+
+__global__ void inc_step_kernel(int64_t* step_dev) { step_dev[0] += 1; }
+
+// The flat-buffer step of the training loop in ONE launch: AdamW on four elements per thread (16-byte accesses), the
+// 16-bit mirror of the updated weights that the next step's GEMMs read (M = bf16 / f16; float: no mirror), and the step
+// counter (publish_step).
+template <typename M>
+__global__ __launch_bounds__(256) void adamw_fused_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
+                                                          float b1, float b2, float eps, float wd, int64_t* step_dev,
+                                                          const uint8_t* __restrict__ skip, M* __restrict__ mirror) {
+  const int64_t steps = step_dev[0];
+  const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bias_corr_dev(b1, b2, steps));
+  const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const int64_t e = i << 2;
+    f32x4 pv = *reinterpret_cast<const f32x4*>(p + e);
+    if (!(skip && skip[e >> 6])) {                     // parameter without a gradient this step: untouched (torch: grad None)
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(g + e);
+      f32x4 mv = *reinterpret_cast<const f32x4*>(m + e), vv = *reinterpret_cast<const f32x4*>(v + e);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float pi = pv[k], mi = mv[k], vi = vv[k];
+        adam_update<false>(pi, gv[k], mi, vi, c);
+        pv[k] = pi; mv[k] = mi; vv[k] = vi;
+      }
+      *reinterpret_cast<f32x4*>(p + e) = pv;
+      *reinterpret_cast<f32x4*>(m + e) = mv;
+      *reinterpret_cast<f32x4*>(v + e) = vv;
+    }
+    if (!std::is_same<M, float>::value) {
+      typedef M m4 __attribute__((ext_vector_type(4)));
+      m4 o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = (M)pv[k];
+      *reinterpret_cast<m4*>(mirror + e) = o;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {       // tail of a buffer whose length is not a multiple of 4
+    const int64_t i = (n4 << 2) + threadIdx.x;
+    float pi = p[i];
+    if (!(skip && skip[i >> 6])) {
+      float mi = m[i], vi = v[i];
+      adam_update<false>(pi, g[i], mi, vi, c);
+      p[i] = pi; m[i] = mi; v[i] = vi;
+    }
+    if (!std::is_same<M, float>::value) mirror[i] = (M)pi;
+  }
+  publish_step(step_dev, steps);
+}
+
+// torch.optim.Adam (amsgrad off, coupled decay) over a flat buffer, one launch: lr from the device; step counter and
+// mirror as adamw_fused_kernel.
+template <typename M>
+__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                       const float* __restrict__ lr_dev, float b1, float b2, float eps,
+                                                       float wd, int64_t* step_dev, const uint8_t* __restrict__ skip,
+                                                       M* __restrict__ mirror) {
+  const int64_t steps = step_dev[0];
+  const BiasCorr bc = bias_corr_dev(b1, b2, steps);   // the counter is read before the rate
+  const AdamCoef c = adam_coef(lr_dev[0], b1, b2, eps, wd, bc);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float pi = p[i];
+    if (!(skip && skip[i >> 6])) {                     // parameter without a gradient this step: untouched (torch: grad None)
+      float mi = m[i], vi = v[i];
+      adam_update<true>(pi, g[i], mi, vi, c);
+      p[i] = pi; m[i] = mi; v[i] = vi;
+    }
+    if (!std::is_same<M, float>::value) mirror[i] = (M)pi;
+  }
+  publish_step(step_dev, steps);
+}
+
+// ---- fp16 loss scaling (BASELINE configs[4]: "fp16 + loss scaling"), all state on the device so the step stays
+// hipGraph-capturable: scale[0], found_inf[0] (int32), good_steps[0] (int32), loss_grad[0] = scale * base.
+__global__ void check_finite_kernel(const float* __restrict__ g, int64_t n, int* __restrict__ found_inf) {
+  bool bad = false;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float v = g[i];
+    bad |= !(fabsf(v) <= 3.402823466e38f);          // inf or nan
+  }
+  if (bad) atomicOr(found_inf, 1);
+}
+
+__global__ void adamw_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                    float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                                    const int64_t* __restrict__ step_dev, const float* __restrict__ scale,
+                                    const int* __restrict__ found_inf, const uint8_t* __restrict__ skip) {
+  if (found_inf[0]) return;                           // overflow: skip the whole update
+  const float inv_scale = 1.0f / scale[0];
+  const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bias_corr_dev(b1, b2, step_dev[0]));
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if (skip && skip[i >> 6]) continue;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_update<false>(pi, g[i] * inv_scale, mi, vi, c);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+  }
+}
+
+// after the step: step counter, dynamic scale (torch.cuda.amp.GradScaler rule), flag reset, next loss gradient
+__global__ void loss_scale_update_kernel(int64_t* step_dev, float* scale, int* found_inf, int* good_steps,
+                                         int growth_interval, float growth, float backoff, float* loss_grad,
+                                         float base) {
+  if (found_inf[0]) {
+    scale[0] *= backoff;
+    good_steps[0] = 0;
+  } else {
+    step_dev[0] += 1;
+    if (++good_steps[0] >= growth_interval) { scale[0] *= growth; good_steps[0] = 0; }
+  }
+  found_inf[0] = 0;
+  loss_grad[0] = scale[0] * base;
+}
+
+// torch.optim.SGD (dampening 0, no nesterov): d = g + wd p; buf = mu buf + d; p -= lr buf   (buf starts at 0,
+// which reproduces torch's "first step: buf = d" rule).  mu == 0: plain p -= lr d, buf untouched.
+__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                           int64_t n, float lr, float mu, float wd, const uint8_t* __restrict__ skip) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    if (skip && skip[i >> 6]) continue;
+    const float pi = p[i];
+    float d = fmaf(wd, pi, g[i]);
+    if (mu != 0.f) {
+      d = fmaf(mu, buf[i], d);
+      buf[i] = d;
+    }
+    p[i] = pi - lr * d;
+  }
+}
+
+// torch.optim.Adagrad: d = g + wd p; sum += d^2; p -= clr d / (sqrt(sum) + eps)
+__global__ void adagrad_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sum,
+                               int64_t n, float clr, float eps, float wd, const uint8_t* __restrict__ skip) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    if (skip && skip[i >> 6]) continue;
+    const float pi = p[i];
+    const float d = fmaf(wd, pi, g[i]);
+    const float si = fmaf(d, d, sum[i]);
+    sum[i] = si;
+    p[i] = pi - clr * (d / (sqrtf(si) + eps));
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dvt_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                   float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                   dvt_stream_t stream) {
+  if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
+  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1,
+              "dvt_adamw_step: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, param, grad, exp_avg,
+                     exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, (float)bc1,
+                     (float)sqrt(bc2));
+  DVT_LAUNCH_CHECK("dvt_adamw_step");
+  return DVT_OK;
+}
+
+int dvt_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                       float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int64_t* step_dev, const uint8_t* skip64, dvt_stream_t stream) {
+  if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
+  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && step_dev && n >= 0, "dvt_adamw_step_dev: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(adamw_dev_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, param, grad, exp_avg,
+                     exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, (const int64_t*)step_dev, skip64);
+  hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, st, step_dev);
+  DVT_LAUNCH_CHECK("dvt_adamw_step_dev");
+  return DVT_OK;
+}
+
+int dvt_adamw_step_fused(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, int64_t* step_dev2,
+                         const uint8_t* skip64, void* mirror, int mirror_dtype, dvt_stream_t stream) {
+  if (n == 0) return DVT_OK;
+  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && step_dev2 && n >= 0, "dvt_adamw_step_fused: bad arguments");
+  DVT_REQUIRE(dvt_aligned16(param) && dvt_aligned16(grad) && dvt_aligned16(exp_avg) && dvt_aligned16(exp_avg_sq),
+              "dvt_adamw_step_fused: buffers must be 16-byte aligned");
+  DVT_REQUIRE(!mirror || (dvt_is_16bit(mirror_dtype) && ((uintptr_t)mirror & 7u) == 0),
+              "dvt_adamw_step_fused: mirror must be bf16 / f16 and 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(grid_for((n >> 2) + 1)), block(256);
+  DVT_LAUNCH_MIRRORED(adamw_fused_kernel, mirror, mirror_dtype, grid, block, st, param, grad, exp_avg, exp_avg_sq, n, lr,
+                      beta1, beta2, eps, weight_decay, step_dev2, skip64);
+  DVT_LAUNCH_CHECK("dvt_adamw_step_fused");
+  return DVT_OK;
+}
+
+int dvt_adamw_step_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, int64_t* step_dev, float* scale,
+                          int32_t* found_inf, int32_t* good_steps, int growth_interval, float growth, float backoff,
+                          float* loss_grad, float loss_grad_base, const uint8_t* skip64, dvt_stream_t stream) {
+  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && step_dev && scale && found_inf && good_steps && loss_grad &&
+                  n >= 0 && growth_interval > 0 && growth >= 1.f && backoff > 0.f && backoff <= 1.f,
+              "dvt_adamw_step_scaled: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (n > 0) {
+    hipLaunchKernelGGL(check_finite_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, grad, n, (int*)found_inf);
+    hipLaunchKernelGGL(adamw_scaled_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, param, grad, exp_avg, exp_avg_sq, n,
+                       lr, beta1, beta2, eps, weight_decay, (const int64_t*)step_dev, (const float*)scale,
+                       (const int*)found_inf, skip64);
+  }
+  hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(1), 0, st, step_dev, scale, (int*)found_inf,
+                     (int*)good_steps, growth_interval, growth, backoff, loss_grad, loss_grad_base);
+  DVT_LAUNCH_CHECK("dvt_adamw_step_scaled");
+  return DVT_OK;
+}
+
+int dvt_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
+                      float beta1, float beta2, float eps, float weight_decay, int64_t* step_dev2, const uint8_t* skip64,
+                      void* mirror, int mirror_dtype, dvt_stream_t stream) {
+  DVT_REQUIRE(n >= 0, "dvt_adam_step_dev: negative size");
+  if (n == 0) return DVT_OK;
+  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && lr_dev && step_dev2, "dvt_adam_step_dev: bad arguments");
+  DVT_REQUIRE(!mirror || dvt_is_16bit(mirror_dtype), "dvt_adam_step_dev: mirror must be bf16 / f16");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)(dvt_cdiv(n, 256) < 4096 ? dvt_cdiv(n, 256) : 4096)), block(256);
+  DVT_LAUNCH_MIRRORED(adam_dev_kernel, mirror, mirror_dtype, grid, block, st, param, grad, exp_avg, exp_avg_sq, n, lr_dev,
+                      beta1, beta2, eps, weight_decay, step_dev2, skip64);
+  DVT_LAUNCH_CHECK("dvt_adam_step_dev");
+  return DVT_OK;
+}
+
+int dvt_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum,
+                 float weight_decay, const uint8_t* skip64, dvt_stream_t stream) {
+  if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
+  DVT_REQUIRE(param && grad && n >= 0 && (momentum == 0.f || momentum_buf), "dvt_sgd_step: bad arguments");
+  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, param, grad, momentum_buf,
+                     n, lr, momentum, weight_decay, skip64);
+  DVT_LAUNCH_CHECK("dvt_sgd_step");
+  return DVT_OK;
+}
+
+int dvt_adagrad_step(float* param, const float* grad, float* state_sum, int64_t n, float lr, float lr_decay,
+                     float eps, float weight_decay, int64_t step, const uint8_t* skip64, dvt_stream_t stream) {
+  if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
+  DVT_REQUIRE(param && grad && state_sum && n >= 0 && step >= 1, "dvt_adagrad_step: bad arguments");
+  const float clr = (float)((double)lr / (1.0 + (double)(step - 1) * (double)lr_decay));
+  hipLaunchKernelGGL(adagrad_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, param, grad, state_sum,
+                     n, clr, eps, weight_decay, skip64);
+  DVT_LAUNCH_CHECK("dvt_adagrad_step");
+  return DVT_OK;
+}
+
+}  // extern "C"

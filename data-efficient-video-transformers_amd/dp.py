@@ -277,7 +277,13 @@ class FlatParameters:
         self._packed_valid = False
 
     # ------------------------------------------------------------------ compute copy
-    def _after_step(self) -> None:
+    def _after_step(self, mirror_written: bool) -> None:
+        """The tail of every optimizer step.  ``mirror_written``: the step's kernel wrote the 16-bit copy itself;
+        otherwise it is cast from the new masters here."""
+        if not mirror_written:
+            self.sync_compute_copy()
+        elif self.compute is not None:
+            self.compute_valid = True
         from . import functional as F       # dropout generator: move past this step's sites (device-side add)
         F.next_step()
         self._packed_valid = False          # the packed convolution weights are stale from here on
@@ -471,18 +477,14 @@ class FlatParameters:
                                    self.found_inf, self.good_steps, self.loss_grad, lr=lr, beta1=betas[0],
                                    beta2=betas[1], eps=eps, weight_decay=weight_decay, loss_grad_base=self.loss_scale,
                                    skip=self.skip_mask, **self.scaler)
-            self.sync_compute_copy()
-            self._after_step()
+            self._after_step(mirror_written=False)
             return
         # one launch: the update, the 16-bit mirror of the new weights, the step counter (on the device, so that the launch
         # can be captured in a hipGraph)
         ops.adamw_step_fused_(self.data, self.grad, self.exp_avg, self.exp_avg_sq, self.step_dev, lr=lr,
                               beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay, skip=self.skip_mask,
                               mirror=self.compute)
-        if self.compute is not None:
-            self.compute_valid = True
-        self._packed_valid = False
-        self._after_step()
+        self._after_step(mirror_written=True)
 
     def adam_step(self, lr, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
         """torch.optim.Adam semantics (coupled L2 decay: contrastivemodel.py:64) in one launch: the update, the 16-bit
@@ -501,10 +503,7 @@ class FlatParameters:
         self.step_count += 1
         ops.adam_step_dev_(self.data, self.grad, self.exp_avg, self.exp_avg_sq, self.step_dev, lr, beta1=betas[0],
                            beta2=betas[1], eps=eps, weight_decay=weight_decay, skip=self.skip_mask, mirror=self.compute)
-        if self.compute is not None:
-            self.compute_valid = True
-        self._packed_valid = False
-        self._after_step()
+        self._after_step(mirror_written=True)
 
     def sgd_step(self, lr: float, momentum: float = 0.0, weight_decay: float = 0.0) -> None:
         """torch.optim.SGD semantics (frame_transformer.py:124-126) in one launch over the flat buffers."""
@@ -513,8 +512,7 @@ class FlatParameters:
         self.step_count += 1
         ops.sgd_step_(self.data, self.grad, getattr(self, "momentum_buf", None), lr=lr, momentum=momentum,
                       weight_decay=weight_decay, skip=self.skip_mask)
-        self.sync_compute_copy()
-        self._after_step()
+        self._after_step(mirror_written=False)
 
     def adagrad_step(self, lr: float, weight_decay: float = 0.0, lr_decay: float = 0.0, eps: float = 1e-10) -> None:
         """torch.optim.Adagrad semantics (frame_transformer.py:130-132) in one launch over the flat buffers (the step count
@@ -524,8 +522,7 @@ class FlatParameters:
         self.step_count += 1
         ops.adagrad_step_(self.data, self.grad, self.state_sum, lr=lr, lr_decay=lr_decay, eps=eps,
                           weight_decay=weight_decay, step=self.step_count, skip=self.skip_mask)
-        self.sync_compute_copy()
-        self._after_step()
+        self._after_step(mirror_written=False)
 
     def init_optimizer_state(self) -> None:
         self.exp_avg = torch.zeros_like(self.data)

@@ -955,7 +955,7 @@ def heads_contract_outer(v: Tensor, gamma: Tensor, W: Tensor, a: Tensor, dW: Ten
     return out
 
 
-# ------------------------------------------------------------------ losses / optimizer
+# ------------------------------------------------------------------ losses
 def bce_logits_fwd(z: Tensor, target: Tensor) -> Tensor:
     _need_cuda(z, target)
     assert z.is_contiguous() and target.is_contiguous() and target.dtype == torch.float32
@@ -1064,16 +1064,6 @@ def ce_argmax_bwd(student: Tensor, teacher: Tensor, gloss: Tensor) -> Tensor:
     L.check(L.load().dvt_ce_argmax_bwd(student.data_ptr(), teacher.data_ptr(), gloss.data_ptr(), ds.data_ptr(), rows,
                                        Cn, dt(student), _stream()), "dvt_ce_argmax_bwd")
     return ds
-
-
-def adamw_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, *, lr: float, beta1: float,
-                beta2: float, eps: float, weight_decay: float, step: int) -> None:
-    _need_cuda(param, grad, exp_avg, exp_avg_sq)
-    for t in (param, grad, exp_avg, exp_avg_sq):
-        assert t.dtype == torch.float32 and t.is_contiguous()
-    L.check(L.load().dvt_adamw_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
-                                    param.numel(), lr, beta1, beta2, eps, weight_decay, step, _stream()),
-            "dvt_adamw_step")
 
 
 def frames_preprocess(frames: Tensor, resize: int, crop: int, mean, std, out_dtype: torch.dtype = torch.bfloat16) -> Tensor:
@@ -1222,21 +1212,6 @@ def contrastive_bwd(sim: Tensor, row_lse: Tensor, temperature: float, gloss: Ten
     return dsim
 
 
-def adamw_step_scaled_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step_dev: Tensor, scale: Tensor,
-                       found_inf: Tensor, good_steps: Tensor, loss_grad: Tensor, *, lr: float, beta1: float, beta2: float,
-                       eps: float, weight_decay: float, growth_interval: int, growth: float, backoff: float,
-                       loss_grad_base: float, skip: Optional[Tensor] = None) -> None:
-    """AdamW under dynamic loss scaling, all scaler state on the device (hipGraph-capturable)."""
-    _need_cuda(param, grad, exp_avg, exp_avg_sq, step_dev, scale, found_inf, good_steps, loss_grad)
-    assert found_inf.dtype == torch.int32 and good_steps.dtype == torch.int32 and step_dev.dtype == torch.int64
-    L.check(L.load().dvt_adamw_step_scaled(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
-                                           param.numel(), lr, beta1, beta2, eps, weight_decay, step_dev.data_ptr(),
-                                           scale.data_ptr(), found_inf.data_ptr(), good_steps.data_ptr(), growth_interval,
-                                           growth, backoff, loss_grad.data_ptr(), loss_grad_base, _skip(skip, param),
-                                           _stream()),
-            "dvt_adamw_step_scaled")
-
-
 def device_delay(microseconds: int) -> None:
     """Keep the current stream busy for a while (measurement aid, see dvt_device_delay)."""
     L.check(L.load().dvt_device_delay(int(microseconds), _stream()), "dvt_device_delay")
@@ -1271,6 +1246,16 @@ def rng_advance_(rng_state: Tensor, delta: int) -> None:
     L.check(L.load().dvt_rng_advance(rng_state.data_ptr(), delta, _stream()), "dvt_rng_advance")
 
 
+# ------------------------------------------------------------------ optimizer steps (csrc/optim.hip)
+def _flat_f32(param: Tensor, grad: Tensor, *state: Optional[Tensor]):
+    """What every optimizer step asks of ``param``, ``grad`` and the state tensors it is given: on the device, fp32,
+    contiguous, one size.  Returns the leading arguments of its entry point: their pointers, then the element count."""
+    _need_cuda(param, grad, *state)
+    for t in (param, grad, *state):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == param.numel())
+    return (*map(_p, (param, grad, *state)), param.numel())
+
+
 def _skip(skip: Optional[Tensor], param: Tensor):
     """Pointer of the optional 64-element-block skip mask of the flat-buffer optimizer steps."""
     if skip is None:
@@ -1280,50 +1265,77 @@ def _skip(skip: Optional[Tensor], param: Tensor):
     return skip.data_ptr()
 
 
-def sgd_step_(param: Tensor, grad: Tensor, momentum_buf: Optional[Tensor], *, lr: float, momentum: float,
-              weight_decay: float, skip: Optional[Tensor] = None) -> None:
-    _need_cuda(param)
-    assert param.dtype == grad.dtype == torch.float32 and param.is_contiguous() and grad.is_contiguous()
-    L.check(L.load().dvt_sgd_step(param.data_ptr(), grad.data_ptr(), _p(momentum_buf), param.numel(), lr, momentum,
-                                  weight_decay, _skip(skip, param), _stream()), "dvt_sgd_step")
+def _mirror(mirror: Optional[Tensor], param: Tensor):
+    """(pointer, dtype code) of the optional 16-bit mirror that a one-launch step writes the updated weights into."""
+    if mirror is None:
+        return None, 0
+    _need_cuda(mirror)
+    assert mirror.numel() == param.numel() and mirror.is_contiguous() and mirror.dtype in (torch.bfloat16, torch.float16)
+    return mirror.data_ptr(), _DT[mirror.dtype]
 
 
-def adagrad_step_(param: Tensor, grad: Tensor, state_sum: Tensor, *, lr: float, lr_decay: float, eps: float,
-                  weight_decay: float, step: int, skip: Optional[Tensor] = None) -> None:
-    _need_cuda(param)
-    assert param.dtype == grad.dtype == torch.float32 and param.is_contiguous() and grad.is_contiguous()
-    L.check(L.load().dvt_adagrad_step(param.data_ptr(), grad.data_ptr(), state_sum.data_ptr(), param.numel(), lr,
-                                      lr_decay, eps, weight_decay, step, _skip(skip, param), _stream()), "dvt_adagrad_step")
+def adamw_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, *, lr: float, beta1: float,
+                beta2: float, eps: float, weight_decay: float, step: int) -> None:
+    L.check(L.load().dvt_adamw_step(*_flat_f32(param, grad, exp_avg, exp_avg_sq), lr, beta1, beta2, eps, weight_decay,
+                                    step, _stream()), "dvt_adamw_step")
 
 
 def adamw_step_dev_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step_dev: Tensor, *,
                     lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
                     skip: Optional[Tensor] = None) -> None:
     """AdamW with the step counter on the device (hipGraph-capturable)."""
-    _need_cuda(param, grad, exp_avg, exp_avg_sq, step_dev)
-    for t in (param, grad, exp_avg, exp_avg_sq):
-        assert t.dtype == torch.float32 and t.is_contiguous()
+    _need_cuda(step_dev)
     assert step_dev.dtype == torch.int64 and step_dev.numel() == 1
-    L.check(L.load().dvt_adamw_step_dev(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(),
-                                        exp_avg_sq.data_ptr(), param.numel(), lr, beta1, beta2, eps,
-                                        weight_decay, step_dev.data_ptr(), _skip(skip, param), _stream()),
-            "dvt_adamw_step_dev")
+    L.check(L.load().dvt_adamw_step_dev(*_flat_f32(param, grad, exp_avg, exp_avg_sq), lr, beta1, beta2, eps, weight_decay,
+                                        step_dev.data_ptr(), _skip(skip, param), _stream()), "dvt_adamw_step_dev")
 
 
 def adamw_step_fused_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step_dev2: Tensor, *,
                       lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
                       skip: Optional[Tensor] = None, mirror: Optional[Tensor] = None) -> None:
     """AdamW + the 16-bit weight mirror + the device step counter (int64[2]: steps, ticket) in one launch."""
-    _need_cuda(param, grad, exp_avg, exp_avg_sq, step_dev2, mirror)
-    for t in (param, grad, exp_avg, exp_avg_sq):
-        assert t.dtype == torch.float32 and t.is_contiguous()
+    _need_cuda(step_dev2)
     assert step_dev2.dtype == torch.int64 and step_dev2.numel() == 2
-    if mirror is not None:
-        assert mirror.numel() == param.numel() and mirror.is_contiguous() and mirror.dtype in (torch.bfloat16, torch.float16)
-    L.check(L.load().dvt_adamw_step_fused(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
-                                          param.numel(), lr, beta1, beta2, eps, weight_decay, step_dev2.data_ptr(),
-                                          _skip(skip, param), _p(mirror), _DT[mirror.dtype] if mirror is not None else 0,
-                                          _stream()), "dvt_adamw_step_fused")
+    L.check(L.load().dvt_adamw_step_fused(*_flat_f32(param, grad, exp_avg, exp_avg_sq), lr, beta1, beta2, eps, weight_decay,
+                                          step_dev2.data_ptr(), _skip(skip, param), *_mirror(mirror, param), _stream()),
+            "dvt_adamw_step_fused")
+
+
+def adamw_step_scaled_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step_dev: Tensor, scale: Tensor,
+                       found_inf: Tensor, good_steps: Tensor, loss_grad: Tensor, *, lr: float, beta1: float, beta2: float,
+                       eps: float, weight_decay: float, growth_interval: int, growth: float, backoff: float,
+                       loss_grad_base: float, skip: Optional[Tensor] = None) -> None:
+    """AdamW under dynamic loss scaling, all scaler state on the device (hipGraph-capturable)."""
+    _need_cuda(step_dev, scale, found_inf, good_steps, loss_grad)
+    assert found_inf.dtype == torch.int32 and good_steps.dtype == torch.int32 and step_dev.dtype == torch.int64
+    L.check(L.load().dvt_adamw_step_scaled(*_flat_f32(param, grad, exp_avg, exp_avg_sq), lr, beta1, beta2, eps, weight_decay,
+                                           step_dev.data_ptr(), scale.data_ptr(), found_inf.data_ptr(), good_steps.data_ptr(),
+                                           growth_interval, growth, backoff, loss_grad.data_ptr(), loss_grad_base,
+                                           _skip(skip, param), _stream()), "dvt_adamw_step_scaled")
+
+
+def adam_step_dev_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step_dev2: Tensor, lr_dev: Tensor, *,
+                   beta1: float, beta2: float, eps: float, weight_decay: float, skip: Optional[Tensor] = None,
+                   mirror: Optional[Tensor] = None) -> None:
+    """torch.optim.Adam (coupled L2 decay) + optional 16-bit mirror + device step counter (int64[2]) in one launch; the
+    learning rate is read from the device scalar ``lr_dev`` (f32)."""
+    _need_cuda(step_dev2, lr_dev)
+    assert step_dev2.dtype == torch.int64 and step_dev2.numel() == 2 and lr_dev.dtype == torch.float32
+    L.check(L.load().dvt_adam_step_dev(*_flat_f32(param, grad, exp_avg, exp_avg_sq), lr_dev.data_ptr(), beta1, beta2, eps,
+                                       weight_decay, step_dev2.data_ptr(), _skip(skip, param), *_mirror(mirror, param),
+                                       _stream()), "dvt_adam_step_dev")
+
+
+def sgd_step_(param: Tensor, grad: Tensor, momentum_buf: Optional[Tensor], *, lr: float, momentum: float,
+              weight_decay: float, skip: Optional[Tensor] = None) -> None:
+    L.check(L.load().dvt_sgd_step(*_flat_f32(param, grad, momentum_buf), lr, momentum, weight_decay, _skip(skip, param),
+                                  _stream()), "dvt_sgd_step")
+
+
+def adagrad_step_(param: Tensor, grad: Tensor, state_sum: Tensor, *, lr: float, lr_decay: float, eps: float,
+                  weight_decay: float, step: int, skip: Optional[Tensor] = None) -> None:
+    L.check(L.load().dvt_adagrad_step(*_flat_f32(param, grad, state_sum), lr, lr_decay, eps, weight_decay, step,
+                                      _skip(skip, param), _stream()), "dvt_adagrad_step")
 
 
 # ------------------------------------------------------------------ per-frame CNN encoder (csrc/conv.hip)
@@ -2281,23 +2293,6 @@ def bn1d_relu_bwd(dy: Tensor, z: Tensor, gamma: Tensor, mean: Tensor, invstd: Te
                                        invstd.data_ptr(), dz.data_ptr(), Cc, _p(dgamma), _p(dbeta), int(accumulate),
                                        R // segments, Cc, segments, int(training), dt(z), _stream()), "dvt_bn1d_relu_bwd")
     return dz
-
-
-def adam_step_dev_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step_dev2: Tensor, lr_dev: Tensor, *,
-                   beta1: float, beta2: float, eps: float, weight_decay: float, skip: Optional[Tensor] = None,
-                   mirror: Optional[Tensor] = None) -> None:
-    """torch.optim.Adam (coupled L2 decay) + optional 16-bit mirror + device step counter (int64[2]) in one launch; the
-    learning rate is read from the device scalar ``lr_dev`` (f32)."""
-    _need_cuda(param, grad, exp_avg, exp_avg_sq, step_dev2, lr_dev, mirror)
-    for t in (param, grad, exp_avg, exp_avg_sq):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == param.numel()
-    assert step_dev2.dtype == torch.int64 and step_dev2.numel() == 2 and lr_dev.dtype == torch.float32
-    if mirror is not None:
-        assert mirror.numel() == param.numel() and mirror.is_contiguous() and mirror.dtype in (torch.bfloat16, torch.float16)
-    L.check(L.load().dvt_adam_step_dev(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
-                                       param.numel(), lr_dev.data_ptr(), beta1, beta2, eps, weight_decay,
-                                       step_dev2.data_ptr(), _skip(skip, param), _p(mirror),
-                                       _DT[mirror.dtype] if mirror is not None else 0, _stream()), "dvt_adam_step_dev")
 
 
 CE_IGNORE_INDEX = -100

@@ -26,16 +26,21 @@ def _grad32(p):
     return g
 
 
+def _zeros_like(p):
+    return torch.zeros_like(p, memory_format=torch.contiguous_format)
+
+
 class _Base(torch.optim.Optimizer):
+    """The one ``step()``: closure, groups, parameters with a gradient.  A subclass supplies ``_init_state`` (create what is
+    missing from a parameter's state) and ``_update`` (its one kernel call)."""
+
     def _invalidate(self, p):
         sink = getattr(p, "_dvt_sink", None)
         if sink is not None:                      # parameters were updated behind a FlatParameters mirror
             sink.owner.invalidate_compute_copy()
 
-
-class AdamW(_Base):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def _begin_step(self):
+        pass
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -43,22 +48,33 @@ class AdamW(_Base):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for grp in self.param_groups:
+        self._begin_step()
+        for i, grp in enumerate(self.param_groups):
             for p in grp["params"]:
                 g = _grad32(p)
                 if g is None:
                     continue
                 st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["step"] = int(st["step"]) + 1
-                ops.adamw_step_(p.data, g, st["exp_avg"], st["exp_avg_sq"], lr=grp["lr"], beta1=grp["betas"][0],
-                                beta2=grp["betas"][1], eps=grp["eps"], weight_decay=grp["weight_decay"],
-                                step=st["step"])
+                self._init_state(st, p, grp)
+                self._update(p, g, st, grp, i)
                 self._invalidate(p)
         return loss
+
+
+class AdamW(_Base):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _init_state(self, st, p, grp):
+        if not st:
+            st["step"] = 0
+            st["exp_avg"] = _zeros_like(p)
+            st["exp_avg_sq"] = _zeros_like(p)
+
+    def _update(self, p, g, st, grp, i):
+        st["step"] = int(st["step"]) + 1
+        ops.adamw_step_(p.data, g, st["exp_avg"], st["exp_avg_sq"], lr=grp["lr"], beta1=grp["betas"][0],
+                        beta2=grp["betas"][1], eps=grp["eps"], weight_decay=grp["weight_decay"], step=st["step"])
 
 
 class Adam(_Base):
@@ -91,77 +107,46 @@ class Adam(_Base):
                 self._lr_dev[i].fill_(lr)
                 self._lr_host[i] = lr
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _begin_step(self):
         capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
         if not capturing:                 # a rate set by hand; inside a capture the scalar is written from outside
             self.sync_lr()
-        for i, grp in enumerate(self.param_groups):
-            for p in grp["params"]:
-                g = _grad32(p)
-                if g is None:
-                    continue
-                st = self.state[p]
-                if not st:
-                    st["step"] = torch.zeros(2, dtype=torch.int64, device=p.device)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                ops.adam_step_dev_(p.data, g, st["exp_avg"], st["exp_avg_sq"], st["step"], self._lr_dev[i],
-                                   beta1=grp["betas"][0], beta2=grp["betas"][1], eps=grp["eps"],
-                                   weight_decay=grp["weight_decay"])
-                self._invalidate(p)
-        return loss
+
+    def _init_state(self, st, p, grp):
+        if not st:
+            st["step"] = torch.zeros(2, dtype=torch.int64, device=p.device)
+            st["exp_avg"] = _zeros_like(p)
+            st["exp_avg_sq"] = _zeros_like(p)
+
+    def _update(self, p, g, st, grp, i):
+        ops.adam_step_dev_(p.data, g, st["exp_avg"], st["exp_avg_sq"], st["step"], self._lr_dev[i],
+                           beta1=grp["betas"][0], beta2=grp["betas"][1], eps=grp["eps"],
+                           weight_decay=grp["weight_decay"])
 
 
 class SGD(_Base):
     def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for grp in self.param_groups:
-            for p in grp["params"]:
-                g = _grad32(p)
-                if g is None:
-                    continue
-                st = self.state[p]
-                if grp["momentum"] != 0 and "momentum_buffer" not in st:
-                    st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                ops.sgd_step_(p.data, g, st.get("momentum_buffer"), lr=grp["lr"], momentum=grp["momentum"],
-                              weight_decay=grp["weight_decay"])
-                self._invalidate(p)
-        return loss
+    def _init_state(self, st, p, grp):
+        if grp["momentum"] != 0 and "momentum_buffer" not in st:
+            st["momentum_buffer"] = _zeros_like(p)
+
+    def _update(self, p, g, st, grp, i):
+        ops.sgd_step_(p.data, g, st.get("momentum_buffer"), lr=grp["lr"], momentum=grp["momentum"],
+                      weight_decay=grp["weight_decay"])
 
 
 class Adagrad(_Base):
     def __init__(self, params, lr=1e-2, lr_decay=0.0, weight_decay=0.0, eps=1e-10):
         super().__init__(params, dict(lr=lr, lr_decay=lr_decay, weight_decay=weight_decay, eps=eps))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for grp in self.param_groups:
-            for p in grp["params"]:
-                g = _grad32(p)
-                if g is None:
-                    continue
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["sum"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["step"] = int(st["step"]) + 1
-                ops.adagrad_step_(p.data, g, st["sum"], lr=grp["lr"], lr_decay=grp["lr_decay"], eps=grp["eps"],
-                                  weight_decay=grp["weight_decay"], step=st["step"])
-                self._invalidate(p)
-        return loss
+    def _init_state(self, st, p, grp):
+        if not st:
+            st["step"] = 0
+            st["sum"] = _zeros_like(p)
+
+    def _update(self, p, g, st, grp, i):
+        st["step"] = int(st["step"]) + 1
+        ops.adagrad_step_(p.data, g, st["sum"], lr=grp["lr"], lr_decay=grp["lr_decay"], eps=grp["eps"],
+                          weight_decay=grp["weight_decay"], step=st["step"])
