@@ -106,6 +106,7 @@ AttnClsDesc = STRUCTS["dvt_attn_cls_desc"]
 LnBwdDesc = STRUCTS["dvt_ln_bwd_desc"]
 LnPending = STRUCTS["dvt_ln_pending"]
 ConvDesc = STRUCTS["dvt_conv_desc"]
+ConvPlanInfo = STRUCTS["dvt_conv_plan_info"]
 Conv3dDesc = STRUCTS["dvt_conv3d_desc"]
 BnAffine = STRUCTS["dvt_bn_affine"]
 PackEntry = STRUCTS["dvt_pack_entry"]

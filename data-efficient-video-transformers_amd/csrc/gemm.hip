@@ -784,10 +784,20 @@ static int generic_kernel_kind(const dvt_gemm_desc* d) {
   if (outs <= 65536 && d->K <= 32) return DVT_GEMM_K_TINY_THREAD;
   return DVT_GEMM_K_GENERIC64;
 }
-// the form a pending reduce takes as a launch of its own (DVT_GEMM_CARRY_*)
+// the kernel a pending reduce runs on as a launch of its own (DVT_CONV_R_*): launch_pending_reduce launches by it, the plan
+// queries report it
+constexpr int kScCi = 32, kScCo = 32;      // splitk_reduce_conv_tiled_kernel: input x output channels of a workgroup's tile
+static int pending_reduce_form(const dvt_splitk_pending* q) {
+  if (q->splits >= 64 && !q->cs_slab && q->M * q->N <= ((int64_t)1 << 20)) return DVT_CONV_R_WIDE;
+  if (q->conv_taps > 0 && !q->cs_slab && q->N % 4 == 0 && q->M * q->N >= ((int64_t)1 << 20) &&
+      q->M == (int64_t)q->conv_taps * q->conv_cin && (size_t)q->conv_taps * kScCi * (kScCo + 1) * 4 <= 64 * 1024)
+    return DVT_CONV_R_SCATTER_TILED;
+  return q->conv_taps > 0 ? DVT_CONV_R_SCATTER : DVT_CONV_R_PLAIN;
+}
+// ... in the terms of dvt_gemm_plan (DVT_GEMM_CARRY_*)
 static int pending_reduce_kind(const dvt_splitk_pending* q) {
-  if (q->splits >= 64 && !q->cs_slab && q->M * q->N <= ((int64_t)1 << 20)) return DVT_GEMM_CARRY_WIDE;
-  return q->conv_taps > 0 ? DVT_GEMM_CARRY_CONV : DVT_GEMM_CARRY_ALONE;
+  const int form = pending_reduce_form(q);
+  return form == DVT_CONV_R_WIDE ? DVT_GEMM_CARRY_WIDE : form == DVT_CONV_R_PLAIN ? DVT_GEMM_CARRY_ALONE : DVT_GEMM_CARRY_CONV;
 }
 
 // Everything dvt_gemm decides before it launches, and the argument checks that go with it.
@@ -926,7 +936,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_wide_kernel(const dvt_split
 // through LDS, and written as 32 x taps contiguous floats per output channel: six launches of 16 - 56 us -> 6 - 15 us each,
 // frametransformer 15.58 -> 15.42 ms same box.  (Carried reduces keep the element-order form in the carrier's grid tail:
 // performing them here instead measured 0 .. +0.1 ms, `gpurun_out/r5_ab_nocarry.log`.)
-constexpr int kScCi = 32, kScCo = 32;
 __global__ __launch_bounds__(256) void splitk_reduce_conv_tiled_kernel(const dvt_splitk_pending q) {
   extern __shared__ float sc_tile[];                 // [taps * 32][33]
   const int taps = q.conv_taps, cin = q.conv_cin;
@@ -965,7 +974,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_conv_tiled_kernel(const dvt
 
 static int launch_pending_reduce(const dvt_splitk_pending* q, hipStream_t st) {
   if (!q || !q->valid) return DVT_OK;
-  if (pending_reduce_kind(q) == DVT_GEMM_CARRY_WIDE) {
+  const int form = pending_reduce_form(q);
+  if (form == DVT_CONV_R_WIDE) {
     hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3((unsigned)dvt_cdiv(q->M * q->N / 8, 32)), dim3(256), 0, st, *q);
     DVT_LAUNCH_CHECK("dvt_gemm(splitk reduce, many slabs)");
     return DVT_OK;
@@ -974,14 +984,13 @@ static int launch_pending_reduce(const dvt_splitk_pending* q, hipStream_t st) {
   int64_t blocks = dvt_cdiv(nvec, 256);
   const int64_t cap = (int64_t)dvt_num_cus() * 8;
   if (blocks > cap) blocks = cap;
-  if (q->conv_taps > 0 && !q->cs_slab && q->N % 4 == 0 && q->M * q->N >= ((int64_t)1 << 20) &&
-      q->M == (int64_t)q->conv_taps * q->conv_cin && (size_t)q->conv_taps * kScCi * (kScCo + 1) * 4 <= 64 * 1024) {
+  if (form == DVT_CONV_R_SCATTER_TILED) {
     const dim3 grid((unsigned)dvt_cdiv(q->conv_cin, kScCi), (unsigned)dvt_cdiv(q->N, kScCo));
     hipLaunchKernelGGL(splitk_reduce_conv_tiled_kernel, grid, dim3(256), (size_t)q->conv_taps * kScCi * (kScCo + 1) * 4, st, *q);
     DVT_LAUNCH_CHECK("dvt_gemm(splitk reduce, convolution scatter, tiled)");
     return DVT_OK;
   }
-  if (q->conv_taps > 0) {
+  if (form == DVT_CONV_R_SCATTER) {
     hipLaunchKernelGGL(splitk_reduce_pending_kernel, dim3((unsigned)blocks), dim3(256), 0, st, *q);
     DVT_LAUNCH_CHECK("dvt_gemm(splitk reduce, convolution scatter)");
     return DVT_OK;
@@ -1312,17 +1321,16 @@ static inline void conv_out_hw(const dvt_conv_desc* d, int64_t* Ho, int64_t* Wo)
   if (d->out_h > 0 && d->out_w > 0) { *Ho = d->out_h; *Wo = d->out_w; }   // (a parity class of a strided data gradient)
 }
 
-static bool conv_implicit_ok(const dvt_conv_desc* d) {
-  if (!d || !d->x || !d->w || !d->y) return false;
+// the geometry is one the implicit kernels serve (no pointer looked at)
+static bool conv_shape_ok(const dvt_conv_desc* d) {
+  if (!d) return false;
   if (!dvt_is_16bit(d->dtype)) return false;
   if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->kh <= 0 || d->kw <= 0 || d->sh <= 0 || d->sw <= 0 || d->ph < 0 || d->pw < 0)
     return false;
-  const int tk = d->Cout <= 128 ? 32 : 64;
   // C % k-tile == 0 (a k-tile inside one filter tap), or C == 8: the stem, its 3 channels zero-extended to one 16-byte
   // chunk per (pixel, tap) by dvt_nchw_to_nhwc_pad
   // (or any C % 8 == 0: the k-tile then straddles taps and every lane derives its own, ConvRows::dma)
   if (d->C % 8 || d->Cout % 8) return false;
-  (void)tk;
   // the C == 8 gather derives a lane's tap by a 16-bit multiply-shift division (ConvRows::dma): exact for these bounds only
   if (d->C == 8 && !((int64_t)d->kh * d->kw < 1024 && d->kw < 64)) return false;
   int64_t Ho, Wo;
@@ -1330,18 +1338,45 @@ static bool conv_implicit_ok(const dvt_conv_desc* d) {
   if (Ho <= 0 || Wo <= 0) return false;
   if (d->N * Ho * Wo >= ((int64_t)1 << 31) || d->N * d->H * d->W >= ((int64_t)1 << 31)) return false;
   if ((int64_t)d->kh * d->kw * d->C >= ((int64_t)1 << 31)) return false;
-  return dvt_aligned16(d->x) && dvt_aligned16(d->w) && dvt_aligned16(d->y);
+  return true;
+}
+
+static bool conv_implicit_ok(const dvt_conv_desc* d) {
+  if (!d || !d->x || !d->w || !d->y) return false;
+  return conv_shape_ok(d) && dvt_aligned16(d->x) && dvt_aligned16(d->w) && dvt_aligned16(d->y);
 }
 
 int dvt_conv2d_implicit_supported(const dvt_conv_desc* d) { return conv_implicit_ok(d) ? 1 : 0; }
 
-// slices of the reduction this descriptor's launch uses (1: the one-launch form); scattered class launches stay unsplit
+// The ONE plan of a forward / data-gradient launch: dvt_conv2d_implicit launches by it; the workspace and statistics sizes
+// and dvt_conv2d_implicit_plan report it.  Scattered class launches (out_rows) stay unsplit.  A split launch runs on the
+// 128 x 128 slab kernels: at most one workgroup per CU in all -> the four-deep ring of configuration 10, else two 64 KiB
+// workgroups per CU (configuration 9).
+struct ConvFwdPlan { int cfg, split, kps, K, Ho, Wo; int64_t rows; };
+static ConvFwdPlan conv_fwd_plan(const dvt_conv_desc* d) {
+  ConvFwdPlan pl{};
+  int64_t Ho, Wo;
+  conv_out_hw(d, &Ho, &Wo);
+  pl.Ho = (int)Ho; pl.Wo = (int)Wo; pl.rows = d->N * Ho * Wo;
+  pl.K = (int)dvt_conv2d_implicit_k(d);
+  const int taps = d->kh * d->kw;
+  pl.cfg = conv_fwd_cfg(pl.rows, d->Cout, d->C, taps);
+  pl.split = d->out_rows ? 1 : conv_fwd_split(pl.rows, d->Cout, d->C, taps, pl.K);
+  pl.kps = pl.K;
+  if (pl.split > 1) {
+    pl.kps = (int)(dvt_cdiv(pl.K / 64, pl.split) * 64);
+    pl.cfg = dvt_cdiv(pl.rows, 128) * dvt_cdiv(d->Cout, 128) * pl.split <= dvt_num_cus() ? 10 : 9;
+  }
+  return pl;
+}
+
+// slices of the reduction this descriptor's launch uses (1: the one-launch form)
 static int conv_desc_split(const dvt_conv_desc* d) {
   if (!d || d->out_rows || d->C <= 0 || d->sh <= 0 || d->sw <= 0) return 1;
   int64_t Ho, Wo;
   conv_out_hw(d, &Ho, &Wo);
   if (Ho <= 0 || Wo <= 0 || d->N <= 0) return 1;
-  return conv_fwd_split(d->N * Ho * Wo, d->Cout, d->C, d->kh * d->kw, dvt_conv2d_implicit_k(d));
+  return conv_fwd_plan(d).split;
 }
 
 // S fp32 slabs [rows][N] for a split launch (0: none needed)
@@ -1362,61 +1397,82 @@ int64_t dvt_conv2d_implicit_k(const dvt_conv_desc* d) {
   return d->C % tk ? dvt_cdiv(K, tk) * tk : K;
 }
 
+// Everything dvt_conv2d_implicit decides before it launches, and the argument checks that go with it (the operand pointers
+// aside: the launcher checks those, the plan query does not need them).
+static int resolve_conv_fwd(const dvt_conv_desc* d, ConvFwdPlan* pl, dvt_conv_plan_info* in) {
+  DVT_REQUIRE(d, "dvt_conv2d_implicit: null descriptor");
+  if (!conv_shape_ok(d))
+    DVT_UNSUPPORTED("dvt_conv2d_implicit: needs a 16-bit dtype, C %% 8 == 0, Cout %% 8 == 0 and "
+                    "16-byte aligned buffers");
+  DVT_REQUIRE(!(d->residual && d->stats_partial), "dvt_conv2d_implicit: residual and stats_partial are exclusive");
+  DVT_REQUIRE(dvt_aligned16(d->residual), "dvt_conv2d_implicit: residual must be 16-byte aligned");
+  DVT_REQUIRE((d->out_h > 0) == (d->out_w > 0) && (!d->out_rows || (((uintptr_t)d->out_rows & 3) == 0 && !d->stats_partial)) &&
+                  (!d->residual_compact || (d->out_rows && d->residual)),
+              "dvt_conv2d_implicit: out_h / out_w come together; out_rows is 4-byte aligned and excludes stats_partial; "
+              "residual_compact needs out_rows and a residual");
+  *pl = conv_fwd_plan(d);
+  const bool split = pl->split > 1;
+  if (split)
+    DVT_REQUIRE(d->workspace && dvt_aligned16(d->workspace),
+                "dvt_conv2d_implicit: this shape runs split-K and needs dvt_conv2d_implicit_workspace_bytes of 16-byte aligned workspace");
+  *in = dvt_conv_plan_info{};
+  in->cfg = pl->cfg; in->split = pl->split; in->k_per_split = pl->kps;
+  in->epilogue = !split && d->residual ? DVT_EPI_RESIDUAL : DVT_EPI_NONE;     // (split: the reduce adds it)
+  in->out_form = split ? 2 : 0;
+  in->reduce = split ? DVT_CONV_R_SPLIT : DVT_CONV_R_NONE;
+  if (d->carry && d->carry->valid) {
+    // a pending split-K reduce rides in a one-slice launch's grid tail; the grid tail of a split launch carries nothing: the
+    // reduce runs by itself first
+    in->carry = split ? DVT_CONV_CARRY_ALONE : DVT_CONV_CARRY_TAIL;
+    in->carry_reduce = split ? pending_reduce_form(d->carry) : DVT_CONV_R_NONE;
+  }
+  return DVT_OK;
+}
+
 int dvt_conv2d_implicit(const dvt_conv_desc* d, dvt_stream_t stream) {
   DVT_REQUIRE(d, "dvt_conv2d_implicit: null descriptor");
   if (!conv_implicit_ok(d))
     DVT_UNSUPPORTED("dvt_conv2d_implicit: needs a 16-bit dtype, C %% 8 == 0, Cout %% 8 == 0 and "
                     "16-byte aligned buffers");
-  int64_t Ho64, Wo64;
-  conv_out_hw(d, &Ho64, &Wo64);
-  const int Ho = (int)Ho64, Wo = (int)Wo64;
+  ConvFwdPlan pl;
+  dvt_conv_plan_info in;
+  const int rcp = resolve_conv_fwd(d, &pl, &in);
+  if (rcp) return rcp;
+  hipStream_t st = (hipStream_t)stream;
   GemmParams p{};
   p.A = (const bf16*)d->x; p.B = (const bf16*)d->w; p.C = d->y;
-  p.M = (int)(d->N * Ho * Wo); p.N = d->Cout; p.K = (int)dvt_conv2d_implicit_k(d);
+  p.M = (int)pl.rows; p.N = d->Cout; p.K = pl.K;
   p.lda = 0; p.ldb = p.K; p.ldc = d->Cout;
-  p.epilogue = d->residual ? DVT_EPI_RESIDUAL : DVT_EPI_NONE; p.out_f32 = 0; p.accumulate = 0;
-  p.bias = nullptr; p.residual = d->residual; p.ldr = d->Cout; p.aux = nullptr; p.ldaux = 0;
-  p.alpha = 1.0f; p.elem = d->dtype; p.k_per_split = p.K; p.slab = nullptr; p.tiles_n = 0; p.colsum_slab = nullptr;
-  p.cH = d->H; p.cW = d->W; p.cC = d->C; p.cHo = Ho; p.cWo = Wo; p.ckh = d->kh; p.ckw = d->kw;
+  p.epilogue = in.epilogue; p.out_f32 = 0; p.accumulate = 0;
+  p.bias = nullptr; p.residual = in.epilogue == DVT_EPI_RESIDUAL ? d->residual : nullptr; p.ldr = d->Cout; p.aux = nullptr; p.ldaux = 0;
+  p.alpha = 1.0f; p.elem = d->dtype; p.k_per_split = in.k_per_split; p.slab = nullptr; p.tiles_n = 0; p.colsum_slab = nullptr;
+  p.cH = d->H; p.cW = d->W; p.cC = d->C; p.cHo = pl.Ho; p.cWo = pl.Wo; p.ckh = d->kh; p.ckw = d->kw;
   p.csh = d->sh; p.csw = d->sw; p.cph = d->ph; p.cpw = d->pw;
   p.cmc = (unsigned)((((uint64_t)1 << 32) + (uint64_t)(d->C / 8) - 1) / (uint64_t)(d->C / 8));   // (C == 8: unused)
   p.cmk = d->kw == 1 ? 0u : (unsigned)((((uint64_t)1 << 32) + (uint64_t)d->kw - 1) / (uint64_t)d->kw);
-  DVT_REQUIRE(!(d->residual && d->stats_partial), "dvt_conv2d_implicit: residual and stats_partial are exclusive");
-  DVT_REQUIRE(dvt_aligned16(d->residual), "dvt_conv2d_implicit: residual must be 16-byte aligned");
-  p.bn_partial = d->stats_partial;
-  DVT_REQUIRE((d->out_h > 0) == (d->out_w > 0) && (!d->out_rows || (((uintptr_t)d->out_rows & 3) == 0 && !d->stats_partial)) &&
-                  (!d->residual_compact || (d->out_rows && d->residual)),
-              "dvt_conv2d_implicit: out_h / out_w come together; out_rows is 4-byte aligned and excludes stats_partial; "
-              "residual_compact needs out_rows and a residual");
   p.orow = d->out_rows; p.res_compact = d->residual_compact;
-  const int split = conv_desc_split(d);
-  if (split > 1) {
-    DVT_REQUIRE(d->workspace && dvt_aligned16(d->workspace),
-                "dvt_conv2d_implicit: this shape runs split-K and needs dvt_conv2d_implicit_workspace_bytes of 16-byte aligned workspace");
-    hipStream_t st = (hipStream_t)stream;
-    if (d->carry && d->carry->valid) {             // (the grid tail of a split launch carries nothing: the reduce runs by itself)
-      const int rc = dvt_splitk_reduce_pending(d->carry, stream);
-      if (rc != DVT_OK) return rc;
-    }
-    const int64_t nk = p.K / 64;
-    p.k_per_split = (int)(dvt_cdiv(nk, split) * 64);
+  if (in.carry == DVT_CONV_CARRY_ALONE) {
+    const int rc = dvt_splitk_reduce_pending(d->carry, stream);
+    if (rc != DVT_OK) return rc;
+  }
+  if (in.out_form == 2) {                            // fp32 slabs, then the reduce that rounds, adds the residual and leaves the statistics
     p.slab = (float*)d->workspace;
-    p.epilogue = DVT_EPI_NONE; p.residual = nullptr; p.bn_partial = nullptr;
-    const int rc = dvt_conv_dma_launch_split(p, split, st);
+    const int rc = dvt_conv_dma_launch_split(p, in.split, in.cfg, st);
     if (rc != DVT_OK) return rc;
     const dim3 grid((unsigned)dvt_cdiv(p.N, 256), (unsigned)dvt_cdiv(p.M, kConvSplitRows));
     DVT_DISPATCH_16BIT(d->dtype, E, hipLaunchKernelGGL((conv_split_reduce_kernel<E>), grid, dim3(256), 0, st, (const float*)p.slab,
-                                                       split, p.M, p.N, (E*)d->y, (const E*)d->residual, d->stats_partial));
+                                                       in.split, p.M, p.N, (E*)d->y, (const E*)d->residual, d->stats_partial));
     DVT_LAUNCH_CHECK("dvt_conv2d_implicit(split-K reduce)");
     return DVT_OK;
   }
-  if (d->carry && d->carry->valid) {               // a pending split-K reduce rides in this launch's grid tail
+  p.bn_partial = d->stats_partial;
+  if (in.carry == DVT_CONV_CARRY_TAIL) {
     const int64_t slab_bytes_c = d->carry->M * d->carry->N * 4 * d->carry->splits;
     int64_t nb = dvt_cdiv(slab_bytes_c, (int64_t)1 << 19);
     p.pig_blocks = (int)(nb < 1 ? 1 : nb > 128 ? 128 : nb);
     p.pig = *d->carry;
   }
-  return dvt_conv_dma_launch(p, conv_fwd_cfg(p.M, d->Cout, d->C, d->kh * d->kw), (hipStream_t)stream);
+  return dvt_conv_dma_launch(p, in.cfg, st);
 }
 
 // one partial row per wave row of a 256-row tile: 2 (128 output rows each) in configurations 0 and 1, 4 (64 rows) in 4, 6, 7
@@ -1426,7 +1482,7 @@ int64_t dvt_conv2d_implicit_stats_parts(const dvt_conv_desc* d) {
   conv_out_hw(d, &Ho, &Wo);
   if (Ho <= 0 || Wo <= 0 || d->N <= 0) return 0;
   if (conv_desc_split(d) > 1) return dvt_cdiv(d->N * Ho * Wo, kConvSplitRows);                      // split launch: the reduce's row blocks
-  const int cfg = conv_fwd_cfg(d->N * Ho * Wo, d->Cout, d->C, d->kh * d->kw);
+  const int cfg = conv_fwd_plan(d).cfg;
   if (cfg == 9 || cfg == 10) return dvt_cdiv(d->N * Ho * Wo, 128) * 2;                             // 128-row tiles of two wave rows
   return dvt_cdiv(d->N * Ho * Wo, 256) * (cfg == 4 || cfg == 6 || cfg == 7 ? 4 : 2);   // wave rows per 256-row tile
 }
@@ -1439,8 +1495,10 @@ size_t dvt_conv2d_implicit_stats_bytes(const dvt_conv_desc* d) {
 // ---- weight gradient: dWt[(ki,kj,c), co] = sum_rows col[row, (ki,kj,c)] * dz[row, co], col gathered on the fly
 struct ConvWgradPlan { int cfg, tk, split, kps; int64_t rows; int Ho, Wo, K; size_t slab_bytes; };
 
-static bool conv_wgrad_plan(const dvt_conv_desc* d, ConvWgradPlan* pl) {
-  if (!d || !d->x || !d->w || !d->y || !dvt_is_16bit(d->dtype)) return false;
+// ptrs: the operand pointers count too (the launcher, _supported, _workspace_bytes), or the geometry alone (the plan query)
+static bool conv_wgrad_plan(const dvt_conv_desc* d, ConvWgradPlan* pl, bool ptrs = true) {
+  if (!d || !dvt_is_16bit(d->dtype)) return false;
+  if (ptrs && (!d->x || !d->w || !d->y)) return false;
   if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->kh <= 0 || d->kw <= 0 || d->sh <= 0 || d->sw <= 0 || d->ph < 0 || d->pw < 0)
     return false;
   if (d->C % 8 || d->Cout % 8) return false;
@@ -1465,7 +1523,7 @@ static bool conv_wgrad_plan(const dvt_conv_desc* d, ConvWgradPlan* pl) {
   pl->kps = (int)(dvt_cdiv(ktiles, split) * pl->tk);
   pl->split = (int)dvt_cdiv(rows, pl->kps);
   pl->slab_bytes = (size_t)pl->split * (size_t)pl->K * (size_t)d->Cout * sizeof(float);
-  return dvt_aligned16(d->x) && dvt_aligned16(d->w) && dvt_aligned16(d->y);
+  return !ptrs || (dvt_aligned16(d->x) && dvt_aligned16(d->w) && dvt_aligned16(d->y));
 }
 
 int dvt_conv2d_implicit_wgrad_supported(const dvt_conv_desc* d) {
@@ -1478,12 +1536,43 @@ size_t dvt_conv2d_implicit_wgrad_workspace_bytes(const dvt_conv_desc* d) {
   return conv_wgrad_plan(d, &pl) ? align256(pl.slab_bytes) : 0;
 }
 
+// the reduce behind the weight-gradient launch as a pending descriptor: what a deferring call leaves in *desc->pending, and
+// what the master-layout reduce of a call that does not defer is launched from
+static dvt_splitk_pending conv_wgrad_pending(const dvt_conv_desc* d, const ConvWgradPlan& pl) {
+  dvt_splitk_pending q{};
+  q.slab = (const float*)d->workspace; q.splits = pl.split; q.valid = 1; q.M = pl.K; q.N = d->Cout; q.C = (float*)d->y;
+  q.ldc = d->Cout;
+  if (d->wgrad_master_layout) {
+    q.conv_cin = d->C; q.conv_taps = d->kh * d->kw; q.accumulate = d->wgrad_accumulate;
+    q.conv_cin_l = d->wgrad_cin_l; q.conv_cout_l = d->wgrad_cout_l;
+  }
+  return q;
+}
+
+// Everything dvt_conv2d_implicit_wgrad decides before it launches (launch: the operand pointers are checked as well).
+static int resolve_conv_wgrad(const dvt_conv_desc* d, bool launch, ConvWgradPlan* pl, dvt_conv_plan_info* in) {
+  if (!conv_wgrad_plan(d, pl, launch))
+    DVT_UNSUPPORTED("dvt_conv2d_implicit_wgrad: needs a 16-bit dtype, C %% 8 == 0 and Cout %% 8 == 0");
+  DVT_REQUIRE(d->workspace, "dvt_conv2d_implicit_wgrad: workspace (dvt_conv2d_implicit_wgrad_workspace_bytes) required");
+  DVT_REQUIRE(!d->defer_reduce || d->pending, "dvt_conv2d_implicit_wgrad: defer_reduce needs a pending descriptor to fill");
+  *in = dvt_conv_plan_info{};
+  in->cfg = pl->cfg; in->split = pl->split; in->k_per_split = pl->kps;
+  in->epilogue = DVT_EPI_NONE;
+  in->out_form = 2;                                  // (always slabs: one slice is reduced like any other count)
+  in->deferred = d->defer_reduce != 0;
+  const dvt_splitk_pending q = conv_wgrad_pending(d, *pl);
+  // the packed dWt of a call that does not defer is summed by the plain reduce whatever its size; a pending descriptor
+  // (deferred, or the master-layout scatter) takes the form launch_pending_reduce gives it
+  in->reduce = d->defer_reduce || d->wgrad_master_layout ? pending_reduce_form(&q) : DVT_CONV_R_PLAIN;
+  return DVT_OK;
+}
+
 // x = d->x (NHWC input of the layer), dz = d->w ([rows, Cout]), dWt = d->y (f32 [kh*kw*C, Cout], overwritten)
 int dvt_conv2d_implicit_wgrad(const dvt_conv_desc* d, dvt_stream_t stream) {
   ConvWgradPlan pl;
-  if (!conv_wgrad_plan(d, &pl))
-    DVT_UNSUPPORTED("dvt_conv2d_implicit_wgrad: needs a 16-bit dtype, C %% 8 == 0 and Cout %% 8 == 0");
-  DVT_REQUIRE(d->workspace, "dvt_conv2d_implicit_wgrad: workspace (dvt_conv2d_implicit_wgrad_workspace_bytes) required");
+  dvt_conv_plan_info in;
+  const int rcp = resolve_conv_wgrad(d, true, &pl, &in);
+  if (rcp) return rcp;
   hipStream_t st = (hipStream_t)stream;
   GemmParams p{};
   p.A = (const bf16*)d->x; p.B = (const bf16*)d->w; p.C = d->y;
@@ -1491,31 +1580,18 @@ int dvt_conv2d_implicit_wgrad(const dvt_conv_desc* d, dvt_stream_t stream) {
   p.lda = 0; p.ldb = d->Cout; p.ldc = d->Cout;
   p.epilogue = DVT_EPI_NONE; p.out_f32 = 1; p.accumulate = 0;
   p.bias = nullptr; p.residual = nullptr; p.ldr = 0; p.aux = nullptr; p.ldaux = 0;
-  p.alpha = 1.0f; p.elem = d->dtype; p.k_per_split = pl.kps; p.slab = (float*)d->workspace; p.tiles_n = 0;
+  p.alpha = 1.0f; p.elem = d->dtype; p.k_per_split = in.k_per_split; p.slab = (float*)d->workspace; p.tiles_n = 0;
   p.colsum_slab = nullptr;
   p.cH = d->H; p.cW = d->W; p.cC = d->C; p.cHo = pl.Ho; p.cWo = pl.Wo; p.ckh = d->kh; p.ckw = d->kw;
   p.csh = d->sh; p.csw = d->sw; p.cph = d->ph; p.cpw = d->pw;
-  int rc = dvt_conv_wgrad_dma_launch(p, pl.split, pl.cfg, st);
+  int rc = dvt_conv_wgrad_dma_launch(p, in.split, in.cfg, st);
   if (rc) return rc;
-  if (d->defer_reduce) {                           // left to the data-gradient launch of the same layer (d->pending -> its carry)
-    DVT_REQUIRE(d->pending, "dvt_conv2d_implicit_wgrad: defer_reduce needs a pending descriptor to fill");
-    dvt_splitk_pending* q = d->pending;
-    q->slab = p.slab; q->splits = pl.split; q->valid = 1; q->M = p.M; q->N = p.N; q->C = (float*)d->y; q->ldc = d->Cout;
-    q->accumulate = 0; q->cs_accumulate = 0; q->cs_slab = nullptr; q->cs_out = nullptr;
-    q->conv_cin = 0; q->conv_taps = 0; q->conv_cin_l = 0; q->conv_cout_l = 0;
-    if (d->wgrad_master_layout) {
-      q->conv_cin = d->C; q->conv_taps = d->kh * d->kw; q->accumulate = d->wgrad_accumulate;
-      q->conv_cin_l = d->wgrad_cin_l; q->conv_cout_l = d->wgrad_cout_l;
-    }
+  const dvt_splitk_pending q = conv_wgrad_pending(d, pl);
+  if (in.deferred) {                                 // left to the data-gradient launch of the same layer (d->pending -> its carry)
+    *d->pending = q;
     return DVT_OK;
   }
-  if (d->wgrad_master_layout) {
-    dvt_splitk_pending q{};
-    q.slab = p.slab; q.splits = pl.split; q.valid = 1; q.M = p.M; q.N = p.N; q.C = (float*)d->y; q.ldc = d->Cout;
-    q.accumulate = d->wgrad_accumulate; q.conv_cin = d->C; q.conv_taps = d->kh * d->kw;
-    q.conv_cin_l = d->wgrad_cin_l; q.conv_cout_l = d->wgrad_cout_l;
-    return launch_pending_reduce(&q, st);
-  }
+  if (d->wgrad_master_layout) return launch_pending_reduce(&q, st);
   const int64_t nvec = (int64_t)p.M * p.N / 8;
   int64_t blocks = dvt_cdiv(nvec, 256);
   const int64_t cap = (int64_t)dvt_num_cus() * 8;
@@ -1524,6 +1600,16 @@ int dvt_conv2d_implicit_wgrad(const dvt_conv_desc* d, dvt_stream_t stream) {
                      p.M, p.N, (float*)d->y, (int64_t)d->Cout, 0, (const float*)nullptr, (float*)nullptr, 0);
   DVT_LAUNCH_CHECK("dvt_conv2d_implicit_wgrad(reduce)");
   return DVT_OK;
+}
+
+int dvt_conv2d_implicit_plan(const dvt_conv_desc* d, int wgrad, dvt_conv_plan_info* info) {
+  DVT_REQUIRE(info, "dvt_conv2d_implicit_plan: null info");
+  if (wgrad) {
+    ConvWgradPlan pl;
+    return resolve_conv_wgrad(d, false, &pl, info);
+  }
+  ConvFwdPlan pl;
+  return resolve_conv_fwd(d, &pl, info);
 }
 
 size_t dvt_colsum_workspace_bytes(int64_t M, int64_t N) {

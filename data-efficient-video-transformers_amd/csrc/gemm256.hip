@@ -843,9 +843,9 @@ static int launch_conv_split(const GemmParams& pin, int split, hipStream_t st) {
   DVT_LAUNCH_CHECK("dvt_conv2d_implicit(dma, split K)");
   return DVT_OK;
 }
-// (at most one workgroup per CU in all: the four-deep ring of configuration 10; else two 64 KiB workgroups per CU)
-int dvt_conv_dma_launch_split(const GemmParams& p, int split, hipStream_t st) {
-  const bool one = dvt_cdiv(p.M, 128) * dvt_cdiv(p.N, 128) * split <= dvt_num_cus();
+// (cfg 10: at most one workgroup per CU in all, the four-deep ring; cfg 9: two 64 KiB workgroups per CU -- the caller's plan)
+int dvt_conv_dma_launch_split(const GemmParams& p, int split, int cfg, hipStream_t st) {
+  const bool one = cfg == 10;
   if (p.elem == DVT_F16) return one ? launch_conv_split<f16, 10>(p, split, st) : launch_conv_split<f16, 9>(p, split, st);
   return one ? launch_conv_split<bf16, 10>(p, split, st) : launch_conv_split<bf16, 9>(p, split, st);
 }

@@ -1883,6 +1883,68 @@ def conv2d_implicit_wgrad(x: Tensor, dz: Tensor, N: int, Cc: int, H: int, W: int
     return (out, pending) if defer_reduce else out
 
 
+class ConvPlan(NamedTuple):
+    """What one dvt_conv2d_implicit / dvt_conv2d_implicit_wgrad call launches (dvt_conv2d_implicit_plan): the LDS-DMA
+    configuration of its gemm_dma_kernel<..., true>, the slices of the reduction and its length per slice, the launch's
+    epilogue and output form ("map" = the 16-bit map, "slab" = fp32 split-K partials), the kernel that sums the slabs as a
+    launch of its own (CONV_REDUCES) and whether that reduce is left in a pending descriptor, and what becomes of a
+    carried reduce (CONV_CARRIES; carry_reduce: its kernel when it is launched on its own)."""
+    cfg: int
+    split: int = 1
+    k_per_split: int = 0
+    epilogue: int = L.EPI_NONE
+    out: str = "map"
+    reduce: str = "none"
+    deferred: bool = False
+    carry: str = "none"
+    carry_reduce: str = "none"
+
+
+CONV_OUTS = {0: "map", 2: "slab"}                     # dvt_conv_plan_info.out_form
+CONV_REDUCES = _enum_names("dvt_conv_reduce", "DVT_CONV_R_")
+CONV_CARRIES = _enum_names("dvt_conv_carry", "DVT_CONV_CARRY_")
+
+
+def conv2d_implicit_plan(N: int, Cc: int, H: int, W: int, Cout: int, k, stride, pad, dtype: torch.dtype, *,
+                         wgrad: bool = False, trim_w: int = 0, residual: bool = False, want_stats: bool = False, carry=None,
+                         out_hw=None, out_rows: bool = False, residual_compact: bool = False, defer_reduce: bool = False,
+                         master: bool = False, accumulate: bool = False, logical: Optional[Tuple[int, int]] = None,
+                         workspace: Optional[bool] = None) -> ConvPlan:
+    """What ``conv2d_implicit`` (or, wgrad=True, ``conv2d_implicit_wgrad``) launches for the same geometry and options
+    (dvt_conv2d_implicit_plan: the launcher's own decisions, no launch, no device, no tensors -- the options that name
+    tensors there are flags here).  workspace: None = given where the launcher's size query asks for one; False = withheld."""
+    (kh, kw), (sh, sw), (ph, pw) = _pair(k), _pair(stride), _pair(pad)
+    d = L.ConvDesc()
+    d.x = d.w = d.y = 1 << 4                          # (stand-ins: the size queries look at them, the plan does not)
+    d.N, d.H, d.W, d.C, d.Cout = N, H, W, Cc, Cout
+    d.kh, d.kw, d.sh, d.sw, d.ph, d.pw = kh, kw, sh, sw, ph, pw
+    d.dtype, d.trim_w = _DT[dtype], trim_w
+    keep = []
+    if out_hw is not None:
+        d.out_h, d.out_w = out_hw
+    if out_rows:
+        d.out_rows, d.residual_compact = 1 << 4, int(residual_compact)
+    if residual:
+        d.residual = 1 << 4
+    if want_stats:
+        d.stats_partial = 1 << 4
+    if carry is not None:
+        d.carry = C.pointer(carry)
+    if wgrad:
+        d.wgrad_master_layout, d.wgrad_accumulate = int(master), int(accumulate)
+        d.wgrad_cout_l, d.wgrad_cin_l = logical if (master and logical is not None) else (0, 0)
+        if defer_reduce:
+            keep.append(L.SplitKPending())
+            d.defer_reduce, d.pending = 1, C.pointer(keep[-1])
+    lib = L.load()
+    need = lib.dvt_conv2d_implicit_wgrad_workspace_bytes(C.byref(d)) if wgrad else lib.dvt_conv2d_implicit_workspace_bytes(C.byref(d))
+    d.workspace = 256 if (need > 0 and workspace is not False) else None
+    q = L.ConvPlanInfo()
+    L.check(lib.dvt_conv2d_implicit_plan(C.byref(d), int(wgrad), C.byref(q)), "dvt_conv2d_implicit_plan")
+    return ConvPlan(q.cfg, q.split, q.k_per_split, q.epilogue, CONV_OUTS[q.out_form], CONV_REDUCES[q.reduce], bool(q.deferred),
+                    CONV_CARRIES[q.carry], CONV_REDUCES[q.carry_reduce])
+
+
 def conv_weight_unpack_grad_t(gt: Tensor, shape, *, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     Cout, Cin, kh, kw = shape
     if out is None:

@@ -817,6 +817,36 @@ size_t dvt_conv2d_implicit_stats_bytes(const dvt_conv_desc* desc);
 int dvt_conv2d_implicit_wgrad_supported(const dvt_conv_desc* desc);
 size_t dvt_conv2d_implicit_wgrad_workspace_bytes(const dvt_conv_desc* desc);
 int dvt_conv2d_implicit_wgrad(const dvt_conv_desc* desc, dvt_stream_t stream);
+/* What dvt_conv2d_implicit (wgrad == 0) or dvt_conv2d_implicit_wgrad (wgrad != 0) would launch for desc, taken from the
+ * same decisions the launchers make (ABI v5 addition; host only, runs without a device: the CU-count dependent thresholds
+ * then assume the MI355X's 256).  The operand pointers x / w / y are not looked at; every other field counts -- a split
+ * launch without desc->workspace is refused as the launcher refuses it, and `carry` reports what becomes of a valid
+ * desc->carry.  Returns what the launcher returns for a descriptor it refuses, else DVT_OK. */
+enum dvt_conv_reduce {             /* the kernel that sums split-K slabs, as a launch of its own */
+  DVT_CONV_R_NONE = 0,             /* forward / data gradient in one slice: no slabs */
+  DVT_CONV_R_SPLIT = 1,            /* conv_split_reduce_kernel (forward: rounds, adds `residual`, leaves the BatchNorm partials) */
+  DVT_CONV_R_PLAIN = 2,            /* splitk_reduce_kernel<float> (the packed dWt) */
+  DVT_CONV_R_WIDE = 3,             /* splitk_reduce_wide_kernel (>= 64 slices, at most 2^20 entries) */
+  DVT_CONV_R_SCATTER = 4,          /* splitk_reduce_pending_kernel scattering into the parameter's layout */
+  DVT_CONV_R_SCATTER_TILED = 5     /* splitk_reduce_conv_tiled_kernel (the same through LDS tiles: 2^20 entries and more) */
+};
+enum dvt_conv_carry {              /* what becomes of a valid desc->carry */
+  DVT_CONV_CARRY_NONE = 0,
+  DVT_CONV_CARRY_TAIL = 1,         /* rides in the grid tail of the one-slice launch */
+  DVT_CONV_CARRY_ALONE = 2         /* launched on its own first (a split launch carries nothing): carry_reduce tells the kernel */
+};
+typedef struct dvt_conv_plan_info {
+  int32_t cfg;            /* LDS-DMA configuration of the gemm_dma_kernel<..., true> launch */
+  int32_t split;          /* slices of the reduction (blockIdx.z); 1: none */
+  int32_t k_per_split;    /* reduction length per slice: channels x taps (forward), output pixels (weight gradient) */
+  int32_t epilogue;       /* DVT_EPI_NONE or DVT_EPI_RESIDUAL of that launch (NONE where the reduce adds the residual) */
+  int32_t out_form;       /* 0 = the map in desc->dtype, 2 = fp32 split-K slabs */
+  int32_t reduce;         /* enum dvt_conv_reduce */
+  int32_t deferred;       /* 1: the reduce is left undone in *desc->pending (`reduce`: what dvt_splitk_reduce_pending would run) */
+  int32_t carry;          /* enum dvt_conv_carry */
+  int32_t carry_reduce;   /* CARRY_ALONE: enum dvt_conv_reduce of the carried reduce's own launch; else NONE */
+} dvt_conv_plan_info;
+int dvt_conv2d_implicit_plan(const dvt_conv_desc* desc, int wgrad, dvt_conv_plan_info* info);
 int dvt_conv_weight_unpack_grad_t(const float* gt, float* dw, int Cout, int Cin, int kh, int kw, int accumulate,
                                   dvt_stream_t stream);
 /* w[Cout,Cin,kh,kw] f32 -> dst[Cout, ld] (column order (ki,kj,ci), zero padded) in dst_dtype, and the

@@ -1,7 +1,10 @@
 """CPU gate on the GEMM family's exact tests: every GEMM kernel symbol of the built library is either launched by a named
 case of tests/test_gpu_gemm_exact.py -- the library's own plan query (dvt_gemm_plan) says that case takes that
 instantiation -- or listed as unreachable from dvt_gemm with a reason; and the operands of those cases see a missing,
-doubled or misplaced k-step and a misplaced output fragment."""
+doubled or misplaced k-step and a misplaced output fragment.
+
+The convolution forms of the LDS-DMA kernel (gemm_dma_kernel<..., true>: the A operand gathered from an NHWC map) are not
+this gate's: tests/test_conv_coverage.py accounts for every one of them, with tests/test_gpu_conv_exact.py."""
 import re
 
 import pytest
