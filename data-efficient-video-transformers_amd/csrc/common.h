@@ -51,6 +51,7 @@ namespace dvt_internal {
 // conv3x1_c64.hip: the 64 -> 64 form of the (3, 1, 1) window convolution, behind dvt_conv3x1_fwd (conv3x1_fwd.hip)
 int conv3x1_c64_supported(int64_t N, int T, int L, int dtype);
 int64_t conv3x1_c64_stats_parts(int64_t N, int T, int L);
+int conv3x1_c64_npb(int64_t N, int T, int L, int dtype);
 int conv3x1_c64_fwd(const void* x, const void* w, int64_t ldw, void* y, float* stats_partial, int64_t N, int T, int L, int dtype,
                     hipStream_t st);
 void bn_bwd_finalize(hipStream_t st, const float* partial, int nparts, int C, float* loc, int accumulate, float* dgamma,
@@ -59,6 +60,7 @@ void bn_bwd_finalize(hipStream_t st, const float* partial, int nparts, int C, fl
 // (behind dvt_conv3x1_stream_bn_bwd, conv3x3_stream.hip)
 int conv3x1_dbn_supported(int64_t N, int T, int L, int dtype);
 int conv3x1_dbn_parts(int64_t N, int T, int L);
+int conv3x1_dbn_nb(int64_t N, int T, int L, int dtype);
 int conv3x1_dbn_pass(int mode, const void* dy, const void* w, int64_t ldw, const void* z, const float* mean, const float* invstd,
                      const float* gamma, const float* beta, int relu, int training, float* partial, const float* loc, void* dz,
                      int64_t N, int T, int L, int dtype, hipStream_t st);

@@ -56,6 +56,9 @@ int tc_plan(int T, int L, Win* q) {
   return 0;
 }
 
+// 16-position blocks per wave: the template parameter of conv3x1_c64_kernel (KP is a multiple of 32, at most 32 kMaxPB)
+int tc_npb(const Win& q) { return q.KP >> 5; }
+
 int tc_grid(int64_t N, const Win& q) {
   const int64_t ntiles = N * q.segs;
   return (int)(ntiles < dvt_num_cus() ? ntiles : dvt_num_cus());
@@ -220,6 +223,13 @@ int64_t conv3x1_c64_stats_parts(int64_t N, int T, int L) {
   return tc_grid(N, q);                            // one partial row per workgroup of the persistent grid
 }
 
+// the launcher's instantiation: position blocks per wave (1 .. 6), 0 where the geometry is not taken
+int conv3x1_c64_npb(int64_t N, int T, int L, int dtype) {
+  Win q;
+  if (!conv3x1_c64_supported(N, T, L, dtype) || !tc_plan(T, L, &q)) return 0;
+  return tc_npb(q);
+}
+
 // (arguments checked by dvt_conv3x1_fwd)
 int conv3x1_c64_fwd(const void* x, const void* w, int64_t ldw, void* y, float* stats_partial, int64_t N, int T, int L, int dtype,
                     hipStream_t st) {
@@ -231,7 +241,7 @@ int conv3x1_c64_fwd(const void* x, const void* w, int64_t ldw, void* y, float* s
   int lds = 2 * p.w_.x_bytes + p.w_.KP * 128;
   if (lds < 2 * kNW * 64 * 8 * 4) lds = 2 * kNW * 64 * 8 * 4;      // (the statistics scratch [2][512][8] overlays the images)
   const bool h = dtype == DVT_F16;
-  switch (p.w_.KP >> 5) {
+  switch (tc_npb(p.w_)) {
     case 1: h ? tc_launch<f16, 1>(p, grid, lds, st) : tc_launch<bf16, 1>(p, grid, lds, st); break;
     case 2: h ? tc_launch<f16, 2>(p, grid, lds, st) : tc_launch<bf16, 2>(p, grid, lds, st); break;
     case 3: h ? tc_launch<f16, 3>(p, grid, lds, st) : tc_launch<bf16, 3>(p, grid, lds, st); break;

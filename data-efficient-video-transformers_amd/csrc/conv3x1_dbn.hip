@@ -319,9 +319,12 @@ void db_launch(const DbParams& p, int grid, int lds, hipStream_t st) {
   hipLaunchKernelGGL((conv3x1_dbn_kernel<E, NB, MODE>), dim3(grid), dim3(kNWv * 64), lds, st, p);
 }
 
+// 16-position blocks of a tile: the template parameter NB (db_plan: KP is a multiple of 32, at most kMaxRows * kHRows = 96)
+int db_nb(const Win& q) { return q.KP >> 4; }
+
 template <typename E, int MODE>
 void db_dispatch(const DbParams& p, int grid, int lds, hipStream_t st) {
-  switch (p.w_.KP >> 4) {
+  switch (db_nb(p.w_)) {
     case 2: db_launch<E, 2, MODE>(p, grid, lds, st); break;
     case 4: db_launch<E, 4, MODE>(p, grid, lds, st); break;
     default: db_launch<E, 6, MODE>(p, grid, lds, st); break;
@@ -338,6 +341,13 @@ int conv3x1_dbn_supported(int64_t N, int T, int L, int dtype) {
 #endif
   Win q;
   return N > 0 && dvt_is_16bit(dtype) && db_plan(T, L, &q) && N * q.segs < ((int64_t)1 << 31) && N * T * L * 144 < ((int64_t)1 << 31) ? 1 : 0;
+}
+
+// the launcher's instantiation: NB (2, 4, 6), 0 where the window kernel does not take the geometry
+int conv3x1_dbn_nb(int64_t N, int T, int L, int dtype) {
+  Win q;
+  if (!conv3x1_dbn_supported(N, T, L, dtype) || !db_plan(T, L, &q)) return 0;
+  return db_nb(q);
 }
 
 int conv3x1_dbn_parts(int64_t N, int T, int L) {

@@ -509,6 +509,12 @@ int dvt_conv3x1_fwd_plan(int64_t N, int T, int L, int Cin, int Cout, int dtype, 
   return 1;
 }
 
+int dvt_conv3x1_c64_plan(int64_t N, int T, int L, int dtype, int* npb) {
+  DVT_REQUIRE(npb, "dvt_conv3x1_c64_plan: npb is required");
+  *npb = dvt_internal::conv3x1_c64_npb(N, T, L, dtype);
+  return *npb != 0 ? 1 : 0;
+}
+
 int64_t dvt_conv3x1_fwd_stats_parts(int64_t N, int T, int L, int Cin) {
   if (Cin == 64) return dvt_internal::conv3x1_c64_stats_parts(N, T, L);
   Window q;

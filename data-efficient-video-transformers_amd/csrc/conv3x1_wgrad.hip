@@ -359,6 +359,15 @@ int dvt_conv3x1_wgrad_supported(int64_t N, int T, int L, int Cin, int Cout, int 
                  N * T * L < ((int64_t)1 << 31) ? 1 : 0;
 }
 
+int dvt_conv3x1_wgrad_plan(int64_t N, int T, int L, int Cin, int Cout, int dtype, int* pipelined) {
+  DVT_REQUIRE(pipelined, "dvt_conv3x1_wgrad_plan: pipelined is required");
+  *pipelined = 0;
+  if (!dvt_conv3x1_wgrad_supported(N, T, L, Cin, Cout, dtype)) return 0;
+  Window q;
+  tw_plan(T, L, &q, pipelined);                       // (the launcher's choice, as in dvt_conv3x1_wgrad)
+  return 1;
+}
+
 size_t dvt_conv3x1_wgrad_workspace_bytes(int64_t N, int T, int L) {
   Window q;
   if (N <= 0 || !tw_plan(T, L, &q)) return 0;

@@ -651,9 +651,36 @@ int params_t(StreamParams* p, Plan* pl, int64_t N, int T, int L) {
   return 1;
 }
 
+// which kernel takes dvt_conv3x1_stream_bn_bwd: the window kernel with helper waves where it takes the geometry (*nb = its
+// position blocks per tile), else the streamed-weight kernel's MODE 1 / 2 (*nb = 0)
+int bn_bwd_route(int64_t N, int T, int L, int dtype, int* nb) {
+  *nb = dvt_internal::conv3x1_dbn_nb(N, T, L, dtype);
+  return *nb ? DVT_CONV3X1_BN_BWD_WINDOW : DVT_CONV3X1_BN_BWD_STREAM;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dvt_conv3x3_stream_plan(int64_t N, int H, int W, int Cin, int Cout, int dtype, int* ci, int* co, int* groups) {
+  DVT_REQUIRE(ci && co && groups, "dvt_conv3x3_stream_plan: ci, co and groups are required");
+  *ci = *co = *groups = 0;
+  if (!dvt_conv3x3_stream_supported(N, H, W, Cin, Cout, dtype)) return 0;
+  Plan pl;
+  *groups = plan_any(Cin, Cout, H, W, &pl);          // (the launcher's: one launch per group of Cout / groups output channels)
+  *ci = Cin;
+  *co = Cout / *groups;
+  return 1;
+}
+
+int dvt_conv3x1_stream_bn_bwd_plan(int64_t N, int T, int L, int dtype, int* kernel, int* nb) {
+  DVT_REQUIRE(kernel && nb, "dvt_conv3x1_stream_bn_bwd_plan: kernel and nb are required");
+  *kernel = DVT_CONV3X1_BN_BWD_NONE;
+  *nb = 0;
+  if (!dvt_conv3x1_stream_supported(N, T, L, 64, 144, dtype)) return 0;
+  *kernel = bn_bwd_route(N, T, L, dtype, nb);
+  return 1;
+}
 
 int dvt_conv3x3_stream_supported(int64_t N, int H, int W, int Cin, int Cout, int dtype) {
   Plan pl;
@@ -749,7 +776,8 @@ int dvt_conv3x1_stream_bn_bwd(const void* dy, const void* w, const void* z, cons
   if (!dvt_conv3x1_stream_supported(N, T, L, 64, 144, dtype))
     DVT_UNSUPPORTED("dvt_conv3x1_stream_bn_bwd: needs a 16-bit dtype and a divisor of L that fills half a 224-pixel tile");
   hipStream_t st0 = (hipStream_t)stream;
-  if (dvt_internal::conv3x1_dbn_supported(N, T, L, dtype)) {
+  int nb_ = 0;
+  if (bn_bwd_route(N, T, L, dtype, &nb_) == DVT_CONV3X1_BN_BWD_WINDOW) {
     // the window kernel with helper waves (conv3x1_dbn.hip): one partial row per workgroup
     float* part0 = (float*)workspace;
     float* loc0 = part0 + (size_t)dvt_num_cus() * kNC * 2 * 144;

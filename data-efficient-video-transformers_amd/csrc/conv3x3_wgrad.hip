@@ -269,14 +269,50 @@ int cw_grid(int64_t N, int H, const CwParams& q) {
   return (int)(ntiles < dvt_num_cus() ? ntiles : dvt_num_cus());
 }
 
+// output-channel blocks of the kernel that takes a group of zcv channels (the template parameter MB)
+int cw_mb(int zcv) { return zcv > kC ? 5 : (zcv > 16 ? 4 : 1); }
+
+// The launches of a Cz-wide gradient, for the launcher and for dvt_conv3x3_c64_wgrad_plan alike: cw_groups says whether the
+// call is taken and holds the two tilings, cw_next walks the groups of dz channels -- groups of 64, the last one up to 80 wide
+// where the 160-byte gradient positions have a plan (wide_ok), else 64 + the rest.
+struct CwGroups {
+  CwParams p64, p80;    // tiling of a group of at most 64 channels / of an 80-wide last group
+  bool wide_ok;
+  int Cz;
+};
+struct CwGroup {
+  int c0, cv, mb;       // dz channels [c0, c0 + cv) on conv3x3_c64_wgrad_kernel<., mb>
+  const CwParams* p;    // its tiling
+};
+
+int cw_groups(int64_t N, int H, int W, int Cz, int dtype, CwGroups* q) {
+  if (!dvt_conv3x3_c64_wgrad_supported(N, H, W, dtype) || Cz < kC || Cz % 16) return 0;
+  plan(H, W, &q->p64);
+  q->wide_ok = plan(H, W, &q->p80, 160) != 0;              // (else the last 80 go as 64 + 16)
+  q->Cz = Cz;
+  return 1;
+}
+
+// the group that starts at channel c0; false behind the last one
+bool cw_next(const CwGroups& q, int c0, CwGroup* g) {
+  const int rem = q.Cz - c0;
+  if (rem <= 0) return false;
+  g->c0 = c0;
+  g->cv = rem > kC && rem <= 80 && q.wide_ok ? rem : (rem < kC ? rem : kC);
+  g->mb = cw_mb(g->cv);
+  g->p = g->cv > kC ? &q.p80 : &q.p64;
+  return true;
+}
+
 // one launch: channels [c0, c0 + cv) of a dz whose rows are ldz channels long, partials into p.slab
 template <typename E>
 void cw_launch(const CwParams& p, int grid, int lds, hipStream_t st) {
-  if (p.zcv > kC) {
+  const int mb = cw_mb(p.zcv);
+  if (mb == 5) {
     static DvtLdsAttr set;
     dvt_lds_attr(set, (const void*)conv3x3_c64_wgrad_kernel<E, 5>, 160 * 1024);
     hipLaunchKernelGGL((conv3x3_c64_wgrad_kernel<E, 5>), dim3(grid), dim3(kNW * 64), lds, st, p);
-  } else if (p.zcv > 16) {
+  } else if (mb == 4) {
     static DvtLdsAttr set;
     dvt_lds_attr(set, (const void*)conv3x3_c64_wgrad_kernel<E, 4>, 160 * 1024);
     hipLaunchKernelGGL((conv3x3_c64_wgrad_kernel<E, 4>), dim3(grid), dim3(kNW * 64), lds, st, p);
@@ -297,16 +333,14 @@ int cw_run(const void* x, const void* dz, float* dw, void* workspace, int64_t N,
   DVT_REQUIRE(dvt_aligned16(x) && dvt_aligned16(dz) && dvt_aligned16(dw) && dvt_aligned16(workspace),
               "%s: buffers must be 16-byte aligned", who);
   DVT_REQUIRE(!defer_reduce || pending, "%s: defer_reduce needs a pending descriptor to fill", who);
-  CwParams p64, p80;
-  if (!dvt_conv3x3_c64_wgrad_supported(N, H, W, dtype) || Cz < 64 || Cz % 16)
+  CwGroups groups;
+  if (!cw_groups(N, H, W, Cz, dtype, &groups))
     DVT_UNSUPPORTED("%s: needs a 16-bit dtype, Cout >= 64 in steps of 16 and two (patch + gradient tile) pairs in 160 KiB of LDS", who);
-  plan(H, W, &p64);
-  const bool wide_ok = plan(H, W, &p80, 160) != 0;        // (else the last 80 go as 64 + 16)
   hipStream_t st = (hipStream_t)stream;
-  for (int c0 = 0; c0 < Cz;) {
-    const int rem = Cz - c0;
-    const int cv = rem > kC && rem <= 80 && wide_ok ? rem : (rem < kC ? rem : kC);
-    CwParams p = cv > kC ? p80 : p64;
+  CwGroup grp;
+  for (int c0 = 0; cw_next(groups, c0, &grp);) {
+    const int cv = grp.cv;
+    CwParams p = *grp.p;
     p.x = x; p.dz = dz; p.slab = (float*)workspace;
     p.N = (int)N; p.H = H; p.W = W; p.ldz = Cz;
     p.tiles_per_img = (int)dvt_cdiv(H, p.R);
@@ -341,6 +375,19 @@ extern "C" {
 int dvt_conv3x3_c64_wgrad_supported(int64_t N, int H, int W, int dtype) {
   CwParams q;
   return N > 0 && dvt_is_16bit(dtype) && plan(H, W, &q) && N * H * W < ((int64_t)1 << 31) ? 1 : 0;
+}
+
+int dvt_conv3x3_c64_wgrad_plan(int64_t N, int H, int W, int Cout, int dtype, int max_launches, int* c0, int* width, int* mb,
+                               int* rows) {
+  DVT_REQUIRE(max_launches >= 0 && (max_launches == 0 || (c0 && width && mb && rows)),
+              "dvt_conv3x3_c64_wgrad_plan: c0, width, mb and rows are required");
+  CwGroups groups;
+  if (!cw_groups(N, H, W, Cout, dtype, &groups)) return 0;
+  CwGroup g;
+  int n = 0;
+  for (int at = 0; cw_next(groups, at, &g); at += g.cv, ++n)
+    if (n < max_launches) { c0[n] = g.c0; width[n] = g.cv; mb[n] = g.mb; rows[n] = g.p->R; }
+  return n;
 }
 
 size_t dvt_conv3x3_c64_wgrad_workspace_bytes(int64_t N, int H, int W) {

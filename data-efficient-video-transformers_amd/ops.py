@@ -1699,6 +1699,75 @@ def conv3x1_fwd_plan(N: int, T: int, Lp: int, dtype: torch.dtype):
     return (npb.value, bool(pipe.value)) if rc == 1 else None
 
 
+def conv3x1_c64_plan(N: int, T: int, Lp: int, dtype: torch.dtype) -> Optional[int]:
+    """Position blocks per wave (the NPB of conv3x1_c64_kernel) dvt_conv3x1_fwd launches for the 64 -> 64 form; None where it
+    does not take the geometry.  Host only."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        return None
+    npb = C.c_int()
+    rc = L.load().dvt_conv3x1_c64_plan(N, T, Lp, _DT[dtype], C.byref(npb))
+    L.check(min(rc, 0), "dvt_conv3x1_c64_plan")
+    return npb.value if rc == 1 else None
+
+
+def conv3x1_wgrad_plan(N: int, T: int, Lp: int, dtype: torch.dtype) -> Optional[bool]:
+    """Whether dvt_conv3x1_wgrad launches the pipelined kernel (conv3x1_wgrad_pipe_kernel) for this geometry; None where it
+    does not take it.  Host only."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        return None
+    pipe = C.c_int()
+    rc = L.load().dvt_conv3x1_wgrad_plan(N, T, Lp, 144, 64, _DT[dtype], C.byref(pipe))
+    L.check(min(rc, 0), "dvt_conv3x1_wgrad_plan")
+    return bool(pipe.value) if rc == 1 else None
+
+
+class BnBwdPlan(NamedTuple):
+    kernel: str      # "window": conv3x1_dbn_kernel<., nb, 1 | 2>; "stream": conv3x3_stream_kernel<., 64, 144, 3, 1 | 2>
+    nb: int          # window: 16-position blocks per tile (2, 4, 6); stream: 0
+
+
+def conv3x1_stream_bn_bwd_plan(N: int, T: int, HW: int, dtype: torch.dtype) -> Optional[BnBwdPlan]:
+    """Which kernel pair takes dvt_conv3x1_stream_bn_bwd for this geometry; None where it is refused.  Host only."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        return None
+    kern, nb = C.c_int(), C.c_int()
+    rc = L.load().dvt_conv3x1_stream_bn_bwd_plan(N, T, HW, _DT[dtype], C.byref(kern), C.byref(nb))
+    L.check(min(rc, 0), "dvt_conv3x1_stream_bn_bwd_plan")
+    names = {v: k[len("DVT_CONV3X1_BN_BWD_"):].lower() for k, v in L.ENUMS["dvt_conv3x1_bn_bwd_kernel"].items()}
+    return BnBwdPlan(names[kern.value], nb.value) if rc == 1 else None
+
+
+def conv3x3_c64_wgrad_plan(N: int, H: int, W: int, Cout: int, dtype: torch.dtype, *, rows: bool = False):
+    """The launches of conv3x3_c64_wgrad: ((first dz channel, channels, MB of conv3x3_c64_wgrad_kernel), ...) -- with
+    ``rows``, a fourth entry: the output rows of a frame per tile --; None where the call is refused.  Host only."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        return None
+    lib = L.load()
+    n = int(lib.dvt_conv3x3_c64_wgrad_plan(N, H, W, Cout, _DT[dtype], 0, None, None, None, None))
+    L.check(min(n, 0), "dvt_conv3x3_c64_wgrad_plan")
+    if n == 0:
+        return None
+    c0, cv, mb, r = ((C.c_int * n)() for _ in range(4))
+    assert int(lib.dvt_conv3x3_c64_wgrad_plan(N, H, W, Cout, _DT[dtype], n, c0, cv, mb, r)) == n
+    return tuple(zip(c0, cv, mb, r)) if rows else tuple(zip(c0, cv, mb))
+
+
+class StreamPlan(NamedTuple):
+    ci: int          # conv3x3_stream_kernel<., ci, co, 9, 0>
+    co: int
+    groups: int      # launches (groups of co output channels)
+
+
+def conv3x3_stream_plan(N: int, H: int, W: int, Cin: int, Cout: int, dtype: torch.dtype) -> Optional[StreamPlan]:
+    """The instantiation dvt_conv3x3_stream launches and how many times; None where the call is refused.  Host only."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        return None
+    ci, co, groups = C.c_int(), C.c_int(), C.c_int()
+    rc = L.load().dvt_conv3x3_stream_plan(N, H, W, Cin, Cout, _DT[dtype], C.byref(ci), C.byref(co), C.byref(groups))
+    L.check(min(rc, 0), "dvt_conv3x3_stream_plan")
+    return StreamPlan(ci.value, co.value, groups.value) if rc == 1 else None
+
+
 def conv3x1_fwd_supported(x: Tensor, wp: Tensor, N: int, T: int, Lp: int, Cin: int, Cout: int) -> bool:
     if not x.is_cuda or x.dtype not in (torch.bfloat16, torch.float16) or wp.dtype != x.dtype:
         return False

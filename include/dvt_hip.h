@@ -724,6 +724,12 @@ int dvt_conv3x3_c64_wgrad(const void* x, const void* dz, float* dw, void* worksp
  * dvt_conv3x3_c64_wgrad_workspace_bytes reports covers the widest group); defer_reduce defers the LAST group's reduce. */
 int dvt_conv3x3_c64_wgrad_wide(const void* x, const void* dz, float* dw, void* workspace, int64_t N, int H, int W, int Cout,
                                int accumulate, int defer_reduce, dvt_splitk_pending* pending, int dtype, dvt_stream_t stream);
+/* The launches of dvt_conv3x3_c64_wgrad (Cout = 64) / _wide (host only): launch i takes the dz channels [c0[i], c0[i] + width[i])
+ * on conv3x3_c64_wgrad_kernel<., mb[i]> (mb = 5: an 80-wide last group, 4: up to 64 channels, 1: a 16-channel tail) in tiles
+ * of rows[i] whole output rows of a frame.  Returns the number of launches -- the first max_launches are written --, 0 where
+ * the call is refused. */
+int dvt_conv3x3_c64_wgrad_plan(int64_t N, int H, int W, int Cout, int dtype, int max_launches, int* c0, int* width, int* mb,
+                               int* rows);
 /* The temporal half of R(2+1)D-18's layer-1 Conv2Plus1D (torchvision r2plus1d_18 as used by frame_transformer.py:64-74: a
  * (3, 1, 1) convolution, 144 mid planes -> 64, stride 1, pad 1) from LDS-resident sliding windows: a workgroup stages a
  * segment of S pixels of one clip over all T + 2 frames once and the three taps read it at three position offsets.
@@ -751,9 +757,15 @@ int64_t dvt_conv3x1_fwd_stats_parts(int64_t N, int T, int L, int Cin);
  * (1 .. 6, the template parameter of conv3x1_fwd_kernel / conv3x1_fwd_pipe_kernel), *pipelined = 1 for the form with helper
  * waves.  Returns 1, or 0 (both outputs 0) where dvt_conv3x1_fwd_supported refuses the geometry or Cin != 144 (since ABI v5). */
 int dvt_conv3x1_fwd_plan(int64_t N, int T, int L, int Cin, int Cout, int dtype, int* npb, int* pipelined);
+/* The same for the 64 -> 64 form (conv3x1_c64_kernel): *npb = 16-position blocks per wave (1 .. 6).  Returns 1, or 0 (*npb 0)
+ * where the geometry is not taken. */
+int dvt_conv3x1_c64_plan(int64_t N, int T, int L, int dtype, int* npb);
 int dvt_conv3x1_fwd(const void* x, const dvt_bn_affine* x_affine, const void* w, int64_t ldw, void* y, float* stats_partial,
                     int64_t N, int T, int L, int Cin, int dtype, dvt_stream_t stream);
 int dvt_conv3x1_wgrad_supported(int64_t N, int T, int L, int Cin, int Cout, int dtype);
+/* Which kernel dvt_conv3x1_wgrad launches (host only): *pipelined = 1 for conv3x1_wgrad_pipe_kernel (three buffer pairs, helper
+ * waves), 0 for conv3x1_wgrad_kernel.  Returns 1, or 0 where dvt_conv3x1_wgrad_supported refuses the geometry. */
+int dvt_conv3x1_wgrad_plan(int64_t N, int T, int L, int Cin, int Cout, int dtype, int* pipelined);
 size_t dvt_conv3x1_wgrad_workspace_bytes(int64_t N, int T, int L);
 int dvt_conv3x1_wgrad(const void* x, const dvt_bn_affine* x_affine, const void* dz, float* dw, void* workspace, int64_t N, int T,
                       int L, int accumulate, int defer_reduce, dvt_splitk_pending* pending, int dtype, dvt_stream_t stream);
@@ -779,6 +791,10 @@ int dvt_conv3x3_c64(const void* x, const void* w, void* y, float* stats_partial,
  * Cout = 144 / 288, [dvt_conv3x3_stream_stats_parts + 64][2][Cout]; residual: only with Cout = 64 / 128. */
 int dvt_conv3x3_stream_supported(int64_t N, int H, int W, int Cin, int Cout, int dtype);
 int64_t dvt_conv3x3_stream_stats_parts(int64_t N, int H, int W, int Cin, int Cout);
+/* Which instantiation dvt_conv3x3_stream launches (host only): conv3x3_stream_kernel<., *ci, *co, 9, 0>, once per group of
+ * *co output channels (*groups launches: 2 for the layer-2 pairs).  Returns 1, or 0 (all outputs 0) where
+ * dvt_conv3x3_stream_supported refuses the call. */
+int dvt_conv3x3_stream_plan(int64_t N, int H, int W, int Cin, int Cout, int dtype, int* ci, int* co, int* groups);
 int dvt_conv3x3_stream(const void* x, const void* w, void* y, float* stats_partial, const void* residual, int64_t N, int H, int W,
                        int Cin, int Cout, int dtype, dvt_stream_t stream);
 /* The (3, 1) sibling over the [T, L] view of N clips (L = H * W pixels per frame; rows of the "image" are L pixels apart): the
@@ -798,6 +814,16 @@ size_t dvt_conv3x1_stream_bn_bwd_workspace_bytes(int64_t N, int T, int L);
 int dvt_conv3x1_stream_bn_bwd(const void* dy, const void* w, const void* z, const dvt_bn_affine* bn, void* dz, float* dgamma,
                               float* dbeta, void* workspace, int64_t N, int T, int L, int training, int accumulate, int dtype,
                               dvt_stream_t stream);
+/* Which kernel pair takes dvt_conv3x1_stream_bn_bwd (host only): the window kernel with helper waves
+ * conv3x1_dbn_kernel<., *nb, 1 | 2> where it takes the geometry (*nb = 16-position blocks per tile: 2, 4 or 6), else the
+ * streamed-weight kernel conv3x3_stream_kernel<., 64, 144, 3, 1 | 2> (*nb = 0).  Returns 1, or 0 (kernel NONE) where
+ * dvt_conv3x1_stream_supported refuses the geometry. */
+enum dvt_conv3x1_bn_bwd_kernel {
+  DVT_CONV3X1_BN_BWD_NONE = 0,
+  DVT_CONV3X1_BN_BWD_WINDOW = 1,
+  DVT_CONV3X1_BN_BWD_STREAM = 2
+};
+int dvt_conv3x1_stream_bn_bwd_plan(int64_t N, int T, int L, int dtype, int* kernel, int* nb);
 int dvt_conv2d_implicit_supported(const dvt_conv_desc* desc);
 /* Row length K of the packed weights w[Cout][K] the forward call expects: kh*kw*C -- rounded up to the kernel's k-tile in
  * the stem form C == 8 (the columns past kh*kw*8 must be zero: dvt_conv_weight_pack with ld = K writes them so). */

@@ -17,6 +17,10 @@ Weight gradient: dW[co, c, ki, kj] = sum_{n, ho, wo} dz[n, ho, wo, co] x[n, ho*s
 reduction runs over output pixels, so the sparse operand is dz ALONG THE PIXEL AXIS (per column and 16 pixels one nonzero)
 and the map is dense: every 32- / 64-pixel k-tile counts, the ragged last one included.
 
+The hand-written LDS-window kernels (tests/test_gpu_window_conv_exact.py, tests/test_window_conv_coverage.py) split the
+reduction otherwise -- 32-channel steps, 32 + 16 in 48-channel chunks, a whole filter row of the stem --: kstep_operands keeps
+the map and gives the weights the sign of the KERNEL's k-step, so that no step cancels itself.
+
 The references are torch.nn.functional.conv2d in float64 and its two adjoints written out tap by tap in float64.
 """
 import torch
@@ -75,6 +79,44 @@ def forward_operands(N, C, H, W, Cout, k, seed):
     kh, kw = pair(k)
     deep = is_deep(C, kh, kw)
     return sparse_map(N * H * W, C, seed, deep).view(N, H, W, C), signed_weights(Cout, C, kh, kw, seed + 1, deep)
+
+
+def kstep_signs(kh, kw, C, ranges, tap_group=None):
+    """[kh * kw, C] +-1 for a kernel whose k-step is (tap group, channel range of `ranges`): the sign of step
+    group * len(ranges) + j flips every two steps, and is constant over a step, so no k-step cancels itself.  tap_group(ki, kj)
+    joins taps that share a k-step (the stem kernel: a whole filter row); default: every tap its own."""
+    s = torch.ones(kh * kw, C, dtype=torch.float64)
+    for tap in range(kh * kw):
+        grp = tap if tap_group is None else tap_group(tap // kw, tap % kw)
+        for j, (lo, hi) in enumerate(ranges):
+            if ((grp * len(ranges) + j) // 2) % 2:
+                s[tap, lo:hi] = -1.0
+    return s
+
+
+def kstep_operands(N, C, H, W, Cout, k, seed, ranges, tap_group=None, valid=None, deep=None):
+    """forward_operands for the hand-written window kernels, whose k-steps are not 16 channels wide: the map keeps one nonzero
+    per pixel and 16-channel range (so every 16-byte slot matters), the weights take the sign of their k-step (kstep_signs).
+    valid: channels that exist (the rest of the C stored ones are zero in the map AND in the weights: a zero-padded layer).
+    -> (x [N, H, W, C], w [Cout, C, kh, kw]) float64"""
+    kh, kw = pair(k)
+    valid = valid or C
+    assert ranges[-1][1] == valid and all(a[1] == b[0] for a, b in zip(ranges, ranges[1:]))
+    deep = is_deep(valid, kh, kw) if deep is None else deep
+    x = torch.zeros(N * H * W, C, dtype=torch.float64)
+    x[:, :valid] = sparse_map(N * H * W, valid, seed, deep)
+    w = X.dense(Cout, kh * kw * C, seed + 1).view(Cout, kh * kw, C)
+    if deep:
+        w = w.clamp(max=2.0)
+    w = w * kstep_signs(kh, kw, C, ranges, tap_group).unsqueeze(0)
+    w[:, :, valid:] = 0.0
+    return x.view(N, H, W, C), w.permute(0, 2, 1).reshape(Cout, C, kh, kw).contiguous()
+
+
+def adjoint_weights(wd):
+    """the layer's parameter whose DATA GRADIENT is the convolution with wd [Cin, Cout, kh, kw] (stride 1, same padding):
+    w[co, ci, ki, kj] = wd[ci, co, kh - 1 - ki, kw - 1 - kj]"""
+    return wd.flip(2, 3).permute(1, 0, 2, 3).contiguous()
 
 
 def wgrad_operands(N, C, H, W, Cout, k, stride, pad, seed, trim_w=0):

@@ -99,6 +99,33 @@ def test_version_and_error_channel_without_gpu():
     assert rc == -1
 
 
+def test_window_convolution_plan_queries_answer_without_a_gpu():
+    """dvt_conv3x1_c64_plan, dvt_conv3x1_wgrad_plan, dvt_conv3x1_stream_bn_bwd_plan, dvt_conv3x3_c64_wgrad_plan and
+    dvt_conv3x3_stream_plan: host-only, declared in the header, wrapped in ops as tuples; they report the layer-1 workload's
+    instantiations and refuse what the launchers refuse (tests/test_window_conv_coverage.py sweeps them)."""
+    import dvt_amd
+    from dvt_amd import ops
+    declared = _declared()
+    for n in ("dvt_conv3x1_c64_plan", "dvt_conv3x1_wgrad_plan", "dvt_conv3x1_stream_bn_bwd_plan", "dvt_conv3x3_c64_wgrad_plan",
+              "dvt_conv3x3_stream_plan"):
+        assert n in declared and n in dvt_amd._lib.SIGNATURES
+    assert dvt_amd._lib.ENUMS["dvt_conv3x1_bn_bwd_kernel"] == {"DVT_CONV3X1_BN_BWD_NONE": 0, "DVT_CONV3X1_BN_BWD_WINDOW": 1,
+                                                               "DVT_CONV3X1_BN_BWD_STREAM": 2}
+    bf = torch.bfloat16
+    # R(2+1)D-18 layer 1 at 28 clips of 12 x 56 x 56, ResNet-18 layer 1 at 256 frames of 56 x 56
+    assert ops.conv3x1_c64_plan(28, 12, 3136, bf) == 6
+    assert ops.conv3x1_stream_bn_bwd_plan(28, 12, 3136, bf) == ops.BnBwdPlan("window", 6)
+    assert ops.conv3x1_wgrad_plan(28, 12, 3136, bf) is True
+    assert ops.conv3x3_c64_wgrad_plan(256, 56, 56, 64, bf) == ((0, 64, 4),)
+    assert ops.conv3x3_c64_wgrad_plan(336, 56, 56, 144, bf) == ((0, 64, 4), (64, 80, 5))
+    assert ops.conv3x3_stream_plan(336, 56, 56, 64, 144, bf) == ops.StreamPlan(64, 144, 1)
+    assert ops.conv3x3_stream_plan(336, 28, 28, 288, 128, bf) == ops.StreamPlan(288, 64, 2)
+    for plan in (ops.conv3x1_c64_plan(3, 5, 32, bf), ops.conv3x1_wgrad_plan(3, 5, 32, bf), ops.conv3x1_stream_bn_bwd_plan(2, 2, 32, bf),
+                 ops.conv3x3_c64_wgrad_plan(2, 13, 20, 72, bf), ops.conv3x3_stream_plan(2, 13, 20, 64, 64, bf),
+                 ops.conv3x1_c64_plan(28, 12, 3136, torch.float32)):
+        assert plan is None
+
+
 def test_vivit_surface_matches_reference_state_dict():
     from dvt_amd.models.vit import ViViT, Transformer, Attention, FeedForward, PreNorm
     from tests.util import golden
