@@ -1,5 +1,6 @@
 // optim.hip -- every optimizer step: AdamW (host step, device step, fused flat-buffer step with mirror, loss-scaled),
-// torch.optim.Adam with coupled decay, SGD, Adagrad.  All are streaming kernels over fp32 master weights.
+// torch.optim.Adam with coupled decay, SGD, Adagrad -- streaming kernels over fp32 master weights -- and LARS, whose
+// per-tensor norms make it a reduction over a table of segments followed by the scaled momentum update.
 //
 // The Adam update, its bias correction, the step-counter ticket and the mirror dispatch are each stated once, below;
 // the kernels differ only in their launch contract (scalar grid-stride or four elements per thread, mirror, ticket,
@@ -247,6 +248,220 @@ __global__ void adagrad_kernel(float* __restrict__ p, const float* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------ LARS (pl_bolts.optimizers.lars.LARS.step)
+// A device table of segments (dvt_lars_seg, one per tensor with a gradient), cut into chunks of kLarsChunk elements: a
+// chunk lies in one segment, segment s owns the chunks [chunk_begin[s], chunk_begin[s] + cdiv(numel, kLarsChunk)), and one
+// block works on one chunk in both kernels.  Inside a chunk thread t owns the quads t, t + 256, ... (elements 4q .. 4q + 3),
+// read as one 16-byte access when every pointer of the segment allows it and as four scalars otherwise; the last
+// len & 3 elements go to the threads 0 .. 2.  Ownership, and with it the order of every sum, depends on numel alone.
+constexpr int kLarsChunk = 8192;
+constexpr int kLarsBlock = 256;
+
+// The segment that owns chunk `c`: the last one whose chunk_begin is <= c (chunk_begin ascends strictly).
+__device__ __forceinline__ int lars_find_segment(const dvt_lars_seg* __restrict__ table, int n, int64_t c) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[mid].chunk_begin <= c) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Elements of the chunk that begins at `start`.  A block past the table's last chunk (the caller's `chunks` larger than
+// the table's own total) resolves to the last segment with start >= numel: it gets 0, so it reads and writes no element.
+__device__ __forceinline__ int lars_chunk_len(int64_t numel, int64_t start) {
+  const int64_t left = numel - start;
+  return left <= 0 ? 0 : (int)(left < kLarsChunk ? left : kLarsChunk);
+}
+
+// The table holds device addresses: they are read as global memory (a generic pointer would compile to FLAT accesses).
+#define DVT_GLOBAL __attribute__((address_space(1)))
+typedef DVT_GLOBAL float gfloat;
+template <typename T>
+__device__ __forceinline__ DVT_GLOBAL T* lars_global(const void* p) { return (DVT_GLOBAL T*)(uintptr_t)p; }
+
+template <bool kVec>
+__device__ __forceinline__ f32x4 lars_load4(const gfloat* p) {
+  if (kVec) return *(const DVT_GLOBAL f32x4*)p;
+  return f32x4{p[0], p[1], p[2], p[3]};
+}
+
+template <bool kVec>
+__device__ __forceinline__ void lars_store4(gfloat* p, f32x4 v) {
+  if (kVec) *(DVT_GLOBAL f32x4*)p = v;
+  else { p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3]; }
+}
+
+// Sum of (a, b) over the block in a fixed order: the xor butterfly inside each wave, then the waves in index order.
+// Every thread returns the same pair.
+__device__ __forceinline__ f32x2 lars_block_sum(float a, float b) {
+  __shared__ float red[2][kLarsBlock / DVT_WAVE];
+#pragma unroll
+  for (int off = DVT_WAVE / 2; off > 0; off >>= 1) {
+    a += __shfl_xor(a, off, DVT_WAVE);
+    b += __shfl_xor(b, off, DVT_WAVE);
+  }
+  __syncthreads();                                      // the previous use of `red` is over
+  if ((threadIdx.x & (DVT_WAVE - 1)) == 0) {
+    red[0][threadIdx.x / DVT_WAVE] = a;
+    red[1][threadIdx.x / DVT_WAVE] = b;
+  }
+  __syncthreads();
+  a = red[0][0]; b = red[1][0];
+#pragma unroll
+  for (int w = 1; w < kLarsBlock / DVT_WAVE; ++w) { a += red[0][w]; b += red[1][w]; }
+  return f32x2{a, b};
+}
+
+template <bool kVec>
+__device__ __forceinline__ void lars_chunk_sumsq(const gfloat* __restrict__ p, const gfloat* __restrict__ g, int len,
+                                                 float& sp, float& sg) {
+  const int n4 = len >> 2;
+  for (int q = threadIdx.x; q < n4; q += kLarsBlock) {
+    const f32x4 pv = lars_load4<kVec>(p + 4 * q), gv = lars_load4<kVec>(g + 4 * q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { sp = fmaf(pv[k], pv[k], sp); sg = fmaf(gv[k], gv[k], sg); }
+  }
+  if ((int)threadIdx.x < (len & 3)) {
+    const float pi = p[4 * n4 + threadIdx.x], gi = g[4 * n4 + threadIdx.x];
+    sp = fmaf(pi, pi, sp); sg = fmaf(gi, gi, sg);
+  }
+}
+
+// partial[c] = (sum p^2, sum g^2) of chunk c.
+__global__ __launch_bounds__(kLarsBlock) void lars_norms_kernel(const dvt_lars_seg* __restrict__ table, int n,
+                                                                f32x2* __restrict__ partial) {
+  const int64_t c = blockIdx.x;
+  const dvt_lars_seg s = table[lars_find_segment(table, n, c)];
+  const int64_t start = (c - s.chunk_begin) * kLarsChunk;
+  const int len = lars_chunk_len(s.numel, start);
+  const gfloat* p = lars_global<float>(s.param) + start;
+  const gfloat* g = lars_global<float>(s.grad) + start;
+  float sp = 0.f, sg = 0.f;
+  if ((((uintptr_t)p | (uintptr_t)g) & 15u) == 0) lars_chunk_sumsq<true>(p, g, len, sp, sg);
+  else lars_chunk_sumsq<false>(p, g, len, sp, sg);
+  const f32x2 r = lars_block_sum(sp, sg);
+  if (threadIdx.x == 0) partial[c] = r;
+}
+
+// (sum p^2, sum g^2) of a whole segment from its chunks' partials: thread t adds the partials t, t + 256, ... in that
+// order, lars_block_sum adds the threads.  The one statement of this sum: dvt_lars_sumsq reports what dvt_lars_step uses.
+__device__ __forceinline__ f32x2 lars_segment_sumsq(const f32x2* __restrict__ partial, const dvt_lars_seg& s) {
+  const int64_t chunks = (s.numel + kLarsChunk - 1) / kLarsChunk;
+  float sp = 0.f, sg = 0.f;
+  for (int64_t i = threadIdx.x; i < chunks; i += kLarsBlock) {
+    const f32x2 v = partial[s.chunk_begin + i];
+    sp += v[0]; sg += v[1];
+  }
+  return lars_block_sum(sp, sg);
+}
+
+__global__ __launch_bounds__(kLarsBlock) void lars_reduce_kernel(const dvt_lars_seg* __restrict__ table,
+                                                                 const f32x2* __restrict__ partial, f32x2* __restrict__ out) {
+  const f32x2 r = lars_segment_sumsq(partial, table[blockIdx.x]);
+  if (threadIdx.x == 0) out[blockIdx.x] = r;
+}
+
+struct LarsCoef {
+  float q, wd, mu, keep, lr;          // d = q (g + wd p); buf = mu buf + keep d
+  bool scaled, first, nesterov;
+};
+
+// One element of LARS.  Without trust scaling (weight_decay == 0 or a zero norm) d is the raw gradient: no decay either.
+// `first`: buf = d itself, not (1 - dampening) d.
+__device__ __forceinline__ void lars_update(float& p, float g, float& buf, const LarsCoef& c) {
+  float d = c.scaled ? c.q * fmaf(c.wd, p, g) : g;
+  if (c.mu != 0.f) {
+    buf = c.first ? d : fmaf(c.mu, buf, c.keep * d);
+    d = c.nesterov ? fmaf(c.mu, buf, d) : buf;
+  }
+  p -= c.lr * d;
+}
+
+template <bool kVec, typename M>
+__device__ __forceinline__ void lars_chunk_update(gfloat* __restrict__ p, const gfloat* __restrict__ g,
+                                                  gfloat* __restrict__ buf, DVT_GLOBAL M* __restrict__ mirror, int len,
+                                                  const LarsCoef& c) {
+  typedef M m4 __attribute__((ext_vector_type(4)));
+  constexpr bool kMirror = !std::is_same<M, float>::value;
+  const bool mom = c.mu != 0.f;
+  const int n4 = len >> 2;
+  for (int q = threadIdx.x; q < n4; q += kLarsBlock) {
+    const int e = 4 * q;
+    f32x4 pv = lars_load4<kVec>(p + e), bv = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 gv = lars_load4<kVec>(g + e);
+    if (mom && !c.first) bv = lars_load4<kVec>(buf + e);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pi = pv[k], bi = bv[k];
+      lars_update(pi, gv[k], bi, c);
+      pv[k] = pi; bv[k] = bi;
+    }
+    lars_store4<kVec>(p + e, pv);
+    if (mom) lars_store4<kVec>(buf + e, bv);
+    if (kMirror) {
+      if (kVec) {
+        m4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = (M)pv[k];
+        *(DVT_GLOBAL m4*)(mirror + e) = o;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mirror[e + k] = (M)pv[k];
+      }
+    }
+  }
+  if ((int)threadIdx.x < (len & 3)) {
+    const int i = 4 * n4 + threadIdx.x;
+    float pi = p[i], bi = (mom && !c.first) ? buf[i] : 0.f;
+    lars_update(pi, g[i], bi, c);
+    p[i] = pi;
+    if (mom) buf[i] = bi;
+    if (kMirror) mirror[i] = (M)pi;
+  }
+}
+
+// The update of one chunk: its segment's norms from the partials, q, then the rule.  lr and the step counter (int64[2],
+// publish_step) are read on the device; the counter only tells the first step from the later ones.
+template <typename M>
+__global__ __launch_bounds__(kLarsBlock) void lars_update_kernel(const dvt_lars_seg* __restrict__ table, int n,
+                                                                 const f32x2* __restrict__ partial,
+                                                                 const float* __restrict__ lr_dev, float mu, float dampening,
+                                                                 int nesterov, float trust, float eps, int64_t* step_dev,
+                                                                 M* /* tag: the mirrors' type */) {
+  const int64_t steps = step_dev[0];
+  const int64_t c = blockIdx.x;
+  const dvt_lars_seg s = table[lars_find_segment(table, n, c)];
+  const f32x2 ss = lars_segment_sumsq(partial, s);
+  const float pn = sqrtf(ss[0]), gn = sqrtf(ss[1]);
+  LarsCoef k;
+  k.scaled = s.weight_decay != 0.f && pn != 0.f && gn != 0.f;
+  k.q = k.scaled ? trust * pn / (gn + s.weight_decay * pn + eps) : 1.f;
+  k.wd = s.weight_decay; k.mu = mu; k.keep = 1.f - dampening; k.lr = lr_dev[0];
+  k.first = steps == 0; k.nesterov = nesterov != 0;
+  const int64_t start = (c - s.chunk_begin) * kLarsChunk;
+  const int len = lars_chunk_len(s.numel, start);
+  gfloat* p = lars_global<float>(s.param) + start;
+  const gfloat* g = lars_global<float>(s.grad) + start;
+  gfloat* buf = mu != 0.f ? lars_global<float>(s.buf) + start : nullptr;
+  DVT_GLOBAL M* mirror = std::is_same<M, float>::value ? nullptr : lars_global<M>(s.mirror) + start;
+  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15u) == 0 && ((uintptr_t)mirror & 7u) == 0;
+  if (vec) lars_chunk_update<true, M>(p, g, buf, mirror, len, k);
+  else lars_chunk_update<false, M>(p, g, buf, mirror, len, k);
+  publish_step(step_dev, steps);
+}
+
+inline int64_t lars_total_chunks(const int64_t* numel, int n, int64_t* chunk_begin) {
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (chunk_begin) chunk_begin[i] = total;
+    total += dvt_cdiv(numel[i], kLarsChunk);
+  }
+  if (chunk_begin) chunk_begin[n] = total;
+  return total;
+}
+
 }  // namespace
 
 extern "C" {
@@ -350,6 +565,52 @@ int dvt_adagrad_step(float* param, const float* grad, float* state_sum, int64_t 
   hipLaunchKernelGGL(adagrad_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, param, grad, state_sum,
                      n, clr, eps, weight_decay, skip64);
   DVT_LAUNCH_CHECK("dvt_adagrad_step");
+  return DVT_OK;
+}
+
+int dvt_lars_plan(const int64_t* numel, int n, dvt_lars_plan_info* info, int64_t* chunk_begin) {
+  DVT_REQUIRE(info && n >= 0 && (numel || n == 0), "dvt_lars_plan: bad arguments");
+  for (int i = 0; i < n; ++i) DVT_REQUIRE(numel[i] > 0, "dvt_lars_plan: every segment needs at least one element");
+  const int64_t total = lars_total_chunks(numel, n, chunk_begin);
+  DVT_REQUIRE(total <= 0x7fffffffll, "dvt_lars_plan: more chunks than one grid holds");
+  info->chunk = kLarsChunk;
+  info->blocks = total;
+  info->grid_cap = 0;                              // one block per chunk, no grid-stride loop
+  info->workspace_bytes = total * (int64_t)sizeof(f32x2);
+  return DVT_OK;
+}
+
+int dvt_lars_sumsq(const dvt_lars_seg* table, int n, int64_t chunks, float* workspace, float* sumsq,
+                   dvt_stream_t stream) {
+  DVT_REQUIRE(n >= 0 && chunks >= 0 && chunks <= 0x7fffffffll, "dvt_lars_sumsq: bad sizes");
+  if (n == 0) return DVT_OK;
+  DVT_REQUIRE(table && workspace && sumsq && chunks >= n, "dvt_lars_sumsq: bad arguments");
+  DVT_REQUIRE(((uintptr_t)workspace & 7u) == 0 && ((uintptr_t)sumsq & 7u) == 0, "dvt_lars_sumsq: buffers must be 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(lars_norms_kernel, dim3((unsigned)chunks), dim3(kLarsBlock), 0, st, table, n, (f32x2*)workspace);
+  hipLaunchKernelGGL(lars_reduce_kernel, dim3((unsigned)n), dim3(kLarsBlock), 0, st, table, (const f32x2*)workspace,
+                     (f32x2*)sumsq);
+  DVT_LAUNCH_CHECK("dvt_lars_sumsq");
+  return DVT_OK;
+}
+
+int dvt_lars_step(const dvt_lars_seg* table, int n, int64_t chunks, float* workspace, const float* lr_dev, float momentum,
+                  float dampening, int nesterov, float trust_coefficient, float eps, int64_t* step_dev2, int mirror,
+                  int mirror_dtype, dvt_stream_t stream) {
+  DVT_REQUIRE(n >= 0 && chunks >= 0 && chunks <= 0x7fffffffll, "dvt_lars_step: bad sizes");
+  if (n == 0) return DVT_OK;
+  DVT_REQUIRE(table && workspace && lr_dev && step_dev2 && chunks >= n, "dvt_lars_step: bad arguments");
+  DVT_REQUIRE(((uintptr_t)workspace & 7u) == 0, "dvt_lars_step: workspace must be 8-byte aligned");
+  DVT_REQUIRE(!mirror || dvt_is_16bit(mirror_dtype), "dvt_lars_step: mirror must be bf16 / f16");
+  DVT_REQUIRE(momentum >= 0.f && (!nesterov || (momentum > 0.f && dampening == 0.f)),
+              "dvt_lars_step: nesterov needs momentum > 0 and dampening == 0");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)chunks), block(kLarsBlock);
+  hipLaunchKernelGGL(lars_norms_kernel, grid, block, 0, st, table, n, (f32x2*)workspace);
+  void* tag = mirror ? (void*)workspace : nullptr;      // non-null selects the 16-bit instantiation; never dereferenced
+  DVT_LAUNCH_MIRRORED(lars_update_kernel, tag, mirror_dtype, grid, block, st, table, n, (const f32x2*)workspace, lr_dev,
+                      momentum, dampening, nesterov, trust_coefficient, eps, step_dev2);
+  DVT_LAUNCH_CHECK("dvt_lars_step");
   return DVT_OK;
 }
 

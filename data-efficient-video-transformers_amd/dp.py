@@ -493,16 +493,63 @@ class FlatParameters:
         The bias-correction count is global, as in ``adamw_step``."""
         if self.exp_avg is None:
             self.init_optimizer_state()
-        if not isinstance(lr, torch.Tensor):
-            if getattr(self, "_lr_dev", None) is None:
-                self._lr_dev, self._lr_host = torch.full((1,), float(lr), dtype=torch.float32, device=self.data.device), lr
-            elif self._lr_host != lr:
-                self._lr_dev.fill_(float(lr))
-                self._lr_host = lr
-            lr = self._lr_dev
+        lr = self._lr_scalar(lr)
         self.step_count += 1
         ops.adam_step_dev_(self.data, self.grad, self.exp_avg, self.exp_avg_sq, self.step_dev, lr, beta1=betas[0],
                            beta2=betas[1], eps=eps, weight_decay=weight_decay, skip=self.skip_mask, mirror=self.compute)
+        self._after_step(mirror_written=True)
+
+    def _lr_scalar(self, lr) -> torch.Tensor:
+        """``lr`` as a device fp32 scalar: a tensor is taken as it is, a float is kept in a scalar of this object that is
+        rewritten when the value changes."""
+        if isinstance(lr, torch.Tensor):
+            return lr
+        if getattr(self, "_lr_dev", None) is None:
+            self._lr_dev, self._lr_host = torch.full((1,), float(lr), dtype=torch.float32, device=self.data.device), lr
+        elif self._lr_host != lr:
+            self._lr_dev.fill_(float(lr))
+            self._lr_host = lr
+        return self._lr_dev
+
+    def lars_step(self, lr, momentum: float = 0.0, weight_decay=0.0, dampening: float = 0.0, nesterov: bool = False,
+                  trust_coefficient: float = 0.001, eps: float = 1e-8) -> None:
+        """``optim.LARS`` semantics over the flat buffers in two launches (per-tensor norms, update): the same kernels, fed
+        a table of slices instead of separate tensors, plus the 16-bit mirror of the updated weights.  ``weight_decay``: a
+        float, or one value per parameter (``self.params`` order; 0 for what ``exclude_from_wt_decay`` excludes).  ``lr``:
+        a float or a device fp32 scalar, as in ``adam_step``.  Parameters nobody wrote a gradient for are not in the table:
+        parameter, buffer and mirror stay as they are.  The norms are taken from ``self.grad`` as it stands, i.e. after
+        ``finish_backward`` from the all-reduced gradient.  The first-step rule (buf = d) follows the one device counter, as
+        the bias correction of ``adam_step`` does.  That counter (``step_dev``) and ``momentum_buf`` are the ones
+        ``adam_step`` and ``sgd_step`` use: one FlatParameters is meant to be stepped by one optimizer.  After an Adam or
+        SGD step on the same object, LARS sees no first step and continues SGD's momentum buffer."""
+        wds = ((float(weight_decay),) * len(self.params) if isinstance(weight_decay, (int, float))
+               else tuple(float(w) for w in weight_decay))
+        if len(wds) != len(self.params):
+            raise ValueError(f"lars_step: {len(wds)} weight_decay values for {len(self.params)} parameters")
+        lr = self._lr_scalar(lr)
+        if momentum != 0.0 and getattr(self, "momentum_buf", None) is None:
+            self.momentum_buf = torch.zeros_like(self.data)
+        if getattr(self, "step_dev", None) is None:
+            self.step_dev = torch.zeros(2, dtype=torch.int64, device=self.data.device)
+        sig = (self._skip_sig, wds, momentum != 0.0)
+        if getattr(self, "_lars_sig", None) != sig:
+            if self.data.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the LARS segment table changed inside a hipGraph capture; run the warm-up steps with the "
+                                   "same arguments and model mode as the captured step")
+            segs = []
+            for i, p in enumerate(self.params):
+                if i in self._skip_sig:
+                    continue
+                lo, hi = self.offsets[i], self.offsets[i] + p.numel()
+                segs.append((self.data[lo:hi], self.grad[lo:hi], self.momentum_buf[lo:hi] if momentum != 0.0 else None,
+                             None if self.compute is None else self.compute[lo:hi], wds[i]))
+            self._lars_table, self._lars_sig = (ops.lars_table(segs) if segs else None), sig
+        if self.compute is not None and not self.compute_valid and self._skip_sig:
+            self.sync_compute_copy()            # the step below writes the mirror of the parameters it updates only
+        self.step_count += 1
+        if self._lars_table is not None:
+            ops.lars_step_(self._lars_table, lr, self.step_dev, momentum=momentum, dampening=dampening, nesterov=nesterov,
+                           trust_coefficient=trust_coefficient, eps=eps)
         self._after_step(mirror_written=True)
 
     def sgd_step(self, lr: float, momentum: float = 0.0, weight_decay: float = 0.0) -> None:

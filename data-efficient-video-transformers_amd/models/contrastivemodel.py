@@ -12,7 +12,8 @@ initialisation draw order are the reference's -- and its semantics:
     then view j) and ``num_batches_tracked`` grows by 2 (:160-161);
   - ``training_step`` L2-normalises both outputs before the loss, ``validation_step`` does not (:160-166, :190-196);
   - ``configure_optimizers``: Adam(lr, weight_decay) with coupled decay and ``LinearWarmupCosineAnnealingLR(
-    warmup_epochs=epochs // 10, max_epochs=epochs)`` (:57-92).
+    warmup_epochs=epochs // 10, max_epochs=epochs)`` (:57-92); the additive config key ``optimizer: "lars"`` selects the
+    reference's commented-out LARS block instead, with the same scheduler.
 
 All arithmetic is HIP: the GEMMs (bias and ReLU in their epilogues), ``dvt_bn1d_relu_*``, dropout, L2-normalisation and the
 contrastive loss.  ``step_views(x_i, x_j)`` runs both views as ONE [2B, .] launch per layer and returns what two
@@ -130,8 +131,18 @@ class SpatioTemporalContrastiveModel(LightningModule):
 
     # ------------------------------------------------------------------ optimisation
     def configure_optimizers(self):
-        optimizer = optim.Adam(self.parameters(), lr=cfg(self.config, "learning_rate"),
-                               weight_decay=cfg(self.config, "weight_decay"))
+        """Adam, as the reference runs; config key ``optimizer: "lars"`` (ours, optional) selects the block the reference
+        keeps commented out (:64-70): LARS over ``exclude_from_wt_decay``'s two groups with ``config["momentum"]``."""
+        which = cfg(self.config, "optimizer") if "optimizer" in self.config else "adam"
+        if which == "adam":
+            optimizer = optim.Adam(self.parameters(), lr=cfg(self.config, "learning_rate"),
+                                   weight_decay=cfg(self.config, "weight_decay"))
+        elif which == "lars":
+            parameters = self.exclude_from_wt_decay(self.named_parameters(), weight_decay=cfg(self.config, "weight_decay"))
+            optimizer = optim.LARS(parameters, lr=cfg(self.config, "learning_rate"), momentum=cfg(self.config, "momentum"),
+                                   weight_decay=cfg(self.config, "weight_decay"), trust_coefficient=0.0001)
+        else:
+            raise ValueError(f"config optimizer: {which!r} is not one of 'adam', 'lars'")
         epochs = cfg(self.config, "epochs")
         scheduler = LinearWarmupCosineAnnealingLR(optimizer, warmup_epochs=epochs // 10, max_epochs=epochs)
         return [optimizer], [scheduler]

@@ -1338,6 +1338,107 @@ def adagrad_step_(param: Tensor, grad: Tensor, state_sum: Tensor, *, lr: float, 
                                       _skip(skip, param), _stream()), "dvt_adagrad_step")
 
 
+LarsSeg = L.STRUCTS["dvt_lars_seg"]
+LarsPlanInfo = L.STRUCTS["dvt_lars_plan_info"]
+
+
+class LarsPlan(NamedTuple):
+    chunk: int                # elements per chunk
+    blocks: int               # blocks per launch: sum of ceil(numel / chunk)
+    grid_cap: int             # 0: none
+    workspace_bytes: int
+    chunk_begin: Tuple[int, ...]      # first chunk of every segment, then the total
+
+
+def lars_plan(numels) -> LarsPlan:
+    """How ``dvt_lars_sumsq`` / ``dvt_lars_step`` cut tensors of these sizes into chunks (host only, no GPU needed)."""
+    numels = [int(n) for n in numels]
+    arr, begin, info = (C.c_int64 * len(numels))(*numels), (C.c_int64 * (len(numels) + 1))(), LarsPlanInfo()
+    L.check(L.load().dvt_lars_plan(C.cast(arr, C.c_void_p), len(numels), C.byref(info), C.cast(begin, C.c_void_p)),
+            "dvt_lars_plan")
+    return LarsPlan(info.chunk, info.blocks, info.grid_cap, info.workspace_bytes, tuple(begin))
+
+
+class LarsTable:
+    """The device segment table of one LARS call, its plan and its workspace.  Holds the tensors it points into, and the
+    host rows in pinned memory, so that ``set_grads`` can point the same table at other gradient tensors."""
+
+    def __init__(self, rows, pinned: Tensor, plan: LarsPlan, keep, mirror_dtype: int, device):
+        self.rows, self.pinned, self.plan, self.keep, self.mirror_dtype = rows, pinned, plan, keep, mirror_dtype
+        self.n = len(plan.chunk_begin) - 1
+        self.has_buf = all(k[2] is not None for k in keep)
+        self.table = torch.empty(pinned.numel(), dtype=torch.uint8, device=device)
+        self.workspace = torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=device)
+        self._uploaded = None
+        self._upload()
+
+    def _upload(self):
+        """Host rows -> device table on the current stream, without waiting for it.  The rows are pinned memory that the
+        copy reads later, so they are written again only after the previous copy is over (an event that has long fired
+        by the next step; no other wait)."""
+        self.table.copy_(self.pinned, non_blocking=True)
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record()
+
+    def grad_ptrs(self):
+        return tuple(k[1].data_ptr() for k in self.keep)
+
+    def set_grads(self, grads) -> None:
+        """The same segments with other gradient tensors (torch's ``zero_grad(set_to_none=True)`` gives every step fresh
+        ones): only the gradient pointers change; table, workspace and plan stay, and the former gradients are let go."""
+        grads = list(grads)
+        assert len(grads) == self.n
+        self._uploaded.synchronize()
+        for r, k, g in zip(self.rows, self.keep, grads):
+            _, r.grad, _ = _flat_f32(k[0], g)
+        self.keep = [(k[0], g, k[2], k[3]) for k, g in zip(self.keep, grads)]
+        self._upload()
+
+
+def lars_table(segments) -> LarsTable:
+    """segments: (param, grad, momentum_buf or None, mirror or None, weight_decay) per tensor with a gradient; empty tensors
+    are left out.  Every tensor obeys the optimizer steps' contract (``_flat_f32``, ``_mirror``); mirrors are given for all
+    segments or for none, in one dtype.  The table is built on the host and copied to the device once."""
+    segments = [s for s in segments if s[0].numel() > 0]
+    if not segments:
+        raise ValueError("lars_table: no segments")
+    _need_cuda(*(t for s in segments for t in s[:4]))
+    plan = lars_plan(s[0].numel() for s in segments)
+    pinned = torch.empty(C.sizeof(LarsSeg) * len(segments), dtype=torch.uint8, pin_memory=True)
+    rows, keep, mdts = (LarsSeg * len(segments)).from_address(pinned.data_ptr()), [], set()
+    for r, (p, g, buf, mirror, wd), begin in zip(rows, segments, plan.chunk_begin):
+        r.param, r.grad, r.buf, r.numel = _flat_f32(p, g, buf)
+        r.mirror, mdt = _mirror(mirror, p)
+        r.chunk_begin, r.weight_decay, r.reserved = begin, float(wd), 0
+        mdts.add(mdt)
+        keep.append((p, g, buf, mirror))
+    if len(mdts) != 1:
+        raise ValueError("lars_table: give a 16-bit mirror of one dtype for every segment, or for none")
+    return LarsTable(rows, pinned, plan, keep, mdts.pop(), segments[0][0].device)
+
+
+def lars_sumsq(t: LarsTable) -> Tensor:
+    """-> f32 [segments, 2]: sum of p^2 and of g^2 per segment, the values ``lars_step_`` forms its norms from."""
+    out = torch.empty((t.n, 2), dtype=torch.float32, device=t.table.device)
+    L.check(L.load().dvt_lars_sumsq(C.cast(t.table.data_ptr(), C.POINTER(LarsSeg)), t.n, t.plan.blocks,
+                                    t.workspace.data_ptr(), out.data_ptr(), _stream()), "dvt_lars_sumsq")
+    return out
+
+
+def lars_step_(t: LarsTable, lr_dev: Tensor, step_dev2: Tensor, *, momentum: float = 0.0, dampening: float = 0.0,
+               nesterov: bool = False, trust_coefficient: float = 0.001, eps: float = 1e-8) -> None:
+    """One LARS step over the table's segments in two launches (norms, update); the learning rate is read from the
+    device scalar ``lr_dev`` (f32), the first-step rule from the device counter ``step_dev2`` (int64[2])."""
+    _need_cuda(step_dev2, lr_dev)
+    assert step_dev2.dtype == torch.int64 and step_dev2.numel() == 2 and lr_dev.dtype == torch.float32
+    if momentum != 0 and not t.has_buf:
+        raise ValueError("lars_step_: momentum != 0 needs a momentum buffer for every segment")
+    L.check(L.load().dvt_lars_step(C.cast(t.table.data_ptr(), C.POINTER(LarsSeg)), t.n, t.plan.blocks,
+                                   t.workspace.data_ptr(), lr_dev.data_ptr(), momentum, dampening, int(bool(nesterov)),
+                                   trust_coefficient, eps, step_dev2.data_ptr(), int(t.mirror_dtype != 0), t.mirror_dtype,
+                                   _stream()), "dvt_lars_step")
+
+
 # ------------------------------------------------------------------ per-frame CNN encoder (csrc/conv.hip)
 def _pair(v):
     return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))

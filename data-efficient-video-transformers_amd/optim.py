@@ -2,8 +2,9 @@
 (``configure_optimizers`` of the reference: frame_transformer.py:123-134, transformer.py:58-61).
 
 Per-parameter launches of the fused update kernels (``dvt_adamw_step`` / ``dvt_adam_step_dev`` / ``dvt_sgd_step`` /
-``dvt_adagrad_step``); a model wrapped in ``dp.FlatParameters`` should use its one-launch
-``adamw_step`` / ``adam_step`` / ``sgd_step`` / ``adagrad_step`` instead.  State names match torch's
+``dvt_adagrad_step``), and ``LARS`` with one ``dvt_lars_step`` per parameter group; a model wrapped in
+``dp.FlatParameters`` should use its one-launch ``adamw_step`` / ``adam_step`` / ``sgd_step`` / ``adagrad_step`` /
+``lars_step`` instead.  State names match torch's
 (``exp_avg``, ``exp_avg_sq``, ``momentum_buffer``, ``sum``, ``step``) so optimizer state dicts
 written by the reference load unchanged.
 """
@@ -77,17 +78,12 @@ class AdamW(_Base):
                         beta2=grp["betas"][1], eps=grp["eps"], weight_decay=grp["weight_decay"], step=st["step"])
 
 
-class Adam(_Base):
-    """torch.optim.Adam (amsgrad off) with coupled L2 weight decay (``g += weight_decay * p`` before the moments):
-    contrastivemodel.py:64 and basicmlp.py:49.  The optimizer owns one device fp32 LR scalar per parameter group
-    (``lr_dev(i)``) that every update reads, and one device step counter per parameter (``state["step"]``, int64[2]:
-    steps taken, launch ticket), so ``step()`` has no host synchronisation and can be captured in a hipGraph; a captured
-    step follows a new rate written by ``sync_lr()`` (which ``lr_scheduler.LinearWarmupCosineAnnealingLR.step`` calls)."""
+class _DeviceLR(_Base):
+    """One device fp32 LR scalar per parameter group (``lr_dev(i)``) that the group's updates read, so that a step captured
+    in a hipGraph follows a new rate written by ``sync_lr()`` (which ``lr_scheduler.LinearWarmupCosineAnnealingLR.step``
+    calls)."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
-        if amsgrad:
-            raise NotImplementedError("Adam(amsgrad=True) has no HIP kernel")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
+    def _init_lr_dev(self):
         self._lr_dev = []
         self._lr_host = []
         for grp in self.param_groups:
@@ -108,9 +104,26 @@ class Adam(_Base):
                 self._lr_host[i] = lr
 
     def _begin_step(self):
-        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-        if not capturing:                 # a rate set by hand; inside a capture the scalar is written from outside
+        if not _capturing():              # a rate set by hand; inside a capture the scalar is written from outside
             self.sync_lr()
+
+
+def _capturing() -> bool:
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+class Adam(_DeviceLR):
+    """torch.optim.Adam (amsgrad off) with coupled L2 weight decay (``g += weight_decay * p`` before the moments):
+    contrastivemodel.py:64 and basicmlp.py:49.  The optimizer owns one device fp32 LR scalar per parameter group
+    (``lr_dev(i)``) that every update reads, and one device step counter per parameter (``state["step"]``, int64[2]:
+    steps taken, launch ticket), so ``step()`` has no host synchronisation and can be captured in a hipGraph; a captured
+    step follows a new rate written by ``sync_lr()`` (which ``lr_scheduler.LinearWarmupCosineAnnealingLR.step`` calls)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
+        if amsgrad:
+            raise NotImplementedError("Adam(amsgrad=True) has no HIP kernel")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
+        self._init_lr_dev()
 
     def _init_state(self, st, p, grp):
         if not st:
@@ -150,3 +163,94 @@ class Adagrad(_Base):
         st["step"] = int(st["step"]) + 1
         ops.adagrad_step_(p.data, g, st["sum"], lr=grp["lr"], lr_decay=grp["lr_decay"], eps=grp["eps"],
                           weight_decay=grp["weight_decay"], step=st["step"])
+
+
+class LARS(_DeviceLR):
+    """pl_bolts' ``LARS`` (layer-wise adaptive rate scaling: contrastivemodel.py:8, :64-70), per parameter with a gradient:
+
+        d = g
+        if weight_decay != 0 and |p| != 0 and |g| != 0:
+            d = trust_coefficient |p| / (|g| + weight_decay |p| + eps) * (g + weight_decay p)
+        if momentum != 0:
+            buf = d on the first step, momentum buf + (1 - dampening) d afterwards
+            d = d + momentum buf if nesterov else buf
+        p = p - lr d
+
+    so ``weight_decay == 0`` is plain momentum SGD, and a zero norm drops the decay term too.  One ``dvt_lars_step`` (two
+    launches: norms, update) per parameter group and step, over a device table of the group's parameters that have a
+    gradient; the table is rebuilt only when that set changes.  Gradient tensors that torch allocates anew every step
+    (``zero_grad(set_to_none=True)``, its default) cost one small asynchronous copy of the table's rows per step, which
+    refreshes the gradient pointers and nothing else; gradients kept in place (``set_to_none=False``) cost nothing.
+    Neither may happen inside a hipGraph capture, whose launches hold the addresses they were captured with.
+    The learning rate is read from ``lr_dev(i)`` as in ``Adam``; no host synchronisation.  State: ``momentum_buffer`` per
+    parameter, as torch's SGD and pl_bolts name it.
+
+    One deviation: "the first step" is the GROUP's (one device counter per group), where pl_bolts looks at each parameter's
+    own state.  A parameter that receives its first gradient in a later step starts from a zero buffer, buf =
+    (1 - dampening) d instead of d; the two agree whenever dampening == 0 or every parameter has a gradient from the first
+    step on.  Under data parallelism the norms are those of the gradient the step sees, i.e. the all-reduced one when the
+    step follows ``FlatParameters.finish_backward``."""
+
+    def __init__(self, params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, trust_coefficient=0.001,
+                 eps=1e-8):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                      nesterov=nesterov, trust_coefficient=trust_coefficient, eps=eps))
+        self._init_lr_dev()
+        self._tables = {}          # group index -> (signature, ops.LarsTable)
+        self._step_dev = {}        # group index -> int64[2] on the device: steps taken, launch ticket
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for grp in self.param_groups:
+            grp.setdefault("nesterov", False)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._tables, self._step_dev = {}, {}      # the loaded buffers are other tensors; groups that hold one have stepped
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._begin_step()
+        for i, grp in enumerate(self.param_groups):
+            live = [(p, g) for p in grp["params"] for g in (_grad32(p),) if g is not None and p.numel() > 0]
+            if not live:
+                continue
+            mom = grp["momentum"] != 0
+            if i not in self._step_dev:
+                resumed = any("momentum_buffer" in self.state[p] for p, _ in live)
+                self._step_dev[i] = torch.tensor([int(resumed), 0], dtype=torch.int64, device=live[0][0].device)
+            sig = tuple(p.data_ptr() for p, _ in live) + (mom, grp["weight_decay"])
+            grads = tuple(g.data_ptr() for _, g in live)
+            cached = self._tables.get(i)
+            if cached is None or cached[0] != sig or cached[1].grad_ptrs() != grads:
+                if _capturing():
+                    raise RuntimeError("the set of parameters with a gradient, or a gradient's address, changed inside a "
+                                       "hipGraph capture; run the warm-up steps with the same model mode as the captured "
+                                       "step and keep the gradient tensors (zero_grad(set_to_none=False))")
+                if cached is not None and cached[0] == sig:
+                    cached[1].set_grads(g for _, g in live)        # fresh gradient tensors: only their pointers change
+                else:
+                    for p, _ in live:
+                        if mom and "momentum_buffer" not in self.state[p]:
+                            self.state[p]["momentum_buffer"] = _zeros_like(p)
+                    cached = (sig, ops.lars_table([(p.data, g, self.state[p].get("momentum_buffer") if mom else None,
+                                                    None, grp["weight_decay"]) for p, g in live]))
+                    self._tables[i] = cached
+            ops.lars_step_(cached[1], self._lr_dev[i], self._step_dev[i], momentum=grp["momentum"],
+                           dampening=grp["dampening"], nesterov=grp["nesterov"],
+                           trust_coefficient=grp["trust_coefficient"], eps=grp["eps"])
+            for p, _ in live:
+                self._invalidate(p)
+        return loss

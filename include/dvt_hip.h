@@ -1214,6 +1214,49 @@ int dvt_probe_bwd_step(const dvt_probe_desc* desc, dvt_stream_t stream);
 int dvt_multilabel_sweep_counts(const float* probs, const unsigned char* labels, int64_t N, int C, const float* thresholds,
                                 int T, int64_t* counts, int64_t* support, dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- LARS (layer-wise adaptive rate scaling)
+ * Additions within ABI v5.  pl_bolts.optimizers.lars.LARS, which the reference imports for its contrastive model
+ * (contrastivemodel.py:8, :64-70).  Per tensor with a gradient, all in fp32:
+ *   d = g
+ *   if weight_decay != 0 and |p| != 0 and |g| != 0:  d = trust_coefficient |p| / (|g| + weight_decay |p| + eps) * (g + weight_decay p)
+ *   if momentum != 0:  buf = d on the first step, momentum buf + (1 - dampening) d afterwards;  d = d + momentum buf (nesterov) or buf
+ *   p = p - lr d
+ * The tensors are the entries of a table ON THE DEVICE (pointers, so that separate allocations and slices of one flat buffer
+ * take the same path); a tensor without a gradient this step is not in the table and stays untouched.  Each segment is cut
+ * into chunks of dvt_lars_plan_info.chunk elements, one block per chunk; chunk_begin is the index of the segment's first
+ * chunk (dvt_lars_plan fills it), ascending over the table.  `workspace` (caller-owned, workspace_bytes, 8-byte aligned,
+ * no initial content required) receives the per-chunk sums of p^2 and g^2; a segment's sums are added from them in a fixed
+ * order that depends on numel alone.  No atomics on floats, no host synchronisation: identical calls from the same state
+ * give bitwise-equal results and may be captured in a hipGraph. */
+typedef struct dvt_lars_seg {
+  float* param;                  /* [numel] f32 */
+  const float* grad;             /* [numel] f32 */
+  float* buf;                    /* [numel] f32 momentum buffer (momentum == 0: unused, may be NULL) */
+  void* mirror;                  /* [numel] bf16 / f16 copy of the updated parameter (`mirror` == 0: unused) */
+  int64_t numel;                 /* >= 1 */
+  int64_t chunk_begin;
+  float weight_decay;
+  int32_t reserved;
+} dvt_lars_seg;
+typedef struct dvt_lars_plan_info {
+  int64_t chunk;                 /* elements per chunk */
+  int64_t blocks;                /* blocks per launch = the total number of chunks, sum of ceil(numel / chunk) */
+  int64_t grid_cap;              /* 0: no cap, every chunk has a block of its own */
+  int64_t workspace_bytes;
+} dvt_lars_plan_info;
+/* Host only.  numel [n] on the host; chunk_begin (optional) receives n + 1 values, the last one the total. */
+int dvt_lars_plan(const int64_t* numel, int n, dvt_lars_plan_info* info, int64_t* chunk_begin);
+/* sumsq f32 [n][2] on the device = {sum p^2, sum g^2} per segment, the values dvt_lars_step uses.  `chunks`: the plan's
+ * `blocks` for this table (the table is on the device, so the host cannot check it against chunk_begin); `workspace`
+ * holds `chunks` pairs.  A larger value only launches idle blocks, which touch no tensor.  Two launches. */
+int dvt_lars_sumsq(const dvt_lars_seg* table, int n, int64_t chunks, float* workspace, float* sumsq, dvt_stream_t stream);
+/* One LARS step over the table in two launches (norms, update).  lr_dev f32 [1] and step_dev2 int64 [2] {steps taken,
+ * launch ticket} on the device, as dvt_adam_step_dev; the counter only tells the first step (buf = d) from later ones.
+ * mirror != 0: every segment's `mirror` is written, mirror_dtype DVT_BF16 / DVT_F16.  n == 0: nothing is launched. */
+int dvt_lars_step(const dvt_lars_seg* table, int n, int64_t chunks, float* workspace, const float* lr_dev, float momentum,
+                  float dampening, int nesterov, float trust_coefficient, float eps, int64_t* step_dev2, int mirror,
+                  int mirror_dtype, dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- data-parallel gradient exchange
  * The reference is single-GPU (pl.Trainer(gpus=1), src/main.py:87); north_star partitions the clips of the global
  * batch over the 8 GPUs of a node, and the only exchange of the path is the SUM of the parameter gradients.  RCCL over
