@@ -14,8 +14,11 @@ state-dict files in torchvision's key layout named by the optional config keys `
 and ``location_net_weights`` (``fc.*`` keys are ignored); a net without a file gets a seeded random init and a one-line
 warning on stderr.  ``compute_dtype`` (config, default bf16; "fp32" / "fp16" selectable).  The reference runs one forward
 per image; here all of a key's frames go through one batched forward and the mean over the frames is taken on the device,
-with one device-to-host copy at the end.  Depth and audio experts: the reference never builds those networks, their
-methods raise ``NotImplementedError``.
+with one device-to-host copy at the end.  Depth expert: the reference never builds that network, its methods raise
+``NotImplementedError``.  Audio expert: the reference names VGGish at models.py:13 (commented out: torch.hub) and calls it at
+:55-57; it is built here only when the config carries ``audio_net: true`` or ``audio_net_weights: <path>`` (``vggish.VGGish``,
+mono 16 kHz waveforms in, one 128-d vector per 0.96 s example out) -- without either key ``forward_audio`` raises
+``NotImplementedError`` and ``return_expert_for_key("audio", ..)`` returns ``[]``, as before.
 """
 from __future__ import annotations
 
@@ -27,12 +30,13 @@ import torch.nn as nn
 from ... import functional as F
 from ..custom_resnet import resnet50
 from ..video_resnet import r3d_18
+from .vggish import SEED as _AUDIO_SEED, vggish
 
 __all__ = ["EmbeddingExtractor", "Identity"]
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp16": torch.float16, "float16": torch.float16,
            "half": torch.float16, "fp32": torch.float32, "float32": torch.float32, "float": torch.float32}
-_SEEDS = {"image_net": 0, "video_net": 1, "location_net": 2}
+_SEEDS = {"image_net": 0, "video_net": 1, "location_net": 2, "audio_net": _AUDIO_SEED}
 
 
 class Identity(nn.Module):
@@ -75,6 +79,10 @@ class EmbeddingExtractor:
         self.image_net = self._build("image_net", resnet50, _cfg(config, "image_net_weights"))
         self.video_net = self._build("video_net", r3d_18, _cfg(config, "video_net_weights"))
         self.location_net = self._build("location_net", resnet50, _cfg(config, "location_net_weights"))
+        self.audio_net = None
+        audio_weights = _cfg(config, "audio_net_weights")
+        if audio_weights or _cfg(config, "audio_net", False, bool):
+            self.audio_net = vggish(audio_weights, compute_dtype=self.compute_dtype, seed=_SEEDS["audio_net"])
 
     def _build(self, name, factory, path):
         with torch.random.fork_rng(devices=[]):
@@ -110,6 +118,18 @@ class EmbeddingExtractor:
         with torch.no_grad():
             return net.features(clips.to(self.device, non_blocking=True))
 
+    def extract_audio(self, waveform):
+        """waveform [L] -> [E, 128]; [..., T, L] -> [..., T * E, 128] on the device (audio expert): one token per 0.96 s
+        example, the E examples of each of the T chunks in order -- [B, 32, 16000] (32 one-second chunks) -> [B, 32, 128],
+        the ``audio`` argument of PyramidViViT."""
+        if self.audio_net is None:
+            raise NotImplementedError("the audio expert (VGGish) is built only when the config carries audio_net: true or "
+                                      "audio_net_weights: <path>")
+        net = self.init_models(self.audio_net)
+        with torch.no_grad():
+            out = net(waveform.to(self.device, non_blocking=True))                # [..., E, 128]
+        return out if waveform.dim() == 1 else out.flatten(-3, -2)
+
     def _mean_over_frames(self, raw, net):
         """raw: F images of [b, 1, 3, H, W] -> [b, 2048] = mean over the F images (the reference's stack -> transpose ->
         adaptive_avg_pool1d(1)), one batched forward of all b * F frames."""
@@ -134,7 +154,7 @@ class EmbeddingExtractor:
         raise NotImplementedError("the depth expert (MiDaS) is never built by the reference (models.py:16); not provided")
 
     def forward_audio(self, audio_sample):
-        raise NotImplementedError("the audio expert (VGGish) is never built by the reference (models.py:11); not provided")
+        return self.extract_audio(audio_sample).cpu().float()
 
     def depth_network_pool(self, depth_output):
         raise NotImplementedError("the depth expert (MiDaS) is never built by the reference; not provided")
@@ -146,6 +166,8 @@ class EmbeddingExtractor:
             return self.forward_video(raw_tensor.unsqueeze(0))
         if key == "location":
             return self._mean_over_frames(raw_tensor, self.location_net)
+        if key == "audio" and self.audio_net is not None:
+            return self.forward_audio(raw_tensor)
         return []
 
     def return_expert_for_key_pretrained(self, key, raw_tensor):

@@ -2687,3 +2687,63 @@ def multilabel_sweep_counts(probs: Tensor, labels: Tensor, thresholds) -> Tuple[
                                                  counts.data_ptr(), support.data_ptr(), _stream()),
             "dvt_multilabel_sweep_counts")
     return counts, support
+
+
+# ------------------------------------------------------------------ VGGish audio expert (csrc/audio.hip)
+LOGMEL_VARIANTS = {name[len("DVT_LOGMEL_"):].lower(): v for name, v in L.ENUMS["dvt_logmel_variant"].items()}
+# The spectrum dvt_logmel_examples computes by default; DESIGN 4.16 has the grounds and both forms' measured times and errors.
+# "dft" stays selectable for that comparison (tools/bench_audio.py); its accuracy is pinned to a looser, stated bound.
+LOGMEL_VARIANT = "fft"
+LOGMEL_FRAMES, LOGMEL_BANDS = 96, 64          # an example's shape, as csrc/audio.hip states it (kExFrames, kMel): the output's trailing dims
+_logmel_tables = {}
+
+
+def logmel_num_examples(L_: int) -> int:
+    """Examples a waveform row of L_ samples yields (dvt_logmel_num_examples; host only)."""
+    return int(L.load().dvt_logmel_num_examples(int(L_)))
+
+
+def logmel_tables_host() -> Tensor:
+    """The front end's tables as dvt_logmel_tables builds them (float64 on the host, rounded once) -> f32 CPU tensor."""
+    lib = L.load()
+    t = torch.empty(lib.dvt_logmel_examples_workspace_bytes() // 4, dtype=torch.float32)
+    L.check(lib.dvt_logmel_tables(t.data_ptr(), t.numel() * 4), "dvt_logmel_tables")
+    return t
+
+
+def logmel_examples(wave: Tensor, out_dtype: torch.dtype = torch.float32, variant: Optional[str] = None) -> Tensor:
+    """wave f32 [R, L] (mono, 16 kHz, in [-1, 1]) -> log-mel examples [R * E, 96, 64] in out_dtype (dvt_logmel_examples);
+    E = logmel_num_examples(L), an empty result when the row is shorter than one example.  The tables are uploaded once per
+    device."""
+    _need_cuda(wave)
+    if wave.dim() != 2 or wave.dtype != torch.float32:
+        raise TypeError("logmel_examples: expected an f32 waveform [R, L]")
+    wave = wave.contiguous()
+    R, L_ = wave.shape
+    E = logmel_num_examples(L_)
+    out = torch.empty((R * E, LOGMEL_FRAMES, LOGMEL_BANDS), dtype=out_dtype, device=wave.device)
+    if out.numel() == 0:
+        return out
+    tab = _logmel_tables.get(wave.device)
+    if tab is None:
+        tab = _logmel_tables[wave.device] = logmel_tables_host().to(wave.device)
+    v = LOGMEL_VARIANTS[LOGMEL_VARIANT if variant is None else variant]
+    with _timed("logmel_examples", wave.numel() * 4 + out.numel() * out.element_size()):
+        L.check(L.load().dvt_logmel_examples(wave.data_ptr(), R, L_, tab.data_ptr(), out.data_ptr(), _DT[out_dtype], v,
+                                             _stream()), "dvt_logmel_examples")
+    return out
+
+
+def vggish_conv1_pool(x: Tensor, w: Tensor, bias: Tensor) -> Tensor:
+    """Conv2d(1, 64, 3, padding=1) + bias + ReLU + MaxPool2d(2, 2) in one launch (dvt_vggish_conv1_pool).  x [N, H, 64] in the
+    compute dtype, w f32 [64, 1, 3, 3], bias f32 [64] -> NHWC [N * H/2 * 32, 64] in x's dtype."""
+    _need_cuda(x, w, bias)
+    if x.dim() != 3 or w.dtype != torch.float32 or bias.dtype != torch.float32 or w.numel() != 576 or bias.numel() != 64:
+        raise TypeError("vggish_conv1_pool: expected x [N, H, 64], w f32 [64, 1, 3, 3], bias f32 [64]")
+    x, w, bias = x.contiguous(), w.contiguous(), bias.contiguous()
+    N, H, W = x.shape
+    y = torch.empty((N * (H // 2) * (W // 2), 64), dtype=x.dtype, device=x.device)
+    with _timed("vggish_conv1_pool", x.numel() * x.element_size() + y.numel() * y.element_size()):
+        L.check(L.load().dvt_vggish_conv1_pool(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), N, H, W, dt(x),
+                                               _stream()), "dvt_vggish_conv1_pool")
+    return y

@@ -1257,6 +1257,30 @@ int dvt_lars_step(const dvt_lars_seg* table, int n, int64_t chunks, float* works
                   float dampening, int nesterov, float trust_coefficient, float eps, int64_t* step_dev2, int mirror,
                   int mirror_dtype, dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- VGGish audio expert: log-mel front end, first layer
+ * Additions within ABI v5.  The audio network the reference names at pretrained/models.py:13 (torchvggish, commented out:
+ * torch.hub needs the network) and calls at :55-57.  csrc/audio.hip; the definition of the front end (16 kHz mono, frames
+ * of 400 every 160, periodic Hann, |rfft_512|, 64 HTK mel bands 125 .. 7500 Hz with a zero DC row, log(mel + 0.01), examples
+ * of 96 frames every 96) is stated once, at the top of that file.
+ *   dvt_logmel_num_examples(L): examples E a row of L samples yields (0 below 15 600).  Host only.
+ *   dvt_logmel_tables: the window, the FFT twiddles, the windowed DFT table and the mel matrix, computed in float64 and
+ *     rounded once, written to a HOST buffer of dvt_logmel_examples_workspace_bytes() bytes; the caller uploads it once and
+ *     passes the device copy (16-byte aligned) as `tables`.
+ *   dvt_logmel_examples: wave f32 [R][L] in [-1, 1] -> out [R * E][96][64] of `dtype` (the NHWC map of a one-channel image,
+ *     H = time, W = mel), fp32 arithmetic, one rounding at the store.  E == 0 or R == 0: nothing is launched.  `variant`
+ *     picks the spectrum: a radix-2 FFT in LDS (the form the Python side uses) or a table DFT on v_mfma_f32_16x16x4_f32 (kept
+ *     for the comparison of the two; its 400-term sums are less accurate); both leave their magnitudes to the same mel product.  No atomics: identical calls give bitwise-equal results.
+ *   dvt_vggish_conv1_pool: Conv2d(1, 64, 3, padding 1) + bias + ReLU + MaxPool2d(2, 2) in one launch.  x [N][H][64] of
+ *     `dtype`, w f32 [64][9] (nn.Conv2d's [64, 1, 3, 3]), bias f32 [64] -> y NHWC [N * H/2 * 32][64] of `dtype`; H even. */
+enum dvt_logmel_variant { DVT_LOGMEL_DFT = 0, DVT_LOGMEL_FFT = 1 };
+int64_t dvt_logmel_num_examples(int64_t L);
+size_t dvt_logmel_examples_workspace_bytes(void);
+int dvt_logmel_tables(float* dst, size_t bytes);
+int dvt_logmel_examples(const float* wave, int64_t R, int64_t L, const float* tables, void* out, int dtype, int variant,
+                        dvt_stream_t stream);
+int dvt_vggish_conv1_pool(const void* x, const float* w, const float* bias, void* y, int64_t N, int H, int W, int dtype,
+                          dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- data-parallel gradient exchange
  * The reference is single-GPU (pl.Trainer(gpus=1), src/main.py:87); north_star partitions the clips of the global
  * batch over the 8 GPUs of a node, and the only exchange of the path is the SUM of the parameter gradients.  RCCL over

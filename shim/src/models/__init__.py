@@ -10,7 +10,7 @@ makes those imports resolve to the MI355X build, with ``main.py`` unchanged: the
 ``__init__.py``, i.e. it is a namespace-package portion, and a regular package found anywhere on ``sys.path`` takes
 precedence over namespace portions -- also over the one in the script directory.  Modules the build does not replace
 (``models.LSTM`` main.py:13 -- built, but selected by importing ``dvt_amd.models.LSTM`` --, and
-``basicmlp``, ``contrastivemodel``, ``pretrained``: out of scope) keep resolving to the
+``basicmlp``, ``contrastivemodel``: selected by importing ``dvt_amd.models...`` as well) keep resolving to the
 reference's files: every other ``models`` directory on ``sys.path`` is appended to this
 package's search path.
 """
