@@ -48,22 +48,8 @@ int dvt_num_cus();
 // failed call fails as well and DVT_LAUNCH_CHECK reports it.
 // conv.hip: reduction of BatchNorm-backward partial rows produced by another translation unit's kernel
 namespace dvt_internal {
-// conv3x1_c64.hip: the 64 -> 64 form of the (3, 1, 1) window convolution, behind dvt_conv3x1_fwd (conv3x1_fwd.hip)
-int conv3x1_c64_supported(int64_t N, int T, int L, int dtype);
-int64_t conv3x1_c64_stats_parts(int64_t N, int T, int L);
-int conv3x1_c64_npb(int64_t N, int T, int L, int dtype);
-int conv3x1_c64_fwd(const void* x, const void* w, int64_t ldw, void* y, float* stats_partial, int64_t N, int T, int L, int dtype,
-                    hipStream_t st);
 void bn_bwd_finalize(hipStream_t st, const float* partial, int nparts, int C, float* loc, int accumulate, float* dgamma,
                      float* dbeta, int c_valid);
-// conv3x1_dbn.hip: the temporal data gradient 64 -> 144 + mid-plane BatchNorm backward as a window kernel with helper waves
-// (behind dvt_conv3x1_stream_bn_bwd, conv3x3_stream.hip)
-int conv3x1_dbn_supported(int64_t N, int T, int L, int dtype);
-int conv3x1_dbn_parts(int64_t N, int T, int L);
-int conv3x1_dbn_nb(int64_t N, int T, int L, int dtype);
-int conv3x1_dbn_pass(int mode, const void* dy, const void* w, int64_t ldw, const void* z, const float* mean, const float* invstd,
-                     const float* gamma, const float* beta, int relu, int training, float* partial, const float* loc, void* dz,
-                     int64_t N, int T, int L, int dtype, hipStream_t st);
 }
 
 struct DvtLdsAttr { unsigned long long done = 0ull; };
@@ -150,6 +136,10 @@ template <> struct Elem16<bf16> {
   static __device__ __forceinline__ f32x4 mma(v8 a, v8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
   }
+  static __device__ __forceinline__ f32x4 mma16(v4 a, v4 b, f32x4 c) {        // the 16x16x16 step
+    typedef __attribute__((ext_vector_type(4))) short s4;
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s4, a), __builtin_bit_cast(s4, b), c, 0, 0, 0);
+  }
   static __device__ __forceinline__ v4 tr_read(const char* lds) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) v4*)(lds));
   }
@@ -160,12 +150,27 @@ template <> struct Elem16<f16> {
   static __device__ __forceinline__ f32x4 mma(v8 a, v8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
   }
+  static __device__ __forceinline__ f32x4 mma16(v4 a, v4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
   static __device__ __forceinline__ v4 tr_read(const char* lds) {
     typedef __attribute__((ext_vector_type(4))) short i16x4;    // same instruction, 16-bit payload reinterpreted
     const i16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)(lds));
     return __builtin_bit_cast(v4, r);
   }
 };
+
+// a compile-time integer as a value: picks the instantiation of a generic lambda (`run(IntC<4>{})`)
+template <int N> struct IntC { static constexpr int value = N; };
+
+// s_waitcnt vmcnt(n) for a wave-uniform run-time n in 0 .. MAX (a larger n waits as MAX, which only waits longer): the
+// counter is an immediate, so each count is an instruction of its own -- one arm per count 0 .. MAX and no more
+template <int N> __device__ __forceinline__ void dvt_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+template <int MAX, int K = 0>
+__device__ __forceinline__ void dvt_wait_vm_upto(int n) {
+  static_assert(MAX >= 1 && MAX <= 14 && K <= MAX, "dvt_wait_vm_upto: counts 1 .. 14");
+  if constexpr (K == MAX) dvt_wait_vm<MAX>();
+  else if (n == K) dvt_wait_vm<K>();
+  else dvt_wait_vm_upto<MAX, K + 1>(n);
+}
 
 // ---------------------------------------------------------------- device: wave64 reductions
 __device__ __forceinline__ float wave_sum(float v) {

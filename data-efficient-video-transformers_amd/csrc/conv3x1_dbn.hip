@@ -12,7 +12,7 @@
 // channels, weights streamed through LDS, the z rows requested at the start of each tile's epilogue because 246 - 256
 // registers leave no room to hold them) ran 155 - 167 + 175 - 186 us per layer: MFMA pipe 14 - 16 % busy, the waves parked at
 // s_waitcnt / s_barrier for 47 % of their cycles (profiles/r06_conv3x1_bound.md).  Here, per tile = a segment of S pixels of one
-// clip over all T frames (conv3x1_c64.hip's window: [position][64] in 144-byte rows, three taps = three position offsets):
+// clip over all T frames (the 64-channel window of conv3x1_window.h: 144-byte rows, three taps = three position offsets):
 //   * waves 0 - 8 (compute): wave u owns output channels [16 u, 16 u + 16) -- its 16 x 192 weights are six fragments in
 //     registers for the whole launch -- and runs all of the tile's 16-position blocks; the results go, rounded, into one of two
 //     staging images [position][144] (296-byte rows: the 16 lanes of a ds_write_b64 group on 16 different bank slots);
@@ -23,22 +23,20 @@
 //     constants in registers) and the rows r, r + 24, r + 48, ... of a tile.
 // Same arithmetic, same rounding points and the same formulas as the first form (the folded affine of BnAffine::init decides
 // every mask); the partial sums are added in another order.
-#include "common.h"
+#include "conv3x1_window.h"
 
 namespace {
 
-constexpr int kCI = 64, kCO = 144, kNC = 9, kNH = 7, kNWv = kNC + kNH;        // compute / helper waves
-constexpr int kXRow = 144;                   // window bytes per position: 8 data slots + 1 padding slot (conv3x1_c64.hip)
-constexpr int kSlots = 9;
+using dvt_window::Window;
+using dvt_window::Form;
+using F = dvt_window::Fmt64;
+constexpr int kCI = F::kC, kCO = 144, kNC = 9, kNH = 7, kNWv = kNC + kNH;     // compute / helper waves
+constexpr int kXRow = F::kRow;               // window bytes per position: 8 data slots + 1 padding slot
 constexpr int kMaxXP = 5;                    // window DMA pieces (1 KiB) per helper wave
 constexpr int kSPitch = 296;                 // staging bytes per position
 constexpr int kCH = kCO / 8;                 // 18 chunks of 16 bytes per position
 constexpr int kHRows = (kNH * 64) / kCH;     // 24 row lanes among the helpers (432 of their 448 threads)
 constexpr int kMaxRows = 4;                  // rows per helper thread and tile: tile <= 96 positions (registers: 16 waves, 128 each)
-
-struct Win {
-  int T, L, S, segs, KP, xpos, x_bytes;
-};
 
 struct DbParams {
   const void* dy;       // [N, T, L, 64]
@@ -50,30 +48,9 @@ struct DbParams {
   const float* loc;     // MODE 2: [2][144] sum dzm * xhat, sum dzm of the whole launch (bn_bwd_finalize)
   float inv_rows;
   int relu, training;
-  Win w_;
+  Window w_;
   int ntiles, ldw;
 };
-
-__device__ __attribute__((aligned(16))) unsigned int db_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void db_wait_vm(int n) {      // n is wave-uniform
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-  }
-}
 
 // NB = 16-position blocks of a tile (KP / 16), MODE 1 = sums, 2 = corrected gradient
 template <typename E, int NB, int MODE>
@@ -83,7 +60,7 @@ __global__ __launch_bounds__(kNWv * 64) void conv3x1_dbn_kernel(const DbParams p
   using V4 = typename Elem16<E>::v4;
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const Win& w = p.w_;
+  const Window& w = p.w_;
   const int S = w.S;
   const int xb = w.x_bytes, gb = w.KP * kSPitch, goff = 3 * w.x_bytes;
   const int n_my = (p.ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;      // tiles of this workgroup (>= 1)
@@ -96,38 +73,18 @@ __global__ __launch_bounds__(kNWv * 64) void conv3x1_dbn_kernel(const DbParams p
     const E* zg = (const E*)p.z;
     E* og = (E*)p.dz;
     const int xp = w.x_bytes >> 10;
-    // window DMA pieces of this wave: frame row << 20 | pixel of the segment << 8 | channel of the chunk, bit 31 = never loaded
     unsigned xq[kMaxXP];
-    int np = 0;
+    dvt_window::window_coords<F, kNH>(w, hw, lane, xq);
+    int np = 0;                                    // window pieces THIS wave requests per tile
 #pragma unroll
-    for (int i = 0; i < kMaxXP; ++i) {
-      const int piece = hw + kNH * i;
-      const int sl = piece * 64 + lane;
-      const int pos = sl / kSlots, c = sl - pos * kSlots;
-      const int tt = pos / S, sx = pos - tt * S;
-      const bool ok = piece < xp && pos < w.xpos && c < 8;
-      xq[i] = ok ? ((unsigned)tt << 20) | ((unsigned)sx << 8) | (unsigned)(c * 8) : 0x80000000u;
-      np += piece < xp ? 1 : 0;
-    }
+    for (int i = 0; i < kMaxXP; ++i) np += hw + kNH * i < xp ? 1 : 0;
     auto pix_of = [&](int j) -> int64_t {
       const int tile = blockIdx.x + j * gridDim.x;
       const int n = tile / w.segs, sg = tile - n * w.segs;
       return (int64_t)n * w.T * w.L + (int64_t)sg * S;
     };
     auto load_window = [&](int j) {
-      const int64_t pix0 = pix_of(j);
-      char* dst = smem + (j % 3) * xb;
-#pragma unroll
-      for (int i = 0; i < kMaxXP; ++i) {
-        const int piece = hw + kNH * i;
-        if (piece < xp) {                          // wave-uniform
-          const int frame = (int)((xq[i] >> 20) & 0x7FF) - 1;
-          const bool ok = (int)xq[i] >= 0 && (unsigned)frame < (unsigned)w.T;
-          const E* src = ok ? xg + (pix0 + (int64_t)frame * w.L + ((xq[i] >> 8) & 0xFFF)) * kCI + (xq[i] & 0xFF)
-                            : reinterpret_cast<const E*>(db_zero16);
-          dvt_dma16(src, dst + piece * 1024);
-        }
-      }
+      dvt_window::window_load<F, kNH>(w, xg, pix_of(j), xq, hw, smem + (j % 3) * xb);
     };
     // this thread: channel group c18 (8 channels) of the rows rr, rr + 24, ... of every tile
     const int rr = htid / kCH, c18 = htid - rr * kCH;
@@ -218,14 +175,18 @@ __global__ __launch_bounds__(kNWv * 64) void conv3x1_dbn_kernel(const DbParams p
       if (i >= 1) request_z(i, zq0);                              // (tile 0's were requested in the prologue)
       // Window i + 1 (requested in interval i - 1) must have landed before the next interval computes from it.  vmcnt retires
       // in issue order: what this interval itself has issued -- its window requests, its stores, its z rows -- may stay in flight.
-      db_wait_vm(nst + (req ? np : 0) + (i >= 1 ? NR : 0));
+      dvt_wait_vm_upto<13>(nst + (req ? np : 0) + (i >= 1 ? NR : 0));
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __syncthreads();                                            // B_{i+1}
     }
     epilogue(n_my - 1, zq0);
     if (MODE == 1) {
-      // threads with equal c18 hold the same 8 channels: fixed-order sum over the 24 row lanes -> this workgroup's partial row
-      float* red = reinterpret_cast<float*>(smem);                // [2][448][8] = 28 KiB over the windows (all reads are done)
+      // threads with equal c18 hold the same 8 channels: fixed-order sum over the 24 row lanes -> this workgroup's partial row.
+      // red = [2][448][8] floats = 28 KiB from the start of LDS: over the windows and, where three windows are shorter than
+      // that (every NB = 2 geometry), over the head of staging image 0, which other helper waves may still be reading in
+      // the epilogue above -- hence the barrier: every wave's last read of windows and staging is behind it.
+      __syncthreads();
+      float* red = reinterpret_cast<float*>(smem);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         red[(0 * kNH * 64 + htid) * 8 + k] = bs[k];
@@ -288,28 +249,8 @@ __global__ __launch_bounds__(kNWv * 64) void conv3x1_dbn_kernel(const DbParams p
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();                                              // B_{i+1}
   }
+  if (MODE == 1) __syncthreads();                                 // (the helpers' last epilogue is done: the scratch may be written)
   __syncthreads();                                                // (the helpers' statistics scratch)
-}
-
-int db_plan(int T, int L, Win* q) {
-  if (T < 1 || L < 1 || T + 2 > 2047) return 0;
-  for (int S = 16; S >= 2; --S) {
-    if (L % S || (T * S) % 32) continue;
-    const int KP = T * S, xpos = (T + 2) * S;
-    if (KP > kMaxRows * kHRows) continue;
-    const int xbytes = (xpos * kXRow + 1023) & ~1023;
-    if (3 * xbytes + 2 * KP * kSPitch + 2048 > 160 * 1024) continue;
-    if ((xbytes >> 10) > kNH * kMaxXP) continue;
-    if (3 * xbytes + 2 * KP * kSPitch < 2 * kNH * 64 * 8 * 4) continue;      // (the statistics scratch overlays the images)
-    q->T = T; q->L = L; q->S = S; q->segs = L / S; q->KP = KP; q->xpos = xpos; q->x_bytes = xbytes;
-    return 1;
-  }
-  return 0;
-}
-
-int db_grid(int64_t N, const Win& q) {
-  const int64_t ntiles = N * q.segs;
-  return (int)(ntiles < dvt_num_cus() ? ntiles : dvt_num_cus());
 }
 
 template <typename E, int NB, int MODE>
@@ -319,12 +260,9 @@ void db_launch(const DbParams& p, int grid, int lds, hipStream_t st) {
   hipLaunchKernelGGL((conv3x1_dbn_kernel<E, NB, MODE>), dim3(grid), dim3(kNWv * 64), lds, st, p);
 }
 
-// 16-position blocks of a tile: the template parameter NB (db_plan: KP is a multiple of 32, at most kMaxRows * kHRows = 96)
-int db_nb(const Win& q) { return q.KP >> 4; }
-
 template <typename E, int MODE>
 void db_dispatch(const DbParams& p, int grid, int lds, hipStream_t st) {
-  switch (db_nb(p.w_)) {
+  switch (p.w_.KP >> 4) {
     case 2: db_launch<E, 2, MODE>(p, grid, lds, st); break;
     case 4: db_launch<E, 4, MODE>(p, grid, lds, st); break;
     default: db_launch<E, 6, MODE>(p, grid, lds, st); break;
@@ -335,43 +273,31 @@ void db_dispatch(const DbParams& p, int grid, int lds, hipStream_t st) {
 
 namespace dvt_internal {
 
-int conv3x1_dbn_supported(int64_t N, int T, int L, int dtype) {
-#ifdef DVT_NO_DBN
-  return 0;
-#endif
-  Win q;
-  return N > 0 && dvt_is_16bit(dtype) && db_plan(T, L, &q) && N * q.segs < ((int64_t)1 << 31) && N * T * L * 144 < ((int64_t)1 << 31) ? 1 : 0;
+// the launcher's choice: three windows + two staging images; inst = 16-position blocks of a tile, the template parameter NB
+// (KP is a multiple of 32, at most kMaxRows * kHRows = 96: 2, 4 or 6)
+Form conv3x1_dbn_form(int64_t N, int T, int L) {
+  Window q;
+  if (N <= 0 || !dvt_window::window_plan<F>(T, L, &q, 0, 2 * kSPitch, 3, kNH * kMaxXP, 2048, kMaxRows * kHRows)) return Form{};
+  const int lds = 3 * q.x_bytes + 2 * q.KP * kSPitch;
+  // (the statistics scratch overlays the windows and, past them, the staging images -- the kernel writes it behind a barrier
+  // of its own; the whole allocation must hold it, and a shorter segment's is smaller still)
+  if (lds < 2 * kNH * 64 * 8 * 4) return Form{};
+  return dvt_window::window_form(N, q, 1, q.KP >> 4, lds, kCO);
 }
 
-// the launcher's instantiation: NB (2, 4, 6), 0 where the window kernel does not take the geometry
-int conv3x1_dbn_nb(int64_t N, int T, int L, int dtype) {
-  Win q;
-  if (!conv3x1_dbn_supported(N, T, L, dtype) || !db_plan(T, L, &q)) return 0;
-  return db_nb(q);
-}
-
-int conv3x1_dbn_parts(int64_t N, int T, int L) {
-  Win q;
-  if (N <= 0 || !db_plan(T, L, &q)) return 0;
-  return db_grid(N, q);
-}
-
-// mode 1: the sums -> partial [parts][2][144]; mode 2: the corrected gradient -> dz (loc = this launch pair's reduced sums)
-int conv3x1_dbn_pass(int mode, const void* dy, const void* w, int64_t ldw, const void* z, const float* mean, const float* invstd,
-                     const float* gamma, const float* beta, int relu, int training, float* partial, const float* loc, void* dz,
-                     int64_t N, int T, int L, int dtype, hipStream_t st) {
+// (f = conv3x1_dbn_form of the same geometry, launchable)
+void conv3x1_dbn_pass(const Form& f, int mode, const void* dy, const void* w, int64_t ldw, const void* z, const float* mean,
+                      const float* invstd, const float* gamma, const float* beta, int relu, int training, float* partial,
+                      const float* loc, void* dz, int64_t N, int dtype, hipStream_t st) {
   DbParams p{};
-  if (!db_plan(T, L, &p.w_)) return DVT_ERR_UNSUPPORTED;
+  p.w_ = f.w;
   p.dy = dy; p.w = w; p.ldw = (int)ldw; p.z = z; p.dz = dz; p.partial = partial; p.loc = loc;
   p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.relu = relu; p.training = training;
-  p.inv_rows = 1.0f / (float)(N * T * L);
+  p.inv_rows = 1.0f / (float)(N * f.w.T * f.w.L);
   p.ntiles = (int)(N * p.w_.segs);
-  const int grid = db_grid(N, p.w_);
-  const int lds = 3 * p.w_.x_bytes + 2 * p.w_.KP * kSPitch;
   const bool h = dtype == DVT_F16;
-  if (mode == 1) { h ? db_dispatch<f16, 1>(p, grid, lds, st) : db_dispatch<bf16, 1>(p, grid, lds, st); }
-  else { h ? db_dispatch<f16, 2>(p, grid, lds, st) : db_dispatch<bf16, 2>(p, grid, lds, st); }
-  return DVT_OK;
+  if (mode == 1) { h ? db_dispatch<f16, 1>(p, f.grid, f.lds, st) : db_dispatch<bf16, 1>(p, f.grid, f.lds, st); }
+  else { h ? db_dispatch<f16, 2>(p, f.grid, f.lds, st) : db_dispatch<bf16, 2>(p, f.grid, f.lds, st); }
 }
 
 }  // namespace dvt_internal

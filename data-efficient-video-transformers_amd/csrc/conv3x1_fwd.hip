@@ -32,18 +32,6 @@ struct TfParams {
   Window w_;
   Affine aff;
   int ntiles, ldw;
-  int nwin, xs;         // pipelined form: window buffers (3 or 4) and the bytes between them
-};
-
-template <typename E> struct Mma16f;
-template <> struct Mma16f<bf16> {
-  static __device__ __forceinline__ f32x4 mma(bf16x4 a, bf16x4 b, f32x4 c) {
-    typedef __attribute__((ext_vector_type(4))) short s4;
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s4, a), __builtin_bit_cast(s4, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mma16f<f16> {
-  static __device__ __forceinline__ f32x4 mma(f16x4 a, f16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
 };
 
 // A 16x16x16 MFMA whose SrcC is the vDst of the 16x16x32 MFMA issued right before it (or the reverse) is not interlocked:
@@ -87,10 +75,10 @@ __global__ __launch_bounds__(kNW * 64) void conv3x1_fwd_kernel(const TfParams p)
   AffineRegs st{};
   if (affine) window_affine_regs(p.aff, st);
   unsigned xq[kFMaxXP];
-  window_coords<kFMaxXP>(w, wid, lane, xq);
+  window_coords<Fmt144, kNW>(w, wid, lane, xq);
   auto load_tile = [&](int tile, int b) {
     const int n = tile / w.segs, sg = tile - n * w.segs;
-    window_load<E, kFMaxXP>(w, xg, (int64_t)n * w.T * w.L + (int64_t)sg * S, xq, wid, smem + b * w.x_bytes);
+    window_load<Fmt144, kNW>(w, xg, (int64_t)n * w.T * w.L + (int64_t)sg * S, xq, wid, smem + b * w.x_bytes);
   };
 
   // ---- this wave: output channels [16 u, 16 u + 16), position blocks pb0 .. pb0 + npb - 1
@@ -122,7 +110,7 @@ __global__ __launch_bounds__(kNW * 64) void conv3x1_fwd_kernel(const TfParams p)
   }
 
   float bs[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const int nst = wid * 8 < w.KP ? (w.KP - wid * 8 + 63) >> 6 : 0;        // output rows (= stores) per thread and tile, wave-uniform
+  const int nst = out64_stores(w, wid);
   int tile = blockIdx.x;
   if (tile < p.ntiles) load_tile(tile, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(kNW * 64) void conv3x1_fwd_kernel(const TfParams p)
       __builtin_amdgcn_sched_barrier(0);
       mfma_shape_fence<NPB>();
 #pragma unroll
-      for (int b = 0; b < NPB; ++b) acc[b] = Mma16f<E>::mma(wr[kt], x4[b], acc[b]);
+      for (int b = 0; b < NPB; ++b) acc[b] = Elem16<E>::mma16(wr[kt], x4[b], acc[b]);
       __builtin_amdgcn_sched_barrier(0);
       mfma_shape_fence<NPB>();                     // (the next tap's first 16x16x32 step takes the same accumulators)
     }
@@ -172,62 +160,18 @@ __global__ __launch_bounds__(kNW * 64) void conv3x1_fwd_kernel(const TfParams p)
     // of 16-pixel segments (2 x 70 KiB at 12 frames) then fit, i.e. half as many tiles -- and a tile's cost here is its
     // chain of phases more than its bytes (conv3x1_window.h)
     __syncthreads();
-    char* const stage = smem + cxo;
-#pragma unroll
-    for (int b = 0; b < NPB; ++b) {
-      V4 o;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[r] = (E)acc[b][r];
-      const int pos = (pb0 + b) * 16 + li;
-      *reinterpret_cast<V4*>(stage + pos * 128 + (((2 * u + (g >> 1)) ^ (pos & 7)) << 4) + ((g & 1) << 3)) = o;
-    }
-    __syncthreads();                               // staging complete
     {
       const int n = tile / w.segs, sg = tile - n * w.segs;
-      const int64_t pix0 = (int64_t)n * w.T * w.L + (int64_t)sg * S;
-      E* yg = (E*)p.y;
-      const int c = threadIdx.x & 7;               // this thread's 8 channels, the same for every tile
-      for (int r = threadIdx.x >> 3; r < w.KP; r += (kNW * 64) >> 3) {
-        const V8 v = *reinterpret_cast<const V8*>(stage + r * 128 + ((c ^ (r & 7)) << 4));
-        const int t = r / S, sx = r - t * S;
-        *reinterpret_cast<V8*>(yg + (pix0 + (int64_t)t * w.L + sx) * kCO + c * 8) = v;
-        if (p.bn_partial) {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const float f = (float)v[k];
-            bs[k] += f;
-            bq[k] = fmaf(f, f, bq[k]);
-          }
-        }
-      }
+      out64_tile<E, NPB>(w, smem + cxo, acc, u, g, li, pb0, (E*)p.y, (int64_t)n * w.T * w.L + (int64_t)sg * S,
+                         p.bn_partial != nullptr, bs, bq, nst);
     }
-    // the next window has landed; this tile's stores (issued behind its requests, at most two per thread: vmcnt counts in
-    // issue order) stay in flight -- waiting for them as well cost ~3 us per tile, 130 us per launch
-    if (nst == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if (nst == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if (nst == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                              // everybody is done with this tile's window and staging
     if (affine && tile + (int)gridDim.x < p.ntiles) {
       window_transform<E>(w, smem + ((it + 1) & 1) * w.x_bytes, st, p.aff.relu);
       __syncthreads();
     }
   }
-  if (p.bn_partial) {                              // threads with equal (tid & 7) hold the same 8 channels: fixed-order sum
-    float* red = reinterpret_cast<float*>(smem);   // [2][512][8] = 32 KiB over the window buffers (all reads of them are done)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      red[(0 * kNW * 64 + threadIdx.x) * 8 + k] = bs[k];
-      red[(1 * kNW * 64 + threadIdx.x) * 8 + k] = bq[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * kCO) {
-      const int stat = threadIdx.x >> 6, ch = threadIdx.x & 63, c = ch >> 3, k = ch & 7;
-      float t = 0.f;
-      for (int j = 0; j < (kNW * 64) >> 3; ++j) t += red[(stat * kNW * 64 + j * 8 + c) * 8 + k];
-      p.bn_partial[((int64_t)blockIdx.x * 2 + stat) * kCO + ch] = t;
-    }
-  }
+  if (p.bn_partial) out64_reduce(reinterpret_cast<float*>(smem), bs, bq, p.bn_partial);      // (over the window buffers)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -243,24 +187,6 @@ __global__ __launch_bounds__(kNW * 64) void conv3x1_fwd_kernel(const TfParams p)
 //                 virtual BatchNorm to window i + 1, which landed before the barrier that opened the interval.
 // Three windows + two staging images fit for 8-pixel segments (3 x 35 + 2 x 12 KiB at 12 frames); a window has a whole
 // interval to land before anybody waits for it.
-__device__ __forceinline__ void wait_vm_n(int n) {      // n is wave-uniform
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-  }
-}
-
 template <typename E, int NPB>
 __global__ __launch_bounds__(2 * kNW * 64) void conv3x1_fwd_pipe_kernel(const TfParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -270,9 +196,8 @@ __global__ __launch_bounds__(2 * kNW * 64) void conv3x1_fwd_pipe_kernel(const Tf
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const Window& w = p.w_;
   const int S = w.S;
-  // window buffers `xs` bytes apart: with four of them a window's trailing zero frame IS the next buffer's leading one (both are
-  // always zero; the request that rewrites one writes zeros over zeros), which is what lets four fit beside two staging images
-  const int xs = p.xs, nwin = p.nwin, gb = w.KP * 128, goff = (nwin - 1) * p.xs + w.x_bytes;
+  // three window buffers, then two staging images
+  const int xs = w.x_bytes, gb = w.KP * 128, goff = 3 * w.x_bytes;
   const int n_my = (p.ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;      // tiles of this workgroup (>= 1)
 
   if (wid >= kNW) {
@@ -284,16 +209,12 @@ __global__ __launch_bounds__(2 * kNW * 64) void conv3x1_fwd_pipe_kernel(const Tf
     AffineRegs st{};
     if (affine) window_affine_regs(p.aff, st, htid);
     unsigned xq[kFMaxXP];
-    window_coords<kFMaxXP>(w, hw, lane, xq);
+    window_coords<Fmt144, kNW>(w, hw, lane, xq);
     auto load_tile = [&](int j) {
       const int tile = blockIdx.x + j * gridDim.x;
       const int n = tile / w.segs, sg = tile - n * w.segs;
-      window_load<E, kFMaxXP>(w, xg, (int64_t)n * w.T * w.L + (int64_t)sg * S, xq, hw, smem + (j % nwin) * xs);
+      window_load<Fmt144, kNW>(w, xg, (int64_t)n * w.T * w.L + (int64_t)sg * S, xq, hw, smem + (j % 3) * xs);
     };
-    int np = 0;                                   // window pieces THIS wave requests per tile
-#pragma unroll
-    for (int i = 0; i < kFMaxXP; ++i) np += hw + kNW * i < (w.x_bytes >> 10) ? 1 : 0;
-    const int ahead = nwin - 1;                   // windows requested ahead of the one being computed
     float bs[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const int c = htid & 7;                       // this thread's 8 channels, the same for every tile
     // the (at most three) output rows this thread stores of every tile: element offset of row r = frame t, pixel sx of the segment
@@ -333,22 +254,19 @@ __global__ __launch_bounds__(2 * kNW * 64) void conv3x1_fwd_pipe_kernel(const Tf
     };
     load_tile(0);
     if (n_my > 1) load_tile(1);
-    if (ahead > 2 && n_my > 2) load_tile(2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                              // P0: the first windows have landed
     if (affine) window_transform<E>(w, smem, st, p.aff.relu);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();                                              // P1: window 0 is ready
     for (int i = 0; i < n_my; ++i) {
-      const bool req = i + ahead < n_my;
-      if (req) load_tile(i + ahead);                              // into the buffer tile i - 1 has left
+      if (i + 2 < n_my) load_tile(i + 2);                         // into the buffer tile i - 1 has left
       int nst = 0;
       if (i >= 1) nst = store_tile(i - 1);
-      if (affine && i + 1 < n_my) window_transform<E>(w, smem + ((i + 1) % nwin) * xs, st, p.aff.relu);
+      if (affine && i + 1 < n_my) window_transform<E>(w, smem + ((i + 1) % 3) * xs, st, p.aff.relu);
       // Window i + 2 must have landed before the next interval transforms it.  vmcnt retires in issue order: behind its
-      // requests this wave has issued (three windows ahead: the requests of window i + 3 and) this interval's stores, which
-      // may all stay in flight.
-      wait_vm_n((ahead > 2 && req ? np : 0) + nst);
+      // requests this wave has issued this interval's stores (at most three), which may all stay in flight.
+      dvt_wait_vm_upto<3>(nst);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __syncthreads();                                            // B_{i+1}
     }
@@ -397,7 +315,7 @@ __global__ __launch_bounds__(2 * kNW * 64) void conv3x1_fwd_pipe_kernel(const Tf
   __syncthreads();                                                // P0
   __syncthreads();                                                // P1
   for (int i = 0; i < n_my; ++i) {
-    const int cxo = (i % nwin) * xs;
+    const int cxo = (i % 3) * xs;
     f32x4 acc[NPB];
 #pragma unroll
     for (int b = 0; b < NPB; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -424,7 +342,7 @@ __global__ __launch_bounds__(2 * kNW * 64) void conv3x1_fwd_pipe_kernel(const Tf
       __builtin_amdgcn_sched_barrier(0);
       mfma_shape_fence<NPB>();
 #pragma unroll
-      for (int b = 0; b < NPB; ++b) acc[b] = Mma16f<E>::mma(wr[kt], x4[b], acc[b]);
+      for (int b = 0; b < NPB; ++b) acc[b] = Elem16<E>::mma16(wr[kt], x4[b], acc[b]);
       __builtin_amdgcn_sched_barrier(0);
       mfma_shape_fence<NPB>();
     }
@@ -445,37 +363,11 @@ __global__ __launch_bounds__(2 * kNW * 64) void conv3x1_fwd_pipe_kernel(const Tf
   __syncthreads();                                                // (the helpers' statistics scratch)
 }
 
-// geometry of the pipelined form: three windows + two staging images; 0 = not taken (the kernel above then)
-// -> number of window buffers (3, or 4 with shared zero frames), 0 = not taken; *xs = bytes between the buffers
-int tfp_plan(int T, int L, Window* q, int* xs) {
-#ifdef DVT_TF_NO_PIPE
-  return 0;
-#endif
-  if (!window_plan(T, L, q, 0, 2 * 128, 3, kNW * kFMaxXP)) return 0;
-  if ((q->KP >> 5) < 1 || (q->KP >> 5) > kMaxPB || 3 * q->x_bytes + 2 * q->KP * 128 < 2 * kNW * 64 * 8 * 4) return 0;
-  *xs = q->x_bytes;
-  // Three buffers.  (Measured and dropped, tools/dev/tf_probe.py on one box: FOUR buffers whose shared zero frames overlap --
-  // the kernel takes nwin / xs for it -- so that a window has two intervals to land: 147 - 150 us against 142 - 145 us; the
-  // requests were never the wait.  Transform before the stores: 149 - 155 us.  The ablations say why: without the requests
-  // 116 us, without the stores 121, without the transform 123 of 141 -- the helpers' three jobs each cost what they issue.)
-  return 3;
-}
-
 template <typename E, int NPB>
 void tfp_launch(const TfParams& p, int grid, int lds, hipStream_t st) {
   static DvtLdsAttr set;
   dvt_lds_attr(set, (const void*)conv3x1_fwd_pipe_kernel<E, NPB>, 160 * 1024);
   hipLaunchKernelGGL((conv3x1_fwd_pipe_kernel<E, NPB>), dim3(grid), dim3(2 * kNW * 64), lds, st, p);
-}
-
-int tf_plan(int T, int L, Window* q) {
-  if (!window_plan(T, L, q, 0, 0, 2, kNW * kFMaxXP)) return 0;   // (the output staging overlays a window)
-  return (q->KP >> 5) <= kMaxPB && 2 * q->x_bytes >= 2 * kNW * 64 * 8 * 4;      // (the statistics scratch overlays the windows)
-}
-
-int tf_grid(int64_t N, const Window& q) {
-  const int64_t ntiles = N * q.segs;
-  return (int)(ntiles < dvt_num_cus() ? ntiles : dvt_num_cus());
 }
 
 template <typename E, int NPB>
@@ -485,44 +377,55 @@ void tf_launch(const TfParams& p, int grid, int lds, hipStream_t st) {
   hipLaunchKernelGGL((conv3x1_fwd_kernel<E, NPB>), dim3(grid), dim3(kNW * 64), lds, st, p);
 }
 
+// The launcher's choice for the 144 -> 64 form; inst = 16-position blocks per wave (KP / 32).  The geometry is taken where the
+// form without helper waves takes it: two windows (the output staging overlays one, the statistics scratch [2][512][8]
+// both) and at most kMaxPB blocks per wave.  That cap is a check on the segment the search found, not a term of the search: a
+// geometry whose longest fitting segment makes a larger tile is refused, a shorter segment is not tried.  The pipelined form
+// (three windows + two staging images) runs instead where its buffers fit.
+Form tf_form(int64_t N, int T, int L) {
+  Window q, qp;
+  if (N <= 0 || !window_plan<Fmt144>(T, L, &q, 0, 0, 2, kNW * kFMaxXP)) return Form{};
+  if ((q.KP >> 5) > kMaxPB || 2 * q.x_bytes < 2 * kNW * 64 * 8 * 4) return Form{};
+  // Three buffers.  (Measured and dropped, tools/dev/tf_probe.py on one box: FOUR buffers whose shared zero frames overlap,
+  // so that a window has two intervals to land: 147 - 150 us against 142 - 145 us; the requests were never the wait.
+  // Transform before the stores: 149 - 155 us.  The ablations say why: without the requests 116 us, without the stores 121,
+  // without the transform 123 of 141 -- the helpers' three jobs each cost what they issue.)
+  if (window_plan<Fmt144>(T, L, &qp, 0, 2 * 128, 3, kNW * kFMaxXP) && (qp.KP >> 5) <= kMaxPB &&
+      3 * qp.x_bytes + 2 * qp.KP * 128 >= 2 * kNW * 64 * 8 * 4)
+    return window_form(N, qp, 1, qp.KP >> 5, 3 * qp.x_bytes + 2 * qp.KP * 128);
+  return window_form(N, q, 0, q.KP >> 5, 2 * q.x_bytes);
+}
+
 }  // namespace
 
 extern "C" {
 
 int dvt_conv3x1_fwd_supported(int64_t N, int T, int L, int Cin, int Cout, int dtype) {
-  if (Cin == 64 && Cout == 64) return dvt_internal::conv3x1_c64_supported(N, T, L, dtype);
-  Window q;
-  return N > 0 && Cin == kCI && Cout == kCO && dvt_is_16bit(dtype) && tf_plan(T, L, &q) && N * q.segs < ((int64_t)1 << 31) &&
-                 N * T * L < ((int64_t)1 << 31) ? 1 : 0;
+  if (Cin == 64 && Cout == 64) return dvt_internal::conv3x1_c64_form(N, T, L).launchable(dtype) ? 1 : 0;
+  return Cin == kCI && Cout == kCO && tf_form(N, T, L).launchable(dtype) ? 1 : 0;
 }
 
 int dvt_conv3x1_fwd_plan(int64_t N, int T, int L, int Cin, int Cout, int dtype, int* npb, int* pipelined) {
   DVT_REQUIRE(npb && pipelined, "dvt_conv3x1_fwd_plan: npb and pipelined are required");
   *npb = 0;
   *pipelined = 0;
-  if (Cin != kCI || !dvt_conv3x1_fwd_supported(N, T, L, Cin, Cout, dtype)) return 0;
-  Window q;
-  int xs_ = 0;
-  *pipelined = tfp_plan(T, L, &q, &xs_) != 0 ? 1 : 0;      // (the launcher's choice, as in dvt_conv3x1_fwd)
-  if (!*pipelined) tf_plan(T, L, &q);
-  *npb = q.KP >> 5;
+  const Form f = tf_form(N, T, L);
+  if (Cin != kCI || Cout != kCO || !f.launchable(dtype)) return 0;
+  *npb = f.inst;
+  *pipelined = f.pipelined;
   return 1;
 }
 
 int dvt_conv3x1_c64_plan(int64_t N, int T, int L, int dtype, int* npb) {
   DVT_REQUIRE(npb, "dvt_conv3x1_c64_plan: npb is required");
-  *npb = dvt_internal::conv3x1_c64_npb(N, T, L, dtype);
+  const Form f = dvt_internal::conv3x1_c64_form(N, T, L);
+  *npb = f.launchable(dtype) ? f.inst : 0;
   return *npb != 0 ? 1 : 0;
 }
 
 int64_t dvt_conv3x1_fwd_stats_parts(int64_t N, int T, int L, int Cin) {
-  if (Cin == 64) return dvt_internal::conv3x1_c64_stats_parts(N, T, L);
-  Window q;
-  if (N <= 0 || !tf_plan(T, L, &q)) return 0;
-  Window qp;
-  int xs_ = 0;
-  if (tfp_plan(T, L, &qp, &xs_)) q = qp;           // (the launcher's choice: the pipelined form where its buffers fit)
-  return tf_grid(N, q);                            // one partial row per workgroup of the persistent grid
+  const Form f = Cin == 64 ? dvt_internal::conv3x1_c64_form(N, T, L) : tf_form(N, T, L);
+  return f.taken ? f.grid : 0;                     // one partial row per workgroup of the persistent grid
 }
 
 int dvt_conv3x1_fwd(const void* x, const dvt_bn_affine* x_affine, const void* w, int64_t ldw, void* y, float* stats_partial,
@@ -534,24 +437,20 @@ int dvt_conv3x1_fwd(const void* x, const dvt_bn_affine* x_affine, const void* w,
   if (N == 0) return DVT_OK;
   if (Cin == 64) {                                 // the stem's temporal half (and its data gradient): conv3x1_c64.hip
     DVT_REQUIRE(!(x_affine && x_affine->mean), "dvt_conv3x1_fwd: x_affine is for the 144-channel form");
-    if (!dvt_internal::conv3x1_c64_supported(N, T, L, dtype))
+    const Form f = dvt_internal::conv3x1_c64_form(N, T, L);
+    if (!f.launchable(dtype))
       DVT_UNSUPPORTED("dvt_conv3x1_fwd (64 channels): needs a 16-bit dtype and a segment length S <= 16 with L %% S == 0, "
                       "(T * S) %% 32 == 0, T * S <= 192 and two windows + the output staging in 160 KiB of LDS");
-    const int rc = dvt_internal::conv3x1_c64_fwd(x, w, ldw, y, stats_partial, N, T, L, dtype, (hipStream_t)stream);
-    if (rc != DVT_OK) return rc;
+    dvt_internal::conv3x1_c64_fwd(f, x, w, ldw, y, stats_partial, N, dtype, (hipStream_t)stream);
     DVT_LAUNCH_CHECK("dvt_conv3x1_fwd(64 channels)");
     return DVT_OK;
   }
-  if (!dvt_conv3x1_fwd_supported(N, T, L, kCI, kCO, dtype))
+  const Form f = tf_form(N, T, L);
+  if (!f.launchable(dtype))
     DVT_UNSUPPORTED("dvt_conv3x1_fwd: needs a 16-bit dtype, 144 -> 64 channels and a segment length S <= 16 with L %% S == 0, "
                     "(T * S) %% 32 == 0, T * S <= 192 and two windows in 160 KiB of LDS");
   TfParams p{};
-  tf_plan(T, L, &p.w_);
-  Window qp;
-  int xs_ = 0;
-  const int nwin = tfp_plan(T, L, &qp, &xs_);
-  const bool pipe = nwin != 0;
-  if (pipe) { p.w_ = qp; p.nwin = nwin; p.xs = xs_; }
+  p.w_ = f.w;
   p.x = x; p.w = w; p.y = y; p.bn_partial = stats_partial; p.ldw = (int)ldw;
   p.ntiles = (int)(N * p.w_.segs);
   if (x_affine && x_affine->mean) {
@@ -560,7 +459,7 @@ int dvt_conv3x1_fwd(const void* x, const dvt_bn_affine* x_affine, const void* w,
     p.aff = Affine{x_affine->mean, x_affine->invstd, x_affine->gamma, x_affine->beta,
                    x_affine->c_valid > 0 ? x_affine->c_valid : kCI, x_affine->relu};
   }
-  const int grid = tf_grid(N, p.w_);
+  const int grid = f.grid, lds = f.lds;
   hipStream_t st = (hipStream_t)stream;
   const bool h = dtype == DVT_F16;
   // Which form takes which block count follows from the LDS budget: a tile of KP <= 96 positions has windows of at most
@@ -570,9 +469,8 @@ int dvt_conv3x1_fwd(const void* x, const dvt_bn_affine* x_affine, const void* w,
   // at KP = 128, S = 2: 3 x 43008 (132 x 320 = 42240 bytes rounded UP to 1 KiB) + 2 x 128 x 128 + 4096 = 165888 > 160 KiB only by
   // the rounding -- a change to kXRow, to that rounding or to the staging size must re-check it (the DVT_REQUIRE defaults
   // below then fire instead of launching a kernel that was not built).
-  if (pipe) {
-    const int lds = (nwin - 1) * p.xs + p.w_.x_bytes + 2 * p.w_.KP * 128;
-    switch (p.w_.KP >> 5) {
+  if (f.pipelined) {
+    switch (f.inst) {
       case 1: h ? tfp_launch<f16, 1>(p, grid, lds, st) : tfp_launch<bf16, 1>(p, grid, lds, st); break;
       case 2: h ? tfp_launch<f16, 2>(p, grid, lds, st) : tfp_launch<bf16, 2>(p, grid, lds, st); break;
       case 3: h ? tfp_launch<f16, 3>(p, grid, lds, st) : tfp_launch<bf16, 3>(p, grid, lds, st); break;
@@ -581,13 +479,7 @@ int dvt_conv3x1_fwd(const void* x, const dvt_bn_affine* x_affine, const void* w,
     DVT_LAUNCH_CHECK("dvt_conv3x1_fwd(pipelined)");
     return DVT_OK;
   }
-  const int lds = 2 * p.w_.x_bytes;
-  switch (p.w_.KP >> 5) {
-#ifdef DVT_TF_NO_PIPE
-    case 1: h ? tf_launch<f16, 1>(p, grid, lds, st) : tf_launch<bf16, 1>(p, grid, lds, st); break;
-    case 2: h ? tf_launch<f16, 2>(p, grid, lds, st) : tf_launch<bf16, 2>(p, grid, lds, st); break;
-    case 3: h ? tf_launch<f16, 3>(p, grid, lds, st) : tf_launch<bf16, 3>(p, grid, lds, st); break;
-#endif
+  switch (f.inst) {
     case 4: h ? tf_launch<f16, 4>(p, grid, lds, st) : tf_launch<bf16, 4>(p, grid, lds, st); break;
     case 5: h ? tf_launch<f16, 5>(p, grid, lds, st) : tf_launch<bf16, 5>(p, grid, lds, st); break;
     case 6: h ? tf_launch<f16, 6>(p, grid, lds, st) : tf_launch<bf16, 6>(p, grid, lds, st); break;

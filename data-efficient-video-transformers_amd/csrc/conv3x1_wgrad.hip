@@ -43,8 +43,6 @@ struct TwParams {
 
 __device__ __forceinline__ int tw_swz(int k) { return ((k >> 1) & 1) | (((k >> 3) & 1) << 1); }   // conv3x3_wgrad.hip's cw_swz
 
-template <int N> struct IntC { static constexpr int value = N; };
-
 template <typename E>
 __global__ __launch_bounds__(kNW * 64) void conv3x1_wgrad_kernel(const TwParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -67,7 +65,7 @@ __global__ __launch_bounds__(kNW * 64) void conv3x1_wgrad_kernel(const TwParams 
   // ---- per-lane coordinates of this wave's DMA pieces (fixed for the launch); dz: frame << 20 | pixel << 8 | source chunk << 1 | valid
   unsigned xq[kMaxXP];
   int zq[kMaxZP];
-  window_coords(w, wid, lane, xq);
+  window_coords<Fmt144, kNW>(w, wid, lane, xq);
   const int c16 = lane & 7;
 #pragma unroll
   for (int i = 0; i < kMaxZP; ++i) {
@@ -80,7 +78,7 @@ __global__ __launch_bounds__(kNW * 64) void conv3x1_wgrad_kernel(const TwParams 
   auto load_tile = [&](int tile, int b) {
     const int n = tile / w.segs, sg = tile - n * w.segs;
     const int64_t pix0 = (int64_t)n * w.T * w.L + (int64_t)sg * S;          // pixel (frame 0, first pixel of the segment)
-    window_load<E>(w, xg, pix0, xq, wid, smem + b * w.x_bytes);
+    window_load<Fmt144, kNW>(w, xg, pix0, xq, wid, smem + b * w.x_bytes);
 #pragma unroll
     for (int i = 0; i < kMaxZP; ++i) {
       const int piece = wid + kNW * i;
@@ -213,7 +211,7 @@ __global__ __launch_bounds__(2 * kNW * 64) void conv3x1_wgrad_pipe_kernel(const 
     if (affine) window_affine_regs(p.aff, st, htid);
     unsigned xq[kMaxXP];
     int zq[kMaxZP];
-    window_coords(w, hw, lane, xq);
+    window_coords<Fmt144, kNW>(w, hw, lane, xq);
     const int c16 = lane & 7;
 #pragma unroll
     for (int i = 0; i < kMaxZP; ++i) {
@@ -227,7 +225,7 @@ __global__ __launch_bounds__(2 * kNW * 64) void conv3x1_wgrad_pipe_kernel(const 
       const int tile = blockIdx.x + j * gridDim.x, b = j % 3;
       const int n = tile / w.segs, sg = tile - n * w.segs;
       const int64_t pix0 = (int64_t)n * w.T * w.L + (int64_t)sg * S;
-      window_load<E>(w, xg, pix0, xq, hw, smem + b * w.x_bytes);
+      window_load<Fmt144, kNW>(w, xg, pix0, xq, hw, smem + b * w.x_bytes);
 #pragma unroll
       for (int i = 0; i < kMaxZP; ++i) {
         const int piece = hw + kNW * i;
@@ -320,33 +318,14 @@ __global__ __launch_bounds__(2 * kNW * 64) void conv3x1_wgrad_pipe_kernel(const 
   }
 }
 
-// the pipelined form's geometry: three (window, gradient tile) pairs; 0 = not taken (the kernel above then)
-int twp_plan(int T, int L, Window* q) {
-#ifdef DVT_TW_NO_PIPE
-  return 0;
-#endif
-  if (!window_plan(T, L, q, 128, 0, 3)) return 0;
-  return ((q->KP * 128) >> 10) <= kNW * kMaxZP;
-}
-
-// pixels per segment and the image sizes for T frames of L pixels (two windows + two dz tiles + the affine table in LDS)
-int tw_plan_two(int T, int L, Window* q) {
-  if (!window_plan(T, L, q, 128, 0, 2)) return 0;
-  return ((q->KP * 128) >> 10) <= kNW * kMaxZP;
-}
-
-// the launcher's choice: the pipelined form where its buffers fit (*pipe = 1), else the two-buffer kernel
-int tw_plan(int T, int L, Window* q, int* pipe = nullptr) {
-  int dummy;
-  if (!pipe) pipe = &dummy;
-  *pipe = twp_plan(T, L, q);
-  if (*pipe) return 1;
-  return tw_plan_two(T, L, q);
-}
-
-int tw_grid(int64_t N, const Window& q) {
-  const int64_t ntiles = N * q.segs;
-  return (int)(ntiles < dvt_num_cus() ? ntiles : dvt_num_cus());
+// The launcher's choice: the pipelined form (three (window, gradient tile) pairs) where its buffers fit, else the two-buffer
+// kernel (two pairs); the gradient tile [KP][64] is carried as at most kNW * kMaxZP DMA pieces.  No instantiation parameter.
+Form tw_form(int64_t N, int T, int L) {
+  Window q;
+  for (int nbuf = 3; nbuf >= 2; --nbuf)
+    if (window_plan<Fmt144>(T, L, &q, 128, 0, nbuf, kNW * kMaxXP) && ((q.KP * 128) >> 10) <= kNW * kMaxZP)
+      return N > 0 ? window_form(N, q, nbuf == 3, 0, nbuf * (q.x_bytes + q.KP * 128)) : Form{};
+  return Form{};
 }
 
 }  // namespace
@@ -354,24 +333,21 @@ int tw_grid(int64_t N, const Window& q) {
 extern "C" {
 
 int dvt_conv3x1_wgrad_supported(int64_t N, int T, int L, int Cin, int Cout, int dtype) {
-  Window q;
-  return N > 0 && Cin == kCI && Cout == kCO && dvt_is_16bit(dtype) && tw_plan(T, L, &q) && N * q.segs < ((int64_t)1 << 31) &&
-                 N * T * L < ((int64_t)1 << 31) ? 1 : 0;
+  return Cin == kCI && Cout == kCO && tw_form(N, T, L).launchable(dtype) ? 1 : 0;
 }
 
 int dvt_conv3x1_wgrad_plan(int64_t N, int T, int L, int Cin, int Cout, int dtype, int* pipelined) {
   DVT_REQUIRE(pipelined, "dvt_conv3x1_wgrad_plan: pipelined is required");
   *pipelined = 0;
-  if (!dvt_conv3x1_wgrad_supported(N, T, L, Cin, Cout, dtype)) return 0;
-  Window q;
-  tw_plan(T, L, &q, pipelined);                       // (the launcher's choice, as in dvt_conv3x1_wgrad)
+  const Form f = tw_form(N, T, L);
+  if (Cin != kCI || Cout != kCO || !f.launchable(dtype)) return 0;
+  *pipelined = f.pipelined;
   return 1;
 }
 
 size_t dvt_conv3x1_wgrad_workspace_bytes(int64_t N, int T, int L) {
-  Window q;
-  if (N <= 0 || !tw_plan(T, L, &q)) return 0;
-  return (size_t)tw_grid(N, q) * kM * kCO * sizeof(float);
+  const Form f = tw_form(N, T, L);
+  return f.taken ? (size_t)f.grid * kM * kCO * sizeof(float) : 0;
 }
 
 int dvt_conv3x1_wgrad(const void* x, const dvt_bn_affine* x_affine, const void* dz, float* dw, void* workspace, int64_t N, int T,
@@ -380,12 +356,12 @@ int dvt_conv3x1_wgrad(const void* x, const dvt_bn_affine* x_affine, const void* 
   DVT_REQUIRE(dvt_aligned16(x) && dvt_aligned16(dz) && dvt_aligned16(dw) && dvt_aligned16(workspace),
               "dvt_conv3x1_wgrad: buffers must be 16-byte aligned");
   DVT_REQUIRE(!defer_reduce || pending, "dvt_conv3x1_wgrad: defer_reduce needs a pending descriptor to fill");
-  if (!dvt_conv3x1_wgrad_supported(N, T, L, kCI, kCO, dtype))
+  const Form f = tw_form(N, T, L);
+  if (!f.launchable(dtype))
     DVT_UNSUPPORTED("dvt_conv3x1_wgrad: needs a 16-bit dtype, 144 -> 64 channels and a segment length S <= 16 with L %% S == 0, "
                     "(T * S) %% 32 == 0 and two (window + gradient tile) pairs in 160 KiB of LDS");
   TwParams p{};
-  int pipe = 0;
-  tw_plan(T, L, &p.w, &pipe);
+  p.w = f.w;
   p.x = x; p.dz = dz; p.slab = (float*)workspace;
   p.z_bytes = p.w.KP * 128;
   p.ntiles = (int)(N * p.w.segs);
@@ -395,28 +371,27 @@ int dvt_conv3x1_wgrad(const void* x, const dvt_bn_affine* x_affine, const void* 
     p.aff = Affine{x_affine->mean, x_affine->invstd, x_affine->gamma, x_affine->beta,
                    x_affine->c_valid > 0 ? x_affine->c_valid : kCI, x_affine->relu};
   }
-  const int grid = tw_grid(N, p.w);
+  const int grid = f.grid;
   hipStream_t st = (hipStream_t)stream;
-  if (pipe) {
-    const int lds3 = 3 * (p.w.x_bytes + p.z_bytes);
+  if (f.pipelined) {
     if (dtype == DVT_BF16) {
       static DvtLdsAttr set;
       dvt_lds_attr(set, (const void*)conv3x1_wgrad_pipe_kernel<bf16>, 160 * 1024);
-      hipLaunchKernelGGL((conv3x1_wgrad_pipe_kernel<bf16>), dim3(grid), dim3(2 * kNW * 64), lds3, st, p);
+      hipLaunchKernelGGL((conv3x1_wgrad_pipe_kernel<bf16>), dim3(grid), dim3(2 * kNW * 64), f.lds, st, p);
     } else {
       static DvtLdsAttr set;
       dvt_lds_attr(set, (const void*)conv3x1_wgrad_pipe_kernel<f16>, 160 * 1024);
-      hipLaunchKernelGGL((conv3x1_wgrad_pipe_kernel<f16>), dim3(grid), dim3(2 * kNW * 64), lds3, st, p);
+      hipLaunchKernelGGL((conv3x1_wgrad_pipe_kernel<f16>), dim3(grid), dim3(2 * kNW * 64), f.lds, st, p);
     }
   } else
   if (dtype == DVT_BF16) {
     static DvtLdsAttr set;
     dvt_lds_attr(set, (const void*)conv3x1_wgrad_kernel<bf16>, 160 * 1024);
-    hipLaunchKernelGGL((conv3x1_wgrad_kernel<bf16>), dim3(grid), dim3(kNW * 64), 2 * (p.w.x_bytes + p.z_bytes), st, p);
+    hipLaunchKernelGGL((conv3x1_wgrad_kernel<bf16>), dim3(grid), dim3(kNW * 64), f.lds, st, p);
   } else {
     static DvtLdsAttr set;
     dvt_lds_attr(set, (const void*)conv3x1_wgrad_kernel<f16>, 160 * 1024);
-    hipLaunchKernelGGL((conv3x1_wgrad_kernel<f16>), dim3(grid), dim3(kNW * 64), 2 * (p.w.x_bytes + p.z_bytes), st, p);
+    hipLaunchKernelGGL((conv3x1_wgrad_kernel<f16>), dim3(grid), dim3(kNW * 64), f.lds, st, p);
   }
   DVT_LAUNCH_CHECK("dvt_conv3x1_wgrad");
   // the slabs are summed by the family's split-K reduce, which scatters [tap * 144 + ci][co] into the parameter's [co][ci][3]

@@ -45,7 +45,7 @@
 //   * epilogue: 16 pixels at a time through LDS, whole pixel rows stored; 144-wide outputs carry the column sums / sums of
 //     squares of the stored values for the BatchNorm that follows (one partial row per compute wave and workgroup), 64-wide
 //     outputs the optional second gradient path (residual) of the data gradient.
-#include "common.h"
+#include "conv3x1_window.h"
 
 namespace {
 
@@ -93,19 +93,7 @@ struct StreamParams {
 
 __device__ __attribute__((aligned(16))) unsigned int conv3s_zero16[4] = {0u, 0u, 0u, 0u};
 
-template <typename E> struct Mma16;
-template <> struct Mma16<bf16> {
-  static __device__ __forceinline__ f32x4 mma(bf16x4 a, bf16x4 b, f32x4 c) {
-    typedef __attribute__((ext_vector_type(4))) short s4;
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s4, a), __builtin_bit_cast(s4, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mma16<f16> {
-  static __device__ __forceinline__ f32x4 mma(f16x4 a, f16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-  }
-};
-
+// (sparse: the counts a batch schedule can ask for -- not the dense dvt_wait_vm_upto of common.h)
 __device__ __forceinline__ void wait_vm(int n) {
   switch (n) {
     case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
@@ -445,7 +433,7 @@ __global__ __launch_bounds__(512) void conv3x3_stream_kernel(const StreamParams 
 #pragma unroll
           for (int u = 0; u < NB; ++u)
 #pragma unroll
-            for (int t = 0; t < 2; ++t) acc[u][t] = Mma16<E>::mma(wf4[u], xf4[t], acc[u][t]);
+            for (int t = 0; t < 2; ++t) acc[u][t] = Elem16<E>::mma16(wf4[u], xf4[t], acc[u][t]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -651,11 +639,11 @@ int params_t(StreamParams* p, Plan* pl, int64_t N, int T, int L) {
   return 1;
 }
 
-// which kernel takes dvt_conv3x1_stream_bn_bwd: the window kernel with helper waves where it takes the geometry (*nb = its
-// position blocks per tile), else the streamed-weight kernel's MODE 1 / 2 (*nb = 0)
-int bn_bwd_route(int64_t N, int T, int L, int dtype, int* nb) {
-  *nb = dvt_internal::conv3x1_dbn_nb(N, T, L, dtype);
-  return *nb ? DVT_CONV3X1_BN_BWD_WINDOW : DVT_CONV3X1_BN_BWD_STREAM;
+// which kernel takes dvt_conv3x1_stream_bn_bwd: the window kernel with helper waves where it takes the launch -- its form
+// (inst = position blocks per tile) -- else a form not taken: the streamed-weight kernel's MODE 1 / 2 runs
+dvt_window::Form bn_bwd_route(int64_t N, int T, int L, int dtype) {
+  const dvt_window::Form f = dvt_internal::conv3x1_dbn_form(N, T, L);
+  return f.launchable(dtype) ? f : dvt_window::Form{};
 }
 
 }  // namespace
@@ -678,7 +666,9 @@ int dvt_conv3x1_stream_bn_bwd_plan(int64_t N, int T, int L, int dtype, int* kern
   *kernel = DVT_CONV3X1_BN_BWD_NONE;
   *nb = 0;
   if (!dvt_conv3x1_stream_supported(N, T, L, 64, 144, dtype)) return 0;
-  *kernel = bn_bwd_route(N, T, L, dtype, nb);
+  const dvt_window::Form f = bn_bwd_route(N, T, L, dtype);
+  *kernel = f.taken ? DVT_CONV3X1_BN_BWD_WINDOW : DVT_CONV3X1_BN_BWD_STREAM;
+  *nb = f.inst;
   return 1;
 }
 
@@ -776,21 +766,18 @@ int dvt_conv3x1_stream_bn_bwd(const void* dy, const void* w, const void* z, cons
   if (!dvt_conv3x1_stream_supported(N, T, L, 64, 144, dtype))
     DVT_UNSUPPORTED("dvt_conv3x1_stream_bn_bwd: needs a 16-bit dtype and a divisor of L that fills half a 224-pixel tile");
   hipStream_t st0 = (hipStream_t)stream;
-  int nb_ = 0;
-  if (bn_bwd_route(N, T, L, dtype, &nb_) == DVT_CONV3X1_BN_BWD_WINDOW) {
+  const dvt_window::Form f = bn_bwd_route(N, T, L, dtype);
+  if (f.taken) {
     // the window kernel with helper waves (conv3x1_dbn.hip): one partial row per workgroup
     float* part0 = (float*)workspace;
     float* loc0 = part0 + (size_t)dvt_num_cus() * kNC * 2 * 144;
-    const int parts = dvt_internal::conv3x1_dbn_parts(N, T, L);
-    int rc = dvt_internal::conv3x1_dbn_pass(1, dy, w, 3 * 64, z, bn->mean, bn->invstd, bn->gamma, bn->beta, bn->relu, training, part0,
-                                            nullptr, nullptr, N, T, L, dtype, st0);
-    if (rc != DVT_OK) return rc;
+    dvt_internal::conv3x1_dbn_pass(f, 1, dy, w, 3 * 64, z, bn->mean, bn->invstd, bn->gamma, bn->beta, bn->relu, training, part0,
+                                   nullptr, nullptr, N, dtype, st0);
     DVT_LAUNCH_CHECK("dvt_conv3x1_stream_bn_bwd(window sums)");
-    dvt_internal::bn_bwd_finalize(st0, part0, parts, 144, loc0, accumulate, dgamma, dbeta, 144);
+    dvt_internal::bn_bwd_finalize(st0, part0, f.grid, 144, loc0, accumulate, dgamma, dbeta, 144);
     DVT_LAUNCH_CHECK("dvt_conv3x1_stream_bn_bwd(finalize)");
-    rc = dvt_internal::conv3x1_dbn_pass(2, dy, w, 3 * 64, z, bn->mean, bn->invstd, bn->gamma, bn->beta, bn->relu, training, nullptr,
-                                        loc0, dz, N, T, L, dtype, st0);
-    if (rc != DVT_OK) return rc;
+    dvt_internal::conv3x1_dbn_pass(f, 2, dy, w, 3 * 64, z, bn->mean, bn->invstd, bn->gamma, bn->beta, bn->relu, training, nullptr,
+                                   loc0, dz, N, dtype, st0);
     DVT_LAUNCH_CHECK("dvt_conv3x1_stream_bn_bwd(window apply)");
     return DVT_OK;
   }

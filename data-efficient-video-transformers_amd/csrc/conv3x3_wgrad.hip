@@ -57,8 +57,6 @@ __device__ __forceinline__ int cw_tail_slot(int k) { return (k & ~12) | ((k & 4)
 // MB: output-channel blocks of 16 this launch computes (4: a whole 64-channel group; 5: the last 80 of a 144-wide dz -- a
 // 16-channel launch of its own re-staged every input patch for a ninth of the work, 70 us against the group's 115; 1: a
 // 16-channel tail).  The slab rows are SN = 80 floats for MB = 5, else 64.
-template <int N> struct IntC { static constexpr int value = N; };
-
 template <typename E, int MB>
 __global__ __launch_bounds__(kNW * 64) void conv3x3_c64_wgrad_kernel(const CwParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];

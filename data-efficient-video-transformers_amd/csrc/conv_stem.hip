@@ -45,26 +45,6 @@ struct StemParams {
 
 __device__ __attribute__((aligned(16))) unsigned int stem_zero16[4] = {0u, 0u, 0u, 0u};
 
-__device__ __forceinline__ void wait_vm_upto(int n) {      // n is wave-uniform, 0 .. 14
-  switch (n) {
-    case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-
 template <typename E>
 __global__ __launch_bounds__(kNW * 64) void conv_stem_kernel(const StemParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -185,7 +165,7 @@ __global__ __launch_bounds__(kNW * 64) void conv_stem_kernel(const StemParams p)
     }
     // the next patch has landed: its requests were issued BEFORE this tile's stores and vmcnt retires in issue order, so the
     // stores (at most 14 per lane) may stay in flight
-    if (more) wait_vm_upto(nstores);
+    if (more) dvt_wait_vm_upto<14>(nstores);
     __syncthreads();
   }
   if (p.bn_partial) {                              // lanes with equal (lane & 7) hold the same 8 channels: fixed-order sum

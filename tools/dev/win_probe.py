@@ -22,6 +22,8 @@ wp_s = ops.conv_weight_pack(w_s, ops.conv2d_implicit_k(64, 144, (3, 3)), dt)
 wd_s = ops.conv_weight_pack_dgrad(w_s, dt)
 w_c = torch.randn(64, 64, 3, 3, device="cuda") * 0.04
 wp_c = ops.conv_weight_pack(w_c, ops.conv2d_implicit_k(64, 64, (3, 3)), dt)
+w_m = torch.randn(64, 64, 3, 1, device="cuda") * 0.07                # temporal 64 -> 64 (the stem's temporal half)
+wp_m = ops.conv_weight_pack(w_m, ops.conv2d_implicit_k(64, 64, (3, 1)), dt)
 dw_t = torch.empty(64, 144, 3, 1, device="cuda")
 dw_s = torch.empty(144, 64, 3, 3, device="cuda")
 NF = N * T
@@ -30,6 +32,7 @@ NF = N * T
 def one(i):
     a, b = x144[i & 1], x64[i & 1]
     ops.conv3x1_fwd(a, wp_t, N, T, Lp, want_stats=True, affine=aff)                      # conv3x1_fwd_kernel
+    ops.conv3x1_fwd(b, wp_m, N, T, Lp, want_stats=True)                                  # conv3x1_c64_kernel
     p = ops.conv3x1_wgrad(a, b, N, T, Lp, dw_t, defer_reduce=True, affine=aff); p.valid = 0   # conv3x1_wgrad_kernel
     ops.conv3x1_stream_bn_bwd(b, wd_t, a, aff, N, T, Lp, True)                           # conv3x3_stream<64,144,3,1/2>
     ops.conv3x3_stream(b, wp_s, NF, H, W, 64, 144, want_stats=True)                      # conv3x3_stream<64,144,9>
