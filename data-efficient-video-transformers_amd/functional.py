@@ -2548,3 +2548,10 @@ def mlp_chain(x: Tensor, layers, *, segments: int = 1, training: bool = True, re
 def contrastive_loss_rows(reps: Tensor, temperature: float) -> Tensor:
     """ContrastiveLoss on reps = cat(z_i, z_j) [2B, D] already in one tensor (the two views of ``step_views``)."""
     return _Contrastive.apply(reps, temperature)
+
+
+# ------------------------------------------------------------------ class-activation maps (csrc/cam.hip; dvt_amd/cam.py)
+# Post-processing of a finished backward: nothing here is differentiated, so the functional layer hands the raw operators on.
+cam_seed = ops.cam_seed
+cam_map = ops.cam_map
+cam_render = ops.cam_render

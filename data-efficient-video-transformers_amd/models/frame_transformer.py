@@ -395,6 +395,33 @@ class FrameTransformer(LightningModule):
         self._accumulate(data, batch[0])
         return loss
 
+    def explain(self, vid, targets=None, target_layer=None, method="gradcam", scale=True):
+        """Class-activation volumes of the video encoder for a genre logit (the reference's Grad-CAM pass, main.py:93-108,
+        taken through the whole model): vid [B, S, frame_len, 3, clip, clip] -> [B, tokens, frame_len, clip, clip], fp32, the
+        maps of all S + 1 chunk rows (row 0 is the learnable CLS clip).  The gradient of the chosen logit -- ``targets``: None
+        (each sample's argmax), a list of ``cam.ClassifierOutputTarget`` or a device int tensor [B] -- passes through head,
+        transformer, positional table and ``fc`` to each chunk's tapped activation; ``target_layer`` defaults to
+        ``vid_model.backbone.layer4[-1]``; ``method``: gradcam / gradcam++ / xgradcam; ``scale=False`` returns the unscaled
+        maps, which keep the chunks comparable.  Mode ``vid`` only.  Runs in eval(); the train / eval mode is restored."""
+        from .. import cam as _cam
+        if self.hparams.model != "vid":
+            raise NotImplementedError(f"explain: built for mode 'vid' (the video branch alone), not {self.hparams.model!r}")
+        bb = getattr(self.vid_model, "backbone", None)
+        if bb is None:
+            raise NotImplementedError("explain: the video encoder is not the R(2+1)D VidResNet")
+        if method not in _cam.CAM_CLASSES:
+            raise ValueError(f"explain: unknown method {method!r} (one of {sorted(_cam.CAM_CLASSES)})")
+        if vid.dim() != 6:
+            raise ValueError("explain: expected chunks [B, S, frame_len, 3, H, W]")
+        was_training = self.training
+        try:
+            maps = _cam.CAM_CLASSES[method](self, [bb.layer4[-1] if target_layer is None else target_layer])(
+                (None, vid), targets, scale=scale)
+        finally:
+            self.train(was_training)
+        B = vid.shape[0]
+        return maps.view((B, maps.shape[0] // B) + tuple(maps.shape[1:]))
+
     def test_epoch(self, batches, callback=None):
         """The reference's ``trainer.test(model, ...)`` (main.py:111) in one call: ``test_step`` over ``batches`` with the
         module in eval() under torch.inference_mode() (as Lightning runs it: the R(2+1)D encoder takes its folded inference

@@ -256,6 +256,11 @@ def _clip_ndhwc8(x, dt):
 class VideoResNet(nn.Module):
     """block / conv_makers / stem: torchvision's VideoResNet arguments (defaults: R(2+1)D-18)."""
 
+    # class-activation tap (dvt_amd/cam.py): the name of one block ("layer4.1") whose output ``features`` makes a leaf of the
+    # autograd graph and leaves in ``cam_tapped``; None (always, outside a CAM call): ``features`` runs as it does without one
+    cam_tap = None
+    cam_tapped = None
+
     def __init__(self, layers=(2, 2, 2, 2), num_classes=400, *, compute_dtype=torch.bfloat16, block=None, conv_makers=None,
                  stem=None):
         super().__init__()
@@ -296,10 +301,22 @@ class VideoResNet(nn.Module):
         """x [N, 3, T, H, W] -> pooled [N, 512]."""
         if x.dim() != 5 or x.shape[1] != 3:
             raise ValueError("VideoResNet expects clips [N, 3, T, H, W]")
+        if self.cam_tap is not None:
+            return self._features_tapped(x)
         if isinstance(self.stem, BasicStem):
             return self._features_3d(x)
         if inference_route(self):
             return self.features_folded(x)
+        fm = self._stem_ndhwc(x)
+        dt = self.compute_dtype
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in layer:
+                fm = blk.forward_ndhwc(fm, dt)
+        y, N, T, H, W = fm
+        return F.mean_rows(y.view(N, T * H * W, y.shape[1]))          # AdaptiveAvgPool3d(1)
+
+    def _stem_ndhwc(self, x):
+        """R2Plus1dStem on the training kernels' route: clips [N, 3, T, H, W] -> the NDHWC map (y, N, T, H1, W1)."""
         dt = self.compute_dtype
         N, _, T, H, W = x.shape
         frames = x.permute(0, 2, 1, 3, 4)                  # [N, T, 3, H, W]: per-frame NCHW
@@ -314,12 +331,36 @@ class VideoResNet(nn.Module):
         y = F.conv_bn_act_raw(frames.view(N * T, 3, H, W), s0.weight, b0, (N * T, 3, H, W, True), k, s, p, relu=True, dtype=dt,
                               cpad=CPAD, dx_frames=dx_frames)
         H1, W1 = (H + 2 * p[0] - k[0]) // s[0] + 1, (W + 2 * p[1] - k[1]) // s[1] + 1
-        fm = _temporal((y, N, T, H1, W1), s3, b3, True, dt)
-        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
-            for blk in layer:
+        return _temporal((y, N, T, H1, W1), s3, b3, True, dt)
+
+    def _features_tapped(self, x):
+        """``features`` with a class-activation tap (dvt_amd/cam.py): ``cam_tap`` names a block ("layer4.1").  Everything up to
+        and including that block runs without autograd; the block's output becomes a leaf and is left, with its geometry, in
+        ``cam_tapped`` = (y [N*T*H*W, C], N, T, H, W); the rest runs with autograd.  A backward from the result therefore stops
+        at the tap: nothing upstream is saved and no weight gradient is formed upstream."""
+        if isinstance(self.stem, BasicStem):
+            raise NotImplementedError("cam_tap: only the R(2+1)D tree carries a class-activation tap (r3d_18 does not)")
+        if self.training:
+            raise RuntimeError("cam_tap: class-activation maps are taken on running statistics: put the module in eval()")
+        blocks = [(f"layer{i + 1}.{j}", blk) for i, layer in enumerate((self.layer1, self.layer2, self.layer3, self.layer4))
+                  for j, blk in enumerate(layer)]
+        names = [n for n, _ in blocks]
+        if self.cam_tap not in names:
+            raise ValueError(f"cam_tap {self.cam_tap!r} names no block of this network (one of {names})")
+        cut = names.index(self.cam_tap) + 1
+        dt = self.compute_dtype
+        with torch.no_grad():
+            fm = self._stem_ndhwc(x)
+            for _, blk in blocks[:cut]:
                 fm = blk.forward_ndhwc(fm, dt)
         y, N, T, H, W = fm
-        return F.mean_rows(y.view(N, T * H * W, y.shape[1]))          # AdaptiveAvgPool3d(1)
+        y = y.detach().requires_grad_()
+        self.cam_tapped = fm = (y, N, T, H, W)
+        with torch.enable_grad():
+            for _, blk in blocks[cut:]:
+                fm = blk.forward_ndhwc(fm, dt)
+            out, N, T, H, W = fm
+            return F.mean_rows(out.view(N, T * H * W, out.shape[1]))          # AdaptiveAvgPool3d(1)
 
     def _features_3d(self, x):
         """Full-3-D tree (r3d_18): every convolution one dvt_conv3d_implicit launch; eval mode, no autograd."""

@@ -2747,3 +2747,98 @@ def vggish_conv1_pool(x: Tensor, w: Tensor, bias: Tensor) -> Tensor:
         L.check(L.load().dvt_vggish_conv1_pool(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), N, H, W, dt(x),
                                                _stream()), "dvt_vggish_conv1_pool")
     return y
+
+
+# ------------------------------------------------------------------ class-activation maps (csrc/cam.hip)
+CAM_METHODS = {"gradcam": L.ENUMS["dvt_cam_method"]["DVT_CAM_GRADCAM"],
+               "gradcam++": L.ENUMS["dvt_cam_method"]["DVT_CAM_GRADCAMPP"],
+               "xgradcam": L.ENUMS["dvt_cam_method"]["DVT_CAM_XGRADCAM"]}
+_cam_jet = {}
+
+
+def cam_seed(logits: Tensor, category: Optional[Tensor] = None) -> Tensor:
+    """logits [B, K] -> the backward seed [B, K] in the logits' dtype (dvt_cam_seed): one-hot at category[b] (device int32 [B])
+    or at the row's argmax where category is None or the entry negative (ties to the lowest index).  No host synchronisation."""
+    _need_cuda(logits, category)
+    if logits.dim() != 2 or logits.shape[1] == 0:
+        raise TypeError("cam_seed: expected logits [B, K]")
+    if category is not None and (category.dtype != torch.int32 or category.dim() != 1 or category.shape[0] != logits.shape[0]):
+        raise TypeError("cam_seed: category must be an int32 tensor [B]")
+    logits = logits.contiguous()
+    category = None if category is None else category.contiguous()
+    B, K = logits.shape
+    seed = torch.empty_like(logits)
+    L.check(L.load().dvt_cam_seed(logits.data_ptr(), _p(category), seed.data_ptr(), B, K, dt(logits), _stream()), "dvt_cam_seed")
+    return seed
+
+
+def cam_map_launches(P: int, C: int) -> int:
+    """Launches dvt_cam_map takes at P positions of C channels: 1 (a workgroup owns a clip's block) or 3.  Host only."""
+    return int(L.load().dvt_cam_map_launches(int(P), int(C)))
+
+
+def cam_map(A: Tensor, G: Tensor, method: str = "gradcam", want_weights: bool = False, want_raw: bool = False):
+    """Activation A and gradient G [N, P, C] (channels last, one dtype, C a multiple of 8) -> (scaled [N, P], raw [N, P] or
+    None, weights [N, C] or None), all f32 (dvt_cam_map).  method: one of CAM_METHODS."""
+    if method not in CAM_METHODS:
+        raise ValueError(f"cam_map: unknown method {method!r} (one of {sorted(CAM_METHODS)})")
+    _need_cuda(A, G)
+    if A.dim() != 3 or A.shape != G.shape or A.dtype != G.dtype:
+        raise TypeError("cam_map: expected A and G [N, P, C] of one shape and dtype")
+    if A.shape[2] % 8 != 0:
+        raise ValueError("cam_map: the channel count must be a multiple of 8")
+    A, G = A.contiguous(), G.contiguous()
+    N, P, C = A.shape
+    scaled = torch.empty((N, P), dtype=torch.float32, device=A.device)
+    raw = torch.empty((N, P), dtype=torch.float32, device=A.device) if want_raw else None
+    weights = torch.empty((N, C), dtype=torch.float32, device=A.device) if want_weights else None
+    if N == 0 or P == 0:
+        return scaled, raw, weights
+    lib = L.load()
+    nbytes = int(lib.dvt_cam_map_workspace_bytes(N, P, C))
+    ws = workspace(nbytes, A.device)
+    with _timed("cam_map", 2 * A.numel() * A.element_size()):
+        L.check(lib.dvt_cam_map(A.data_ptr(), G.data_ptr(), N, P, C, dt(A), CAM_METHODS[method], _p(weights), _p(raw),
+                                scaled.data_ptr(), _p(ws), nbytes, _stream()), "dvt_cam_map")
+    return scaled, raw, weights
+
+
+def cam_jet_table_host() -> Tensor:
+    """The JET colour table as dvt_cam_jet_table builds it (float64 on the host) -> uint8 CPU tensor [256, 3], RGB."""
+    t = torch.empty((256, 3), dtype=torch.uint8)
+    L.check(L.load().dvt_cam_jet_table(t.data_ptr(), t.numel()), "dvt_cam_jet_table")
+    return t
+
+
+def cam_render(scaled: Tensor, size, frames: Optional[Tensor] = None, use_rgb: bool = False, image_weight: float = 0.5,
+               want_mask: bool = True):
+    """scaled f32 [N, T', H', W'] -> (mask f32 [N, T, H, W] or None, overlay uint8 [N, T, H, W, 3] or None) with size =
+    (T, H, W) (dvt_cam_render): trilinear upsample with half-pixel centres and, with frames ([N, T, H, W, 3], uint8, or f32
+    in [0, 1]), the JET overlay of show_cam_on_image in the same launch.  The table is uploaded once per device."""
+    _need_cuda(scaled, frames)
+    if scaled.dim() != 4 or scaled.dtype != torch.float32:
+        raise TypeError("cam_render: expected f32 maps [N, T', H', W']")
+    T, H, W = (int(v) for v in size)
+    N, Ti, Hi, Wi = scaled.shape
+    if min(T, H, W) <= 0:
+        raise ValueError("cam_render: size must be positive (T, H, W)")
+    if frames is None and not want_mask:
+        raise ValueError("cam_render: nothing to compute (no frames and no mask)")
+    scaled = scaled.contiguous()
+    mask = torch.empty((N, T, H, W), dtype=torch.float32, device=scaled.device) if want_mask else None
+    overlay = jet = None
+    if frames is not None:
+        if frames.dtype not in (torch.uint8, torch.float32) or tuple(frames.shape) != (N, T, H, W, 3):
+            raise TypeError(f"cam_render: frames must be uint8 or f32 [N, T, H, W, 3] = {(N, T, H, W, 3)}")
+        frames = frames.contiguous()
+        overlay = torch.empty((N, T, H, W, 3), dtype=torch.uint8, device=scaled.device)
+        jet = _cam_jet.get(scaled.device)
+        if jet is None:
+            jet = _cam_jet[scaled.device] = cam_jet_table_host().to(scaled.device)
+    if N == 0 or min(Ti, Hi, Wi) == 0:
+        return mask, overlay
+    with _timed("cam_render", scaled.numel() * 4 + N * T * H * W * (4 + (6 if frames is not None else 0))):
+        L.check(L.load().dvt_cam_render(scaled.data_ptr(), N, Ti, Hi, Wi, T, H, W, _p(mask), _p(frames),
+                                        int(frames is not None and frames.dtype == torch.float32), _p(jet), _p(overlay),
+                                        float(image_weight), int(bool(use_rgb)), _stream()), "dvt_cam_render")
+    return mask, overlay

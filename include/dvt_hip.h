@@ -1281,6 +1281,49 @@ int dvt_logmel_examples(const float* wave, int64_t R, int64_t L, const float* ta
 int dvt_vggish_conv1_pool(const void* x, const float* w, const float* bias, void* y, int64_t N, int H, int W, int dtype,
                           dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- class-activation maps (Grad-CAM) of the video encoder
+ * Additions within ABI v5.  What the reference does with the pytorch_grad_cam library at src/main.py:93-108, on the device;
+ * csrc/cam.hip.  All three entry points run asynchronously on `stream`, use only the caller's buffers, sum in fp32 in a fixed
+ * order without atomics (identical calls give bitwise-equal results) and launch nothing for N == 0 (B == 0).
+ *   dvt_cam_seed: logits [B][K] of `dtype` -> seed [B][K] of `dtype`, one-hot at category[b] (device int32 [B]), or at the
+ *     row's argmax (ties to the lowest index, as numpy.argmax) where `category` is NULL or the entry negative; an entry >= K
+ *     leaves the row zero.  No host synchronisation.
+ *   dvt_cam_map: activation A and gradient G [N][P][C] of `dtype`, channels last, P = T' H' W', C a multiple of 8 and at most
+ *     DVT_CAM_MAX_C, both 16-byte aligned -> weights f32 [N][C] (optional), raw f32 [N][P] (optional), scaled f32 [N][P].
+ *       DVT_CAM_GRADCAM    w = (1 / P) sum_p G
+ *       DVT_CAM_XGRADCAM   w = sum_p G A / (sum_p A + 1e-7)
+ *       DVT_CAM_GRADCAMPP  w = sum_p max(G, 0) a,  a = G^2 / (2 G^2 + S G^3 + 1e-6) (0 where G == 0),  S = sum_p A
+ *     raw = max(sum_c w A, 0);  scaled = (raw - min_p raw) / (1e-7 + max_p (raw - min_p raw)) per clip (the library's
+ *     scale_cam_image); an all-zero raw row gives an all-zero scaled row.
+ *     Launches: ONE, one workgroup per clip, where P <= DVT_CAM_FUSED_MAX_P and P * C <= DVT_CAM_FUSED_MAX_ELEMS (layer 4 at
+ *     2*7*7 x 512, layer 3 at 3*14*14 x 256); otherwise THREE (weights per 64-channel slab; map and chunk extrema; scaling)
+ *     and a workspace of dvt_cam_map_workspace_bytes(N, P, C) bytes (0 for the one-launch form).  dvt_cam_map_launches(P, C)
+ *     names the form.  Host only, both.
+ *   dvt_cam_jet_table: the 256 x 3 byte JET table in RGB order, built in float64 (x = i / 255: r = clamp(1.5 - |4x - 3|),
+ *     g = clamp(1.5 - |4x - 2|), b = clamp(1.5 - |4x - 1|), entries floor(255 v + 0.5)), written to a HOST buffer.
+ *   dvt_cam_render: scaled f32 [N][Ti][Hi][Wi] -> mask f32 [N][T][H][W] (optional when frames are given): separable linear
+ *     interpolation with half-pixel centres, per axis src = (o + 0.5) I / O - 0.5 clamped to [0, I - 1], taps floor(src) and
+ *     min(floor(src) + 1, I - 1) (torch's interpolate(mode="trilinear", align_corners=False); Ti == T == 1 is the bilinear
+ *     case).  With `frames` ([N][T][H][W][3], uint8, or f32 in [0, 1] when frames_f32) it also writes `overlay` uint8
+ *     [N][T][H][W][3], the library's show_cam_on_image per frame: heat = jet[(int)(255 mask)] / 255 (RGB if use_rgb, else
+ *     BGR; the index clamped to 0 .. 255), blend = (1 - image_weight) heat + image_weight img, out = (uint8)(255 blend /
+ *     max over the frame of blend), zeros where that maximum is 0.  `jet`: a device copy of dvt_cam_jet_table's bytes.  One
+ *     workgroup per output frame evaluates the blend twice (maximum, then write) and stores no intermediate. */
+#define DVT_CAM_MAX_C 2048
+#define DVT_CAM_FUSED_MAX_P 4096
+#define DVT_CAM_FUSED_MAX_ELEMS 262144
+enum dvt_cam_method { DVT_CAM_GRADCAM = 0, DVT_CAM_GRADCAMPP = 1, DVT_CAM_XGRADCAM = 2 };
+int dvt_cam_seed(const void* logits, const int32_t* category, void* seed, int64_t B, int64_t K, int dtype,
+                 dvt_stream_t stream);
+int dvt_cam_map_launches(int64_t P, int64_t C);
+size_t dvt_cam_map_workspace_bytes(int64_t N, int64_t P, int64_t C);
+int dvt_cam_map(const void* A, const void* G, int64_t N, int64_t P, int64_t C, int dtype, int method, float* weights,
+                float* raw, float* scaled, void* workspace, size_t workspace_bytes, dvt_stream_t stream);
+int dvt_cam_jet_table(uint8_t* dst, size_t bytes);
+int dvt_cam_render(const float* scaled, int64_t N, int Ti, int Hi, int Wi, int T, int H, int W, float* mask,
+                   const void* frames, int frames_f32, const uint8_t* jet, uint8_t* overlay, float image_weight, int use_rgb,
+                   dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- data-parallel gradient exchange
  * The reference is single-GPU (pl.Trainer(gpus=1), src/main.py:87); north_star partitions the clips of the global
  * batch over the 8 GPUs of a node, and the only exchange of the path is the SUM of the parameter gradients.  RCCL over
