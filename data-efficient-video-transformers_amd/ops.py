@@ -1088,6 +1088,65 @@ def frames_preprocess(frames: Tensor, resize: int, crop: int, mean, std, out_dty
     return out
 
 
+def _host_table(table, cols: int, what: str) -> Tensor:
+    """A parameter table as a contiguous int32 CPU tensor [rows, cols]: the launchers validate it on the host before any launch."""
+    if isinstance(table, Tensor) and table.is_cuda:
+        raise ValueError(f"{what}: the table is a host array (validated before any launch), got a device tensor")
+    t = torch.as_tensor(table, dtype=torch.int32).contiguous()
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError(f"{what}: the table must be [rows, {cols}], got {tuple(t.shape)}")
+    return t
+
+
+def frames_augment(frames: Tensor, table, out_hw, mean=None, std=None, out_dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """uint8 RGB frames [F, H0, W0, 3] + host table [N, 7] int32 (src_index, top, left, h, w, hflip, vflip) ->
+    [N, 3, out_h, out_w] in ``out_dtype``: per sample crop -> Pillow bilinear resize -> flips -> ToTensor -> Normalize
+    (MMX_Frame_dl.py:63-71), bit-exact in fp32.  ``out_dtype=torch.uint8`` -> [N, out_h, out_w, 3] bytes, not normalised."""
+    if not isinstance(frames, Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("frames must be uint8 [F, H0, W0, 3]")
+    tab = _host_table(table, 7, "frames_augment")
+    if out_dtype != torch.uint8 and out_dtype not in _DT:
+        raise ValueError(f"frames_augment: no kernel writes {out_dtype}")
+    _need_cuda(frames)
+    frames = frames.contiguous()
+    Fr, H0, W0, _ = frames.shape
+    out_h, out_w = (int(v) for v in ((out_hw, out_hw) if isinstance(out_hw, int) else out_hw))
+    N = tab.shape[0]
+    lib = L.load()
+    nbytes = lib.dvt_frames_augment_workspace_bytes(N, H0, W0, out_h, out_w)
+    if nbytes == 0:
+        raise ValueError(f"frames_augment: one output row of a {H0}x{W0} frame resized to {out_h}x{out_w} does not fit "
+                         "the LDS band of the kernel")
+    ws = workspace(nbytes, frames.device)
+    u8 = out_dtype == torch.uint8
+    out = torch.empty((N, out_h, out_w, 3) if u8 else (N, 3, out_h, out_w), dtype=out_dtype, device=frames.device)
+    m = sd = None
+    if not u8:
+        m = C.cast((C.c_float * 3)(*[float(v) for v in mean]), C.c_void_p)
+        sd = C.cast((C.c_float * 3)(*[float(v) for v in std]), C.c_void_p)
+    L.check(lib.dvt_frames_augment(frames.data_ptr(), Fr, H0, W0, tab.data_ptr(), N, out.data_ptr(),
+                                   L.ENUMS["dvt_augment_dst"]["DVT_AUGMENT_U8_HWC"] if u8 else _DT[out_dtype], out_h, out_w,
+                                   m, sd, ws.data_ptr(), _stream()), "dvt_frames_augment")
+    return out
+
+
+def frames_erase(x: Tensor, table, value=(0, 0, 0)) -> Tensor:
+    """RandomErasing with a constant fill, in place on x [F, 3, H, W]: host table [F, 4] int32 (top, left, h, w), h == 0
+    leaves the frame alone (MMX_Frame_dl.py:87).  Only the rectangles are written.  Returns x."""
+    if not isinstance(x, Tensor) or x.dim() != 4 or x.shape[1] != 3 or x.dtype not in _DT:
+        raise ValueError("x must be a floating-point tensor [F, 3, H, W]")
+    tab = _host_table(table, 4, "frames_erase")
+    if tab.shape[0] != x.shape[0]:
+        raise ValueError(f"frames_erase: {tab.shape[0]} table rows for {x.shape[0]} frames")
+    _need_cuda(x)
+    if not x.is_contiguous():
+        raise ValueError("frames_erase works in place and needs a contiguous tensor")
+    v = (C.c_float * 3)(*[float(c) for c in value])
+    L.check(L.load().dvt_frames_erase(x.data_ptr(), dt(x), x.shape[0], x.shape[2], x.shape[3], tab.data_ptr(),
+                                      C.cast(v, C.c_void_p), _stream()), "dvt_frames_erase")
+    return x
+
+
 def f1_samples(probs: Tensor, labels: Tensor, thresholds) -> Tensor:
     """samples-averaged F1 of ``probs > t`` for every t (callbacks.py:38-41) -> f32 [T] on the device."""
     _need_cuda(probs, labels)

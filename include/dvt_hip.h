@@ -544,6 +544,31 @@ int dvt_heads_contract_outer(const float* v, const float* gamma, const void* W, 
 size_t dvt_frames_preprocess_workspace_bytes(int64_t frames, int H0, int W0, int resize, int crop);
 int dvt_frames_preprocess(const void* src, void* dst, int dst_dtype, int64_t frames, int H0, int W0, int resize,
                           int crop, const float* mean, const float* std, void* workspace, dvt_stream_t stream);
+/* Addition within ABI v5: the random training augmentations of the frame loader, with the random draws made by the caller.
+ *   image branch  RandomResizedCrop(224) -> RandomHorizontalFlip(0.3) -> RandomVerticalFlip(0.3) -> [AutoAugment] ->
+ *                 ToTensor -> Normalize   (src/dataloaders/mmx/MMX_Frame_dl.py:63-71, live at :154)
+ *   video branch  Resize(120) -> CenterCrop(112) -> ToTensor -> Normalize -> RandomErasing()   (:81-88, live at :152-153)
+ * dvt_frames_augment: sample n of `samples` reads frame table[n].src_index of src[frames, H0, W0, 3] (uint8, device) and is
+ *   img.crop((left, top, left + w, top + h)).resize((out_w, out_h), BILINEAR), transpose(FLIP_LEFT_RIGHT) if hflip,
+ *   transpose(FLIP_TOP_BOTTOM) if vflip, then ToTensor + Normalize -- Pillow's 8-bit resample as above, its taps clipped to
+ *   the crop window (not to the frame).  table: HOST array of samples x 7 int32 rows {src_index, top, left, h, w, hflip,
+ *   vflip}, validated whole before any launch (0 <= src_index < frames; h, w >= 1; window inside the frame; flips 0 / 1): a
+ *   bad row returns DVT_ERR_BAD_ARG and dvt_last_error() names it.  dst_dtype: a dvt_dtype -> dst[samples, 3, out_h, out_w]
+ *   normalised; DVT_AUGMENT_U8_HWC -> dst[samples, out_h, out_w, 3] uint8, not normalised (mean / std unused; where the
+ *   AutoAugment policy operations would go).  One coefficient launch per 64 samples and one fused launch: a workgroup resamples the
+ *   input rows of a band of output rows horizontally into LDS (uint8) and runs the vertical pass from there; no
+ *   intermediate image in HBM.  The band height is chosen so that the band of a full-height window fits 64 KiB of LDS;
+ *   a geometry whose single output row does not fit is refused (DVT_ERR_UNSUPPORTED; workspace_bytes returns 0).
+ * dvt_frames_erase: RandomErasing with a constant fill, in place on x[frames, 3, H, W] (dtype): table is a HOST array of
+ *   frames x 4 int32 rows {top, left, h, w}; h == 0 leaves the frame alone, otherwise h, w >= 1 and the rectangle lies inside
+ *   the frame (H, W <= 65535).  value: host array of 3 (one fill per channel).  Writes the rectangles only. */
+enum dvt_augment_dst { DVT_AUGMENT_U8_HWC = 8 };
+size_t dvt_frames_augment_workspace_bytes(int64_t samples, int H0, int W0, int out_h, int out_w);
+int dvt_frames_augment(const void* src, int64_t frames, int H0, int W0, const int32_t* table, int64_t samples, void* dst,
+                       int dst_dtype, int out_h, int out_w, const float* mean, const float* std, void* workspace,
+                       dvt_stream_t stream);
+int dvt_frames_erase(void* x, int dtype, int64_t frames, int H, int W, const int32_t* table, const float* value,
+                     dvt_stream_t stream);
 
 /* ---------------------------------------------------------------- multi-modal gating + contrastive loss
  * F.normalize(x) (collabgating.py:70) and the normaliser of F.cosine_similarity (ntxent.py:63):
