@@ -2,14 +2,17 @@
 
 Mirrors the ``transforms.Compose`` pipelines of the reference loaders for inputs that are already decoded RGB arrays in HBM:
 the four deterministic ones (src/dataloaders/mmx/MMX_Light_dl.py:184-217) and the two random training ones of
-src/dataloaders/mmx/MMX_Frame_dl.py -- ``RandomResizedCrop(224) -> flips -> [AutoAugment] -> ToTensor -> Normalize`` for every
+src/dataloaders/mmx/MMX_Frame_dl.py -- ``RandomResizedCrop(224) -> flips -> AutoAugment -> ToTensor -> Normalize`` for every
 training image (:63-71, live at :154) and ``Resize(120) -> CenterCrop(112) -> ToTensor -> Normalize -> RandomErasing()`` for
 every training video frame (:81-88, live at :152-153).  MMX_Light_dl.py disables its image branch in ``__getitem__`` (:276);
 MMX_Frame_dl.py, which feeds the ``frame`` / ``sum`` / ``distil`` / ``sum_residual`` / ``pre_modal`` modes, does not.
 
 The random parameters are drawn on the host with the torch CPU generator, by torchvision's documented rules and in its
-order (``RandomResizedCrop.get_params``, ``torch.rand(1) < p``, ``RandomErasing.get_params``); the kernels receive them as a
-table.  AutoAugment's policy operations are not built: ``frames_augment(..., out_dtype=torch.uint8)`` is where they would go.
+order (``RandomResizedCrop.get_params``, ``torch.rand(1) < p``, ``RandomErasing.get_params``, ``AutoAugment.get_params``); the
+kernels receive them as a table.  AutoAugment's operations run on the uint8 output of ``frames_augment(...,
+out_dtype=torch.uint8)``: ``train_transform_autoaugment`` is the reference's whole line :63-71 (``train_transform`` is the line
+without its AutoAugment stage).  The operations are Pillow's, as torchvision's PIL path calls them; their magnitudes, affine
+matrices and 16.16 fixed-point coefficients are computed here on the host, so the kernel sees integers only.
 """
 from __future__ import annotations
 
@@ -120,6 +123,7 @@ class RandomResizedCropFlip:
     reading frame ``index[n]``: the loader's one random frame of a clip, or two views of one frame.  ``params``: a table
     ``[N, 7]`` (src_index, top, left, h, w, hflip, vflip) to use instead of drawing one; the table used is kept in
     ``.last_params`` (int32 CPU tensor), so that a saliency overlay can be mapped back to the frame.
+    ``dtype=torch.uint8``: ``[..., size, size, 3]`` bytes, not normalised (the input of ``AutoAugment``).
     """
 
     def __init__(self, size: int, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), hflip_p: float = 0.0, vflip_p: float = 0.0,
@@ -149,7 +153,7 @@ class RandomResizedCropFlip:
         out = ops.frames_augment(flat, params, (self.size, self.size), self.mean, self.std, self.dtype)
         self.last_params = torch.as_tensor(params, dtype=torch.int32).clone()
         if index is None and out.shape[0] == flat.shape[0]:
-            return out.view(*lead, 3, self.size, self.size)
+            return out.view(*lead, *out.shape[1:])
         return out
 
 
@@ -193,6 +197,7 @@ class _Then:
 
 
 def train_transform(dtype=torch.bfloat16, auto_augment: bool = False, generator=None):      # MMX_Frame_dl.py:63-71
+    """The line without its AutoAugment stage; ``train_transform_autoaugment`` is the whole line."""
     if auto_augment:
         raise NotImplementedError("AutoAugment's policy operations are not built; they belong between the resample and "
                                   "ToTensor, on the uint8 output of ops.frames_augment(..., out_dtype=torch.uint8)")
@@ -202,3 +207,170 @@ def train_transform(dtype=torch.bfloat16, auto_augment: bool = False, generator=
 
 def train_vid_frame(dtype=torch.bfloat16, generator=None):                                  # MMX_Frame_dl.py:81-88
     return _Then(train_vid(dtype), RandomErasing(generator=generator))
+
+
+# ---------------------------------------------------------------- AutoAugment (torchvision's, on its PIL path)
+AUTOAUGMENT_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast",
+                   "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize", "Invert")      # = enum dvt_autoaugment_op
+_AA_GEOMETRIC = ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate")
+_AA_BLEND = ("Brightness", "Color", "Contrast", "Sharpness")
+_AA_BINS = 10
+_AA_POSTERIZE_BITS = (8, 8, 7, 7, 6, 6, 5, 5, 4, 4)
+
+# AutoAugmentPolicy.IMAGENET: 25 sub-policies of two (operation, probability, magnitude bin)
+IMAGENET_POLICY = (
+    (("Posterize", 0.4, 8), ("Rotate", 0.6, 9)), (("Solarize", 0.6, 5), ("AutoContrast", 0.6, None)),
+    (("Equalize", 0.8, None), ("Equalize", 0.6, None)), (("Posterize", 0.6, 7), ("Posterize", 0.6, 6)),
+    (("Equalize", 0.4, None), ("Solarize", 0.2, 4)), (("Equalize", 0.4, None), ("Rotate", 0.8, 8)),
+    (("Solarize", 0.6, 3), ("Equalize", 0.6, None)), (("Posterize", 0.8, 5), ("Equalize", 1.0, None)),
+    (("Rotate", 0.2, 3), ("Solarize", 0.6, 8)), (("Equalize", 0.6, None), ("Posterize", 0.4, 6)),
+    (("Rotate", 0.8, 8), ("Color", 0.4, 0)), (("Rotate", 0.4, 9), ("Equalize", 0.6, None)),
+    (("Equalize", 0.0, None), ("Equalize", 0.8, None)), (("Invert", 0.6, None), ("Equalize", 1.0, None)),
+    (("Color", 0.6, 4), ("Contrast", 1.0, 8)), (("Rotate", 0.8, 8), ("Color", 1.0, 2)),
+    (("Color", 0.8, 8), ("Solarize", 0.8, 7)), (("Sharpness", 0.4, 7), ("Invert", 0.6, None)),
+    (("ShearX", 0.6, 5), ("Equalize", 1.0, None)), (("Color", 0.4, 0), ("Equalize", 0.6, None)),
+    (("Equalize", 0.4, None), ("Solarize", 0.2, 4)), (("Solarize", 0.6, 5), ("AutoContrast", 0.6, None)),
+    (("Invert", 0.6, None), ("Equalize", 1.0, None)), (("Color", 0.6, 4), ("Contrast", 1.0, 8)),
+    (("Equalize", 0.8, None), ("Equalize", 0.6, None)),
+)
+
+
+def autoaugment_magnitude(op: str, magnitude_id, sign: int, H: int, W: int) -> float:
+    """``AutoAugment._augmentation_space(10, (H, W))``: bin ``magnitude_id`` of the operation's float32 ``torch.linspace``, as a
+    Python float, negated for a signed operation when ``sign == 0``; Posterize: the number of bits; no magnitude: 0.0."""
+    if op == "Posterize":
+        return float(_AA_POSTERIZE_BITS[magnitude_id])
+    if op == "Solarize":
+        return float(torch.linspace(255.0, 0.0, _AA_BINS)[magnitude_id].item())
+    if op in ("ShearX", "ShearY"):
+        top = 0.3
+    elif op == "TranslateX":
+        top = 150.0 / 331.0 * W
+    elif op == "TranslateY":
+        top = 150.0 / 331.0 * H
+    elif op == "Rotate":
+        top = 30.0
+    elif op in _AA_BLEND:
+        top = 0.9
+    else:
+        return 0.0
+    m = float(torch.linspace(0.0, top, _AA_BINS)[magnitude_id].item())
+    return -m if sign == 0 else m
+
+
+def _aa_inverse_matrix(op: str, mag: float, H: int, W: int):
+    """The matrix Pillow's ``transform(AFFINE)`` receives: output pixel centre -> input position."""
+    if op == "ShearX":                             # about the origin (F.affine(..., center=[0, 0])); torchvision passes
+        # degrees(atan(mag)) and takes tan again: for all ten bins and both signs the 16.16 coefficient is the same
+        return [1.0, mag, 0.0, 0.0, 1.0, 0.0]
+    if op == "ShearY":
+        return [1.0, 0.0, 0.0, mag, 1.0, 0.0]
+    if op == "TranslateX":
+        return [1.0, 0.0, -float(int(mag)), 0.0, 1.0, 0.0]
+    if op == "TranslateY":
+        return [1.0, 0.0, 0.0, 0.0, 1.0, -float(int(mag))]
+    r = -math.radians(mag % 360.0)                 # Image.rotate about (W / 2, H / 2)
+    m = [round(math.cos(r), 15), round(math.sin(r), 15), 0.0, round(-math.sin(r), 15), round(math.cos(r), 15), 0.0]
+    cx, cy = W / 2, H / 2
+    m[2] = m[0] * -cx + m[1] * -cy + m[2]
+    m[5] = m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def autoaugment_slot(op: str, mag: float, H: int, W: int):
+    """The eight int32 {op, p0 .. p6} of a table slot of ``dvt_frames_autoaugment``: Pillow's 16.16 coefficients
+    ``FIX(v) = floor(v * 65536 + 0.5)`` of a geometric operation (a2, a5 with the half-pixel offset), the float32 bits of a
+    blend factor ``1 + mag``, the posterize mask, the solarize threshold ``ceil(mag)``."""
+    p = [0] * 7
+    if op in _AA_GEOMETRIC:
+        m = _aa_inverse_matrix(op, mag, H, W)
+        fix = lambda v: int(math.floor(v * 65536.0 + 0.5))  # noqa: E731
+        p[:6] = [fix(m[0]), fix(m[1]), fix(m[2] + m[0] * 0.5 + m[1] * 0.5), fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5)]
+    elif op in _AA_BLEND:
+        p[0] = int(torch.tensor(1.0 + mag, dtype=torch.float32).view(torch.int32).item())
+    elif op == "Posterize":
+        p[0] = ~(2 ** (8 - int(mag)) - 1) & 0xFF
+    elif op == "Solarize":
+        p[0] = int(math.ceil(mag))
+    return [AUTOAUGMENT_OPS.index(op)] + p
+
+
+class AutoAugment:
+    """``transforms.AutoAugment(policy) -> ToTensor -> Normalize(mean, std)`` on uint8 frames, one sub-policy per sample.
+
+    ``policy``: ``"imagenet"`` or a list of sub-policies ``((op, p, magnitude_id), (op, p, magnitude_id))`` with the names of
+    ``AUTOAUGMENT_OPS``.  ``draw(n, H, W)`` makes torchvision's draws per sample, in its order -- ``randint(len(policy))``,
+    ``rand(2)``, ``randint(2, (2,))`` -- and returns the int32 table ``[n, 2, 8]``; operation i applies when ``probs[i] <= p``,
+    otherwise its slot is Identity.  ``__call__(frames_u8, params=None)``: uint8 ``[..., H, W, 3]`` -> ``[..., 3, H, W]`` in
+    ``dtype`` (``torch.uint8``: ``[..., H, W, 3]``, not normalised); the table used is kept in ``.last_params``.
+    """
+
+    def __init__(self, policy="imagenet", mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype: torch.dtype = torch.bfloat16,
+                 generator=None):
+        if isinstance(policy, str):
+            if policy != "imagenet":
+                raise NotImplementedError(f"AutoAugment policy {policy!r} is not built: 'imagenet' or a list of sub-policies")
+            policy = IMAGENET_POLICY
+        self.policy = tuple(tuple((str(op), float(p), mid) for op, p, mid in sub) for sub in policy)
+        for sub in self.policy:
+            if len(sub) != 2 or any(op not in AUTOAUGMENT_OPS for op, _, _ in sub):
+                raise ValueError(f"policy: a sub-policy is two (op, p, magnitude_id) with op in {AUTOAUGMENT_OPS}, got {sub}")
+        self.mean, self.std, self.dtype, self.generator = tuple(mean), tuple(std), dtype, generator
+        self.last_params = None
+
+    def draw(self, n: int, H: int, W: int) -> torch.Tensor:
+        rows = []
+        for _ in range(n):
+            policy_id = int(torch.randint(len(self.policy), (1,), generator=self.generator).item())
+            probs = torch.rand((2,), generator=self.generator)
+            signs = torch.randint(2, (2,), generator=self.generator)
+            slots = []
+            for i, (op, p, mid) in enumerate(self.policy[policy_id]):
+                if probs[i] <= p:
+                    slots.append(autoaugment_slot(op, autoaugment_magnitude(op, mid, int(signs[i]), H, W), H, W))
+                else:
+                    slots.append([0] * 8)
+            rows.append(slots)
+        return torch.tensor(rows, dtype=torch.int32).reshape(-1, 2, 8)
+
+    def __call__(self, frames_u8: torch.Tensor, params=None) -> torch.Tensor:
+        if (not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() < 3
+                or frames_u8.shape[-1] != 3):
+            raise ValueError("frames_u8 must be uint8 [..., H, W, 3]")
+        lead = frames_u8.shape[:-3]
+        flat = frames_u8.reshape(-1, *frames_u8.shape[-3:])
+        H, W = flat.shape[1], flat.shape[2]
+        if params is None:
+            params = self.draw(flat.shape[0], H, W)
+        out = ops.frames_autoaugment(flat, params, self.mean, self.std, self.dtype)
+        self.last_params = torch.as_tensor(params, dtype=torch.int32).reshape(-1, 2, 8).clone()
+        return out.view(*lead, *out.shape[1:])
+
+
+class _CropFlipAutoAugment:
+    """``second(first(frames))`` with ``first`` a RandomResizedCropFlip writing uint8 and ``second`` an AutoAugment.
+    ``__call__(frames, index=None, params=None, policy_params=None)`` as ``RandomResizedCropFlip.__call__``; the two tables
+    used are ``.first.last_params`` and ``.second.last_params``, together ``.last_params``."""
+
+    def __init__(self, first: RandomResizedCropFlip, second: AutoAugment):
+        self.first, self.second = first, second
+        self.last_params = None
+
+    def __call__(self, frames: torch.Tensor, index=None, params=None, policy_params=None) -> torch.Tensor:
+        u8 = self.first(frames, index=index, params=params)            # [..., size, size, 3] or [N, size, size, 3]
+        out = self.second(u8, params=policy_params)
+        self.last_params = (self.first.last_params, self.second.last_params)
+        return out
+
+
+def train_transform_autoaugment(dtype=torch.bfloat16, generator=None):                      # MMX_Frame_dl.py:63-71
+    """The reference's whole training-image line: ``RandomResizedCrop(224) -> RandomHorizontalFlip(0.3) ->
+    RandomVerticalFlip(0.3) -> AutoAugment() -> ToTensor -> Normalize``.  Crop and flips write uint8 through
+    ``ops.frames_augment(..., out_dtype=torch.uint8)``; ``AutoAugment`` (ImageNet policy) reads that.  This factory, not
+    ``train_transform(auto_augment=True)`` (which keeps refusing), is the way to the AutoAugment stage.  Accepts ``index=``
+    as ``RandomResizedCropFlip`` does; one generator serves both stages, crop and flips of all samples drawn first."""
+    first = RandomResizedCropFlip(224, hflip_p=0.3, vflip_p=0.3, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype=torch.uint8,
+                                  generator=generator)
+    return _CropFlipAutoAugment(first, AutoAugment("imagenet", IMAGENET_MEAN, IMAGENET_STD, dtype, generator))

@@ -1147,6 +1147,37 @@ def frames_erase(x: Tensor, table, value=(0, 0, 0)) -> Tensor:
     return x
 
 
+def frames_autoaugment(frames_u8: Tensor, table, mean=None, std=None, out_dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """uint8 RGB frames [N, H, W, 3] + host table [N, 2, 8] int32 (two slots {op, p0 .. p6} per sample, applied in order;
+    ``input_stage.AutoAugment.draw`` makes one) -> [N, 3, H, W] in ``out_dtype``: torchvision's AutoAugment operations as its
+    PIL path computes them, then ToTensor -> Normalize (MMX_Frame_dl.py:63-71), bit-exact in fp32, in one launch per 48
+    samples.  ``out_dtype=torch.uint8`` -> [N, H, W, 3] bytes, not normalised."""
+    if not isinstance(frames_u8, Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+        raise ValueError("frames_u8 must be uint8 [N, H, W, 3]")
+    if isinstance(table, Tensor) and table.is_cuda:
+        raise ValueError("frames_autoaugment: table is a host array (validated before any launch), got a device tensor")
+    tab = torch.as_tensor(table, dtype=torch.int32).contiguous()
+    N, H, W, _ = frames_u8.shape
+    if tuple(tab.shape) not in ((N, 2, 8), (N, 16)):
+        raise ValueError(f"frames_autoaugment: table must be [{N}, 2, 8] for {N} frames, got {tuple(tab.shape)}")
+    u8 = out_dtype == torch.uint8
+    if not u8 and out_dtype not in _DT:
+        raise ValueError(f"frames_autoaugment: out_dtype: no kernel writes {out_dtype}")
+    if not u8 and (mean is None or std is None or len(mean) != 3 or len(std) != 3):
+        raise ValueError("frames_autoaugment: mean and std must hold one number per channel")
+    _need_cuda(frames_u8)
+    frames_u8 = frames_u8.contiguous()
+    out = torch.empty((N, H, W, 3) if u8 else (N, 3, H, W), dtype=out_dtype, device=frames_u8.device)
+    m = sd = None
+    if not u8:
+        m = C.cast((C.c_float * 3)(*[float(v) for v in mean]), C.c_void_p)
+        sd = C.cast((C.c_float * 3)(*[float(v) for v in std]), C.c_void_p)
+    L.check(L.load().dvt_frames_autoaugment(frames_u8.data_ptr(), N, H, W, tab.data_ptr(), out.data_ptr(),
+                                            L.ENUMS["dvt_augment_dst"]["DVT_AUGMENT_U8_HWC"] if u8 else _DT[out_dtype], m, sd,
+                                            _stream()), "dvt_frames_autoaugment")
+    return out
+
+
 def f1_samples(probs: Tensor, labels: Tensor, thresholds) -> Tensor:
     """samples-averaged F1 of ``probs > t`` for every t (callbacks.py:38-41) -> f32 [T] on the device."""
     _need_cuda(probs, labels)

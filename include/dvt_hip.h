@@ -545,7 +545,7 @@ size_t dvt_frames_preprocess_workspace_bytes(int64_t frames, int H0, int W0, int
 int dvt_frames_preprocess(const void* src, void* dst, int dst_dtype, int64_t frames, int H0, int W0, int resize,
                           int crop, const float* mean, const float* std, void* workspace, dvt_stream_t stream);
 /* Addition within ABI v5: the random training augmentations of the frame loader, with the random draws made by the caller.
- *   image branch  RandomResizedCrop(224) -> RandomHorizontalFlip(0.3) -> RandomVerticalFlip(0.3) -> [AutoAugment] ->
+ *   image branch  RandomResizedCrop(224) -> RandomHorizontalFlip(0.3) -> RandomVerticalFlip(0.3) -> AutoAugment ->
  *                 ToTensor -> Normalize   (src/dataloaders/mmx/MMX_Frame_dl.py:63-71, live at :154)
  *   video branch  Resize(120) -> CenterCrop(112) -> ToTensor -> Normalize -> RandomErasing()   (:81-88, live at :152-153)
  * dvt_frames_augment: sample n of `samples` reads frame table[n].src_index of src[frames, H0, W0, 3] (uint8, device) and is
@@ -554,8 +554,8 @@ int dvt_frames_preprocess(const void* src, void* dst, int dst_dtype, int64_t fra
  *   the crop window (not to the frame).  table: HOST array of samples x 7 int32 rows {src_index, top, left, h, w, hflip,
  *   vflip}, validated whole before any launch (0 <= src_index < frames; h, w >= 1; window inside the frame; flips 0 / 1): a
  *   bad row returns DVT_ERR_BAD_ARG and dvt_last_error() names it.  dst_dtype: a dvt_dtype -> dst[samples, 3, out_h, out_w]
- *   normalised; DVT_AUGMENT_U8_HWC -> dst[samples, out_h, out_w, 3] uint8, not normalised (mean / std unused; where the
- *   AutoAugment policy operations would go).  One coefficient launch per 64 samples and one fused launch: a workgroup resamples the
+ *   normalised; DVT_AUGMENT_U8_HWC -> dst[samples, out_h, out_w, 3] uint8, not normalised (mean / std unused; the
+ *   input of dvt_frames_autoaugment).  One coefficient launch per 64 samples and one fused launch: a workgroup resamples the
  *   input rows of a band of output rows horizontally into LDS (uint8) and runs the vertical pass from there; no
  *   intermediate image in HBM.  The band height is chosen so that the band of a full-height window fits 64 KiB of LDS;
  *   a geometry whose single output row does not fit is refused (DVT_ERR_UNSUPPORTED; workspace_bytes returns 0).
@@ -569,6 +569,32 @@ int dvt_frames_augment(const void* src, int64_t frames, int H0, int W0, const in
                        dvt_stream_t stream);
 int dvt_frames_erase(void* x, int dtype, int64_t frames, int H, int W, const int32_t* table, const float* value,
                      dvt_stream_t stream);
+/* Addition within ABI v5: the AutoAugment stage of the image branch above (torchvision's AutoAugment on its PIL path, the
+ * random draws made by the caller).  dvt_frames_autoaugment: sample n of src[samples, H, W, 3] (uint8, device) takes the
+ *   two operations of table[n] in order.  table: HOST array of samples x 2 slots x 8 int32 {op, p0 .. p6}, validated whole
+ *   before any HIP call (op in range; a posterize mask is a run of high bits; a blend factor is finite; a solarize threshold
+ *   lies in [0, 256]): a bad slot returns DVT_ERR_BAD_ARG and dvt_last_error() names it; so are null pointers, by name.
+ *     geometric (SHEAR_X .. ROTATE)       p0 .. p5 = a0 .. a5, Pillow's 16.16 fixed-point inverse affine matrix, a2 and a5 with
+ *                                         the half-pixel offset: xin = (a2 + a1 y + a0 x) >> 16, yin = (a5 + a4 y + a3 x) >> 16,
+ *                                         nearest, 0 outside the image (Image.transform(AFFINE, NEAREST), Image.rotate)
+ *     blend (BRIGHTNESS .. SHARPNESS)     p0 = the bits of the float32 factor f: deg + f (img - deg) in float32, the product and
+ *                                         the sum rounded separately, truncated for 0 <= f <= 1 and clipped otherwise
+ *                                         (ImageEnhance); deg = 0 / luma / the rounded mean luma of the image / ImageFilter.SMOOTH
+ *     POSTERIZE  p0 = the byte mask;  SOLARIZE  p0 = ceil(threshold): v < p0 ? v : 255 - v;  INVERT;  IDENTITY
+ *     AUTOCONTRAST, EQUALIZE              per channel, from the channel's 256-bin histogram (ImageOps, cutoff 0)
+ *   dst_dtype: DVT_AUGMENT_U8_HWC -> dst[samples, H, W, 3] uint8; a dvt_dtype -> dst[samples, 3, H, W] after ToTensor +
+ *   Normalize in the float32 arithmetic of dvt_frames_augment (two IDENTITY slots give the bits of that entry point; mean / std
+ *   unused for uint8).  One launch per 48 samples, one workgroup per sample: the first operation reads src and leaves its
+ *   result in LDS as uint8, the second reads that image and writes dst; an operation that needs a statistic of its whole
+ *   input (histograms, the luma sum: integer counts) makes a counting pass over that input first.  No workspace.  H, W >= 3,
+ *   and 3 H W bytes must fit the LDS image of a workgroup (160,000 bytes: 224 x 224 fits); a larger image returns
+ *   DVT_ERR_UNSUPPORTED. */
+enum dvt_autoaugment_op { DVT_AA_IDENTITY = 0, DVT_AA_SHEAR_X = 1, DVT_AA_SHEAR_Y = 2, DVT_AA_TRANSLATE_X = 3,
+  DVT_AA_TRANSLATE_Y = 4, DVT_AA_ROTATE = 5, DVT_AA_BRIGHTNESS = 6, DVT_AA_COLOR = 7, DVT_AA_CONTRAST = 8,
+  DVT_AA_SHARPNESS = 9, DVT_AA_POSTERIZE = 10, DVT_AA_SOLARIZE = 11, DVT_AA_AUTOCONTRAST = 12, DVT_AA_EQUALIZE = 13,
+  DVT_AA_INVERT = 14 };
+int dvt_frames_autoaugment(const void* src, int64_t samples, int H, int W, const int32_t* table, void* dst, int dst_dtype,
+                           const float* mean, const float* std, dvt_stream_t stream);
 
 /* ---------------------------------------------------------------- multi-modal gating + contrastive loss
  * F.normalize(x) (collabgating.py:70) and the normaliser of F.cosine_similarity (ntxent.py:63):
