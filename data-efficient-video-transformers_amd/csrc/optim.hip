@@ -1,6 +1,7 @@
 // optim.hip -- every optimizer step: AdamW (host step, device step, fused flat-buffer step with mirror, loss-scaled),
-// torch.optim.Adam with coupled decay, SGD, Adagrad -- streaming kernels over fp32 master weights -- and LARS, whose
-// per-tensor norms make it a reduction over a table of segments followed by the scaled momentum update.
+// torch.optim.Adam with coupled decay, SGD, Adagrad -- streaming kernels over fp32 master weights -- LARS, whose
+// per-tensor norms make it a reduction over a table of segments followed by the scaled momentum update, and the global
+// gradient norm with its in-place clip over the same kind of table.
 //
 // The Adam update, its bias correction, the step-counter ticket and the mirror dispatch are each stated once, below;
 // the kernels differ only in their launch contract (scalar grid-stride or four elements per thread, mirror, ticket,
@@ -452,6 +453,126 @@ __global__ __launch_bounds__(kLarsBlock) void lars_update_kernel(const dvt_lars_
   publish_step(step_dev, steps);
 }
 
+// ------------------------------------------------------------------ global gradient norm and in-place clip
+// (Lightning's gradient_clip_val = torch.nn.utils.clip_grad_norm_ over all gradients.)  The segment table, the chunks and
+// their ownership are LARS's; only `grad` and `numel` of a row are read.  One float per chunk: the sum of g^2 (kind 2) or
+// max |g| (kind inf), and ONE total over the whole table.  Every sum and maximum is taken in an order that numel alone
+// fixes -- under data parallelism every rank forms the coefficient from the same all-reduced gradient, and a total that
+// depended on the arrival order of the blocks would let the ranks' weights drift apart.
+enum { kNormTwo = 0, kNormInf = 1 };
+
+// max that keeps a NaN (fmaxf drops it): the clip must see a non-finite gradient under either norm.
+__device__ __forceinline__ float grad_max(float a, float b) { return (a != a || a > b) ? a : b; }
+
+template <int kKind>
+__device__ __forceinline__ float grad_join(float a, float b) { return kKind == kNormTwo ? a + b : grad_max(a, b); }
+
+// lars_block_sum for one value under either join: the xor butterfly inside each wave, then the waves in index order.
+template <int kKind>
+__device__ __forceinline__ float grad_block_join(float a) {
+  __shared__ float red[kLarsBlock / DVT_WAVE];
+#pragma unroll
+  for (int off = DVT_WAVE / 2; off > 0; off >>= 1) a = grad_join<kKind>(a, __shfl_xor(a, off, DVT_WAVE));
+  __syncthreads();                                      // the previous use of `red` is over
+  if ((threadIdx.x & (DVT_WAVE - 1)) == 0) red[threadIdx.x / DVT_WAVE] = a;
+  __syncthreads();
+  a = red[0];
+#pragma unroll
+  for (int w = 1; w < kLarsBlock / DVT_WAVE; ++w) a = grad_join<kKind>(a, red[w]);
+  return a;
+}
+
+template <int kKind, bool kVec>
+__device__ __forceinline__ float grad_chunk_partial(const gfloat* __restrict__ g, int len) {
+  float acc = 0.f;
+  const int n4 = len >> 2;
+  for (int q = threadIdx.x; q < n4; q += kLarsBlock) {
+    const f32x4 gv = lars_load4<kVec>(g + 4 * q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc = kKind == kNormTwo ? fmaf(gv[k], gv[k], acc) : grad_max(acc, fabsf(gv[k]));
+  }
+  if ((int)threadIdx.x < (len & 3)) {
+    const float gi = g[4 * n4 + threadIdx.x];
+    acc = kKind == kNormTwo ? fmaf(gi, gi, acc) : grad_max(acc, fabsf(gi));
+  }
+  return acc;
+}
+
+// The total over all `chunks` partials: thread t joins the partials t, t + 256, ... in that order, then the block.
+template <int kKind>
+__device__ __forceinline__ float grad_total(const float* __restrict__ partial, int64_t chunks) {
+  float acc = 0.f;
+  for (int64_t i = threadIdx.x; i < chunks; i += kLarsBlock) acc = grad_join<kKind>(acc, partial[i]);
+  return grad_block_join<kKind>(acc);
+}
+
+template <int kKind>
+__device__ __forceinline__ float grad_norm_of(float total) { return kKind == kNormTwo ? sqrtf(total) : total; }
+
+// partial[c] of chunk c.
+template <int kKind>
+__global__ __launch_bounds__(kLarsBlock) void grad_norm_kernel(const dvt_lars_seg* __restrict__ table, int n,
+                                                               float* __restrict__ partial) {
+  const int64_t c = blockIdx.x;
+  const dvt_lars_seg s = table[lars_find_segment(table, n, c)];
+  const int64_t start = (c - s.chunk_begin) * kLarsChunk;
+  const int len = lars_chunk_len(s.numel, start);
+  const gfloat* g = lars_global<float>(s.grad) + start;
+  const float acc = ((uintptr_t)g & 15u) == 0 ? grad_chunk_partial<kKind, true>(g, len)
+                                              : grad_chunk_partial<kKind, false>(g, len);
+  const float r = grad_block_join<kKind>(acc);
+  if (threadIdx.x == 0) partial[c] = r;
+}
+
+// out = {norm, total} from the partials: one block.  (A last-block ticket inside grad_norm_kernel would save this launch,
+// but its release / acquire pair per block -- the L2s of the XCDs are not coherent with each other without it -- cost
+// 75 us at 3521 chunks, four times the two launches together.)
+template <int kKind>
+__global__ __launch_bounds__(kLarsBlock) void grad_total_kernel(const float* __restrict__ partial, int64_t chunks,
+                                                                float* __restrict__ out) {
+  const float total = grad_total<kKind>(partial, chunks);
+  if (threadIdx.x == 0) {
+    out[0] = grad_norm_of<kKind>(total);
+    out[1] = total;
+  }
+}
+
+// g *= coef in place, coef = min(1, max_norm / (norm * inv_scale + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s rule on the
+// UNSCALED norm.  Every block forms the same total from the partials.  A non-finite total leaves the gradient as it is
+// (the loss-scaled step's own found_inf check must still see the values that overflowed), and so does coef == 1, which
+// saves the pass.  Block 0 reports norm * inv_scale.
+template <int kKind>
+__global__ __launch_bounds__(kLarsBlock) void grad_clip_kernel(const dvt_lars_seg* __restrict__ table, int n,
+                                                               const float* __restrict__ partial, int64_t chunks,
+                                                               float max_norm, const float* __restrict__ scale_dev,
+                                                               int scale_is_inverse, float* __restrict__ out) {
+  const float norm = grad_norm_of<kKind>(grad_total<kKind>(partial, chunks));
+  const float inv_scale = !scale_dev ? 1.f : (scale_is_inverse ? scale_dev[0] : 1.0f / scale_dev[0]);
+  const float unscaled = norm * inv_scale;
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = unscaled;
+  if (!(fabsf(norm) <= 3.402823466e38f)) return;        // inf or nan
+  const float coef = fminf(1.0f, max_norm / (unscaled + 1e-6f));
+  if (coef == 1.0f) return;
+  const int64_t c = blockIdx.x;
+  const dvt_lars_seg s = table[lars_find_segment(table, n, c)];
+  const int64_t start = (c - s.chunk_begin) * kLarsChunk;
+  const int len = lars_chunk_len(s.numel, start);
+  gfloat* g = lars_global<float>(const_cast<float*>(s.grad)) + start;
+  const int n4 = len >> 2;
+  if (((uintptr_t)g & 15u) == 0) {
+    for (int q = threadIdx.x; q < n4; q += kLarsBlock) lars_store4<true>(g + 4 * q, lars_load4<true>(g + 4 * q) * coef);
+  } else {
+    for (int q = threadIdx.x; q < n4; q += kLarsBlock) lars_store4<false>(g + 4 * q, lars_load4<false>(g + 4 * q) * coef);
+  }
+  if ((int)threadIdx.x < (len & 3)) g[4 * n4 + threadIdx.x] *= coef;
+}
+
+#define DVT_LAUNCH_NORM_KIND(KERNEL, kind, grid, block, st, ...)                                           \
+  do {                                                                                                     \
+    if ((kind) == DVT_NORM_INF) hipLaunchKernelGGL((KERNEL<kNormInf>), grid, block, 0, st, __VA_ARGS__);   \
+    else hipLaunchKernelGGL((KERNEL<kNormTwo>), grid, block, 0, st, __VA_ARGS__);                          \
+  } while (0)
+
 inline int64_t lars_total_chunks(const int64_t* numel, int n, int64_t* chunk_begin) {
   int64_t total = 0;
   for (int i = 0; i < n; ++i) {
@@ -611,6 +732,37 @@ int dvt_lars_step(const dvt_lars_seg* table, int n, int64_t chunks, float* works
   DVT_LAUNCH_MIRRORED(lars_update_kernel, tag, mirror_dtype, grid, block, st, table, n, (const f32x2*)workspace, lr_dev,
                       momentum, dampening, nesterov, trust_coefficient, eps, step_dev2);
   DVT_LAUNCH_CHECK("dvt_lars_step");
+  return DVT_OK;
+}
+
+int dvt_grad_norm(const dvt_lars_seg* table, int n, int64_t chunks, float* workspace, int norm_kind, float* out2,
+                  dvt_stream_t stream) {
+  DVT_REQUIRE(n >= 0 && chunks >= 0 && chunks <= 0x7fffffffll, "dvt_grad_norm: bad sizes");
+  DVT_REQUIRE(norm_kind == DVT_NORM_2 || norm_kind == DVT_NORM_INF, "dvt_grad_norm: norm_kind must be DVT_NORM_2 or DVT_NORM_INF");
+  if (n == 0) return DVT_OK;
+  DVT_REQUIRE(table && workspace && out2 && chunks >= n, "dvt_grad_norm: bad arguments");
+  DVT_REQUIRE(((uintptr_t)workspace & 3u) == 0 && ((uintptr_t)out2 & 3u) == 0, "dvt_grad_norm: buffers must be 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  DVT_LAUNCH_NORM_KIND(grad_norm_kernel, norm_kind, dim3((unsigned)chunks), dim3(kLarsBlock), st, table, n, workspace);
+  DVT_LAUNCH_NORM_KIND(grad_total_kernel, norm_kind, dim3(1), dim3(kLarsBlock), st, (const float*)workspace, chunks, out2);
+  DVT_LAUNCH_CHECK("dvt_grad_norm");
+  return DVT_OK;
+}
+
+int dvt_grad_clip(const dvt_lars_seg* table, int n, int64_t chunks, float* workspace, int norm_kind, float max_norm,
+                  const float* scale_dev, int scale_is_inverse, float* norm_out, dvt_stream_t stream) {
+  DVT_REQUIRE(n >= 0 && chunks >= 0 && chunks <= 0x7fffffffll, "dvt_grad_clip: bad sizes");
+  DVT_REQUIRE(norm_kind == DVT_NORM_2 || norm_kind == DVT_NORM_INF, "dvt_grad_clip: norm_kind must be DVT_NORM_2 or DVT_NORM_INF");
+  DVT_REQUIRE(max_norm >= 0.f, "dvt_grad_clip: max_norm must be >= 0");
+  if (n == 0) return DVT_OK;
+  DVT_REQUIRE(table && workspace && norm_out && chunks >= n, "dvt_grad_clip: bad arguments");
+  DVT_REQUIRE(((uintptr_t)workspace & 3u) == 0 && ((uintptr_t)norm_out & 3u) == 0, "dvt_grad_clip: buffers must be 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)chunks), block(kLarsBlock);
+  DVT_LAUNCH_NORM_KIND(grad_norm_kernel, norm_kind, grid, block, st, table, n, workspace);
+  DVT_LAUNCH_NORM_KIND(grad_clip_kernel, norm_kind, grid, block, st, table, n, (const float*)workspace, chunks, max_norm,
+                       scale_dev, scale_is_inverse, norm_out);
+  DVT_LAUNCH_CHECK("dvt_grad_clip");
   return DVT_OK;
 }
 

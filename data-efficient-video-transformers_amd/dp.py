@@ -26,6 +26,7 @@ Design (MI355X-first, not a DDP clone):
 """
 from __future__ import annotations
 
+import contextlib
 from typing import List, Optional
 
 import torch
@@ -142,10 +143,14 @@ class GradSink:
     shared encoder).  Under data parallelism its bucket's all-reduce may already be in flight when a later write
     arrives: adding a local gradient to the (partly) reduced sum would be wrong on every rank and races with the
     collective.  Such a *late* write is redirected transparently: ``buf`` / ``fresh`` then name a per-sink side buffer,
-    which ``FlatParameters.finish_backward`` all-reduces by itself and adds to the reduced gradient."""
+    which ``FlatParameters.finish_backward`` all-reduces by itself and adds to the reduced gradient.
+
+    Gradient accumulation (``FlatParameters.no_sync``): ``fresh`` is per WINDOW -- the first write since ``zero_grad``
+    overwrites, every later one, in any micro-batch, accumulates -- while the bucket counts are per PASS: ``_pass`` names
+    the pass whose count this sink has already left."""
 
     __slots__ = ("_buf", "_fresh", "bucket", "owner", "index", "unwritten", "_late", "_late_fresh", "late_written",
-                 "_zeroed", "_uncounted")
+                 "_zeroed", "_uncounted", "_pass")
 
     def __init__(self, buf: torch.Tensor, bucket: int, owner: "FlatParameters", index: int):
         self._buf = buf         # view shaped like the parameter
@@ -159,6 +164,7 @@ class GradSink:
         self.late_written = False
         self._zeroed = False    # the slice holds zeros written by finish_backward and nobody has written it since
         self._uncounted = False  # this step's bucket count does not wait for it (nobody wrote it in the previous step)
+        self._pass = 0          # the backward pass of the window (owner._pass) in which it was last counted
 
     def _is_late(self) -> bool:
         o = self.owner
@@ -185,7 +191,12 @@ class GradSink:
             self._fresh = False
             self.unwritten = False
             self._zeroed = False
+            self._pass = self.owner._pass
             if not self._uncounted:          # (a parameter the bucket did not wait for: nothing to count down)
+                self.owner._on_first_write(self)
+        elif self._pass != self.owner._pass:  # written in an earlier pass of the window: its first write of THIS pass
+            self._pass = self.owner._pass
+            if not self._uncounted:
                 self.owner._on_first_write(self)
 
 
@@ -234,6 +245,9 @@ class FlatParameters:
                        if grad_reduce_dtype not in (None, torch.float32) else None)
         self.exchange_enabled = True        # False: skip the collectives (measures the step without its exchange)
         self.defer_exchange = False         # True: no bucket launches during backward; one exchange_all() after it
+        self._no_sync = False               # inside no_sync(): a non-final micro-batch of an accumulation window
+        self._pass = 0                      # backward passes finished inside no_sync() since zero_grad
+        self._exchange_outside = False      # inside exchange_outside(): finish_backward leaves the deferred exchange out
 
         # buckets: walk parameters in reverse registration order
         bucket_elems = int(bucket_mb * (1 << 20) / 4)
@@ -262,6 +276,7 @@ class FlatParameters:
             self.sinks.append(s)
             self.bucket_size[bucket_of[i]] += 1
         self._pending = list(self.bucket_size)
+        self._armed = list(self.bucket_size)   # the counts zero_grad armed: every later pass of the window starts from them
         self._handles = []
         self._launched = [False] * len(self.bucket_ranges)
         self.exp_avg = None
@@ -338,6 +353,7 @@ class FlatParameters:
     def zero_grad(self) -> None:
         """Marks every sink fresh (first write overwrites): no memset pass."""
         self._pending = list(self.bucket_size)
+        self._pass = 0
         for s in self.sinks:
             s._fresh = True
             s._late_fresh = True
@@ -356,9 +372,61 @@ class FlatParameters:
         for b, n in enumerate(self._pending):      # (a bucket of dead parameters only: exchanged at finish_backward as before)
             if n <= 0:
                 self._pending[b] = 1 << 30
+        self._armed = list(self._pending)
+
+    # ------------------------------------------------------------------ gradient accumulation
+    @contextlib.contextmanager
+    def no_sync(self):
+        """The non-final micro-batches of a gradient-accumulation window, under DDP's name (the reference's trainer:
+        ``accumulate_grad_batches=8``, src/main.py:85):
+
+            flat.zero_grad()
+            for j in range(k):
+                with flat.no_sync() if j < k - 1 else contextlib.nullcontext():
+                    model.loss(x[j], y[j])[0].backward(seed)     # seed = flat.accumulation_scale(k), or flat.loss_grad
+                    flat.finish_backward()
+            flat.clip_grad_norm_(1.0); flat.adamw_step(...)
+
+        ``zero_grad`` opens the window; the first write of the window to a sink overwrites, every later one accumulates.
+        Inside ``no_sync`` no bucket is launched and no collective of any kind runs, and ``finish_backward`` does the
+        local part only (the deferred LayerNorm reduces; nothing is zeroed or marked unwritten) and re-arms the bucket
+        counts.  In the final micro-batch, outside, a bucket leaves when each of its sinks has been written IN THAT PASS
+        (the sums of the earlier passes are already in place); a sink that an earlier pass wrote and the final one does
+        not holds its bucket until ``finish_backward``, as a dead parameter does.  The late-write redirect works inside
+        the final pass as in a plain step.  ``unwritten`` / ``skip_mask`` mean "written in no pass of the window".  With
+        ``defer_exchange``, ``exchange_all()`` runs once, after the final pass.
+
+        LayerNorm's dgamma / dbeta reduces are deferred for FIRST writes only (functional._ln_bwd), i.e. in the first pass
+        of a window; the accumulating writes of later passes take the in-order route, which is correct and costs those
+        passes the one-launch flush."""
+        if self._no_sync:
+            raise RuntimeError("no_sync() does not nest")
+        self._no_sync = True
+        try:
+            yield self
+        finally:
+            self._no_sync = False
+
+    @contextlib.contextmanager
+    def exchange_outside(self):
+        """With ``defer_exchange``: every ``finish_backward()`` inside does the local part only, as
+        ``finish_backward(exchange=False)`` does, for a caller that launches ``exchange_all()`` itself around code that
+        calls the plain form (``graph.capture_accumulated_step`` cuts its last graph there)."""
+        self._exchange_outside = True
+        try:
+            yield self
+        finally:
+            self._exchange_outside = False
+
+    def accumulation_scale(self, k: int) -> float:
+        """Seed every backward of a window of ``k`` micro-batches with this: the summed, all-reduced gradient is then the
+        mean over the ``world * k`` micro-batches."""
+        if int(k) < 1:
+            raise ValueError("accumulation_scale: k must be >= 1")
+        return 1.0 / (self.world * int(k))
 
     def _launch_bucket(self, b: int) -> None:
-        if self._launched[b] or self.defer_exchange:
+        if self._launched[b] or self.defer_exchange or self._no_sync:
             return
         self._launched[b] = True
         if self._exchanging():
@@ -389,9 +457,14 @@ class FlatParameters:
     def finish_backward(self, exchange: bool = True) -> None:
         """Call after loss.backward(): zero gradients nobody wrote (and exclude them from the optimizer step), flush
         remaining buckets, wait for the collectives (on the compute stream, not the host), fold in late writes.
-        ``exchange=False`` (with ``defer_exchange``): local part only; ``exchange_all()`` follows."""
+        ``exchange=False`` (with ``defer_exchange``): local part only; ``exchange_all()`` follows.
+        Inside ``no_sync()``: the local part of a non-final micro-batch only (see there)."""
         from . import functional as F       # dgamma / dbeta reduces still deferred: one launch, then their sinks are written
         F.ln_flush(end_of_step=True)
+        if self._no_sync:                    # a non-final micro-batch: nothing leaves, the next pass counts its buckets anew
+            self._pass += 1
+            self._pending = list(self._armed)
+            return
         if self.comm is not None and self.comm.trace is not None:      # end of backward on the compute stream
             ev = torch.cuda.Event(enable_timing=True)
             ev.record(torch.cuda.current_stream())
@@ -407,7 +480,7 @@ class FlatParameters:
                 unwritten.append(s.index)
         self._set_skip(tuple(unwritten))
         if self.defer_exchange:
-            if exchange:
+            if exchange and not self._exchange_outside:
                 self.exchange_all()
             return
         late = [s for s in self.sinks if s.late_written]
@@ -446,18 +519,37 @@ class FlatParameters:
     # ------------------------------------------------------------------ optimizer
     # ------------------------------------------------------------------ fp16 loss scaling (BASELINE configs[4])
     def enable_loss_scaling(self, init_scale: float = 65536.0, growth_interval: int = 2000, growth: float = 2.0,
-                            backoff: float = 0.5) -> torch.Tensor:
+                            backoff: float = 0.5, accumulate: int = 1) -> torch.Tensor:
         """Dynamic loss scaling with every piece of scaler state on the device (no host sync, hipGraph-capturable).
         Returns ``loss_grad``, the device scalar to seed backward with: ``loss.backward(flat.loss_grad)``; it holds
         ``scale / world`` and is refreshed by every ``adamw_step``.  A step whose all-reduced gradient contains a
-        non-finite value is skipped on the device and halves the scale."""
+        non-finite value is skipped on the device and halves the scale.  ``accumulate``: the number of micro-batches of
+        an accumulation window (``no_sync``); ``loss_grad`` then holds ``scale * accumulation_scale(accumulate)``."""
         dev = self.data.device
+        self._loss_grad_base = self.accumulation_scale(accumulate)
         self.scaler = dict(growth_interval=int(growth_interval), growth=float(growth), backoff=float(backoff))
         self.scale_dev = torch.full((1,), float(init_scale), dtype=torch.float32, device=dev)
         self.found_inf = torch.zeros(1, dtype=torch.int32, device=dev)
         self.good_steps = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.loss_grad = torch.full((), float(init_scale) * self.loss_scale, dtype=torch.float32, device=dev)
+        self.loss_grad = torch.full((), float(init_scale) * self._loss_grad_base, dtype=torch.float32, device=dev)
         return self.loss_grad
+
+    def clip_grad_norm_(self, max_norm: float, norm_type: float = 2.0) -> torch.Tensor:
+        """torch.nn.utils.clip_grad_norm_ (Lightning's ``gradient_clip_val``) over the whole flat gradient, in two
+        launches: call it after ``finish_backward()`` (the norm is then the all-reduced gradient's, the same bits on every
+        rank) and before any ``*_step``.  One cached one-segment table over ``self.grad``; alignment padding and the
+        slices nobody wrote hold zeros and change neither norm.  Under loss scaling the scale is read from ``scale_dev``
+        on the device, so ``max_norm`` bounds the UNSCALED gradient.  Returns the norm before clipping (unscaled) as a
+        device scalar; no host synchronisation, capturable in a hipGraph.  ``norm_type``: 2 or inf.  Deviation from torch: a
+        non-finite norm leaves the gradient as it is, so that the loss-scaled step still sees the overflow and skips."""
+        ops.norm_kind(norm_type)                 # NotImplementedError for any other norm, before anything is built
+        if getattr(self, "_clip_table", None) is None:
+            if self.data.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("clip_grad_norm_ builds its segment table at the first call; make that call in a "
+                                   "warm-up step, not inside a hipGraph capture")
+            self._clip_table = ops.grad_table([self.grad])
+        scale = self.scale_dev if getattr(self, "scaler", None) is not None else None
+        return ops.grad_clip_(self._clip_table, max_norm, norm_type, scale=scale)
 
     def adamw_step(self, lr: float, weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
         """torch.optim.AdamW semantics (frame_transformer.py:127-129) in one launch.
@@ -475,7 +567,7 @@ class FlatParameters:
         if getattr(self, "scaler", None) is not None:
             ops.adamw_step_scaled_(self.data, self.grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self.scale_dev,
                                    self.found_inf, self.good_steps, self.loss_grad, lr=lr, beta1=betas[0],
-                                   beta2=betas[1], eps=eps, weight_decay=weight_decay, loss_grad_base=self.loss_scale,
+                                   beta2=betas[1], eps=eps, weight_decay=weight_decay, loss_grad_base=self._loss_grad_base,
                                    skip=self.skip_mask, **self.scaler)
             self._after_step(mirror_written=False)
             return
@@ -607,7 +699,7 @@ class FlatParameters:
                 else:
                     cur.copy_(src)
         if getattr(self, "scaler", None) is not None:
-            self.loss_grad.copy_(self.scale_dev.reshape(()) * self.loss_scale)
+            self.loss_grad.copy_(self.scale_dev.reshape(()) * self._loss_grad_base)
         self.invalidate_compute_copy()
 
     def broadcast_parameters(self, src: int = 0) -> None:

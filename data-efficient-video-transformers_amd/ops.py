@@ -1480,7 +1480,7 @@ class LarsTable:
         assert len(grads) == self.n
         self._uploaded.synchronize()
         for r, k, g in zip(self.rows, self.keep, grads):
-            _, r.grad, _ = _flat_f32(k[0], g)
+            _, r.grad, _ = _flat_f32(g if k[0] is None else k[0], g)      # (k[0] None: a row of ``grad_table``)
         self.keep = [(k[0], g, k[2], k[3]) for k, g in zip(self.keep, grads)]
         self._upload()
 
@@ -1527,6 +1527,65 @@ def lars_step_(t: LarsTable, lr_dev: Tensor, step_dev2: Tensor, *, momentum: flo
                                    t.workspace.data_ptr(), lr_dev.data_ptr(), momentum, dampening, int(bool(nesterov)),
                                    trust_coefficient, eps, step_dev2.data_ptr(), int(t.mirror_dtype != 0), t.mirror_dtype,
                                    _stream()), "dvt_lars_step")
+
+
+# ------------------------------------------------------------------ global gradient norm and clip (csrc/optim.hip)
+def grad_table(grads) -> LarsTable:
+    """A segment table over gradients alone, for ``grad_norm`` / ``grad_clip_``: the rows, plan, workspace and upload of
+    ``lars_table`` with no parameter, buffer or mirror pointer (those kernels read ``grad`` and ``numel`` only).  Empty
+    tensors are left out."""
+    grads = [g for g in grads if g.numel() > 0]
+    if not grads:
+        raise ValueError("grad_table: no gradients")
+    _need_cuda(*grads)
+    plan = lars_plan(g.numel() for g in grads)
+    pinned = torch.empty(C.sizeof(LarsSeg) * len(grads), dtype=torch.uint8, pin_memory=True)
+    rows, keep = (LarsSeg * len(grads)).from_address(pinned.data_ptr()), []
+    for r, g, begin in zip(rows, grads, plan.chunk_begin):
+        _, r.grad, r.numel = _flat_f32(g, g)
+        r.param, r.buf, r.mirror = None, None, None
+        r.chunk_begin, r.weight_decay, r.reserved = begin, 0.0, 0
+        keep.append((None, g, None, None))
+    return LarsTable(rows, pinned, plan, keep, 0, grads[0].device)
+
+
+def norm_kind(norm_type) -> int:
+    """``norm_type`` of torch.nn.utils.clip_grad_norm_ -> dvt_norm_kind; 2 and inf have kernels."""
+    if isinstance(norm_type, (int, float)) and float(norm_type) == 2.0:
+        return L.ENUMS["dvt_norm_kind"]["DVT_NORM_2"]
+    if isinstance(norm_type, (int, float)) and float(norm_type) == float("inf"):
+        return L.ENUMS["dvt_norm_kind"]["DVT_NORM_INF"]
+    raise NotImplementedError(f"norm_type={norm_type!r}: the gradient norm kernels compute the 2-norm and the inf-norm")
+
+
+def grad_norm(t: LarsTable, norm_type=2.0, *, raw: bool = False) -> Tensor:
+    """-> f32 [1] on the device: the ``norm_type`` norm (2 or inf) of all gradients of the table taken as one vector, in
+    two launches (partials, total).  ``raw``: the reduced total itself instead -- the sum of squares for norm_type 2 (the maximum either way
+    for inf)."""
+    out = torch.empty(2, dtype=torch.float32, device=t.table.device)
+    L.check(L.load().dvt_grad_norm(C.cast(t.table.data_ptr(), C.POINTER(LarsSeg)), t.n, t.plan.blocks,
+                                   t.workspace.data_ptr(), norm_kind(norm_type), out.data_ptr(), _stream()),
+            "dvt_grad_norm")
+    return out[1:2] if raw else out[0:1]
+
+
+def grad_clip_(t: LarsTable, max_norm: float, norm_type=2.0, inv_scale: Optional[Tensor] = None, *,
+               scale: Optional[Tensor] = None) -> Tensor:
+    """torch.nn.utils.clip_grad_norm_ over the table's gradients in two launches: g *= min(1, max_norm / (norm * s + 1e-6))
+    in place, s = ``inv_scale[0]`` or ``1 / scale[0]`` (device fp32 scalars; give at most one -- ``scale`` is the loss scale
+    as ``adamw_step_scaled_`` holds it) or 1.  -> f32 [1] on the device: norm * s, the norm before clipping.  A non-finite
+    norm leaves the gradients as they are (``dvt_grad_clip`` in include/dvt_hip.h)."""
+    if inv_scale is not None and scale is not None:
+        raise ValueError("grad_clip_: give inv_scale or scale, not both")
+    s = inv_scale if inv_scale is not None else scale
+    if s is not None:
+        _need_cuda(s)
+        assert s.dtype == torch.float32 and s.numel() == 1
+    out = torch.empty(1, dtype=torch.float32, device=t.table.device)
+    L.check(L.load().dvt_grad_clip(C.cast(t.table.data_ptr(), C.POINTER(LarsSeg)), t.n, t.plan.blocks,
+                                   t.workspace.data_ptr(), norm_kind(norm_type), float(max_norm), _p(s),
+                                   int(inv_scale is not None), out.data_ptr(), _stream()), "dvt_grad_clip")
+    return out
 
 
 # ------------------------------------------------------------------ per-frame CNN encoder (csrc/conv.hip)

@@ -31,6 +31,39 @@ def _zeros_like(p):
     return torch.zeros_like(p, memory_format=torch.contiguous_format)
 
 
+_clip_tables = {}          # (gradient data pointers) -> ops.LarsTable over them; one entry per set, as LARS caches its table
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ (Lightning's ``gradient_clip_val``) for the per-parameter optimizers of this module:
+    ONE norm over the gradients of all ``parameters`` that have one, then ``g *= min(1, max_norm / (norm + 1e-6))`` in
+    place, in two launches (``dvt_grad_clip``).  "Has a gradient" is the optimizers' rule (``_grad32``): a
+    ``FlatParameters`` view nobody wrote is left out, like ``grad is None``.  Returns the norm before clipping as a device
+    fp32 scalar; no host synchronisation.  The segment table is cached on the set of gradient addresses and rebuilt when
+    it changes (which may not happen inside a hipGraph capture).  ``norm_type``: 2 or inf.  ``error_if_nonfinite=True``
+    needs a host read of the norm and raises NotImplementedError; deviation from torch: a non-finite norm leaves the
+    gradients as they are instead of spreading NaN.  A model wrapped in ``dp.FlatParameters`` should call its
+    ``clip_grad_norm_`` (one segment, and the loss scale)."""
+    if error_if_nonfinite:
+        raise NotImplementedError("error_if_nonfinite=True needs a host read of the norm; check the returned scalar instead")
+    ops.norm_kind(norm_type)                  # NotImplementedError for any other norm
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [g for p in parameters for g in (_grad32(p),) if g is not None and g.numel() > 0]
+    if not grads:
+        return torch.zeros(1, dtype=torch.float32)
+    sig = tuple(g.data_ptr() for g in grads) + tuple(g.numel() for g in grads)
+    table = _clip_tables.get(sig)
+    if table is None:
+        if _capturing():
+            raise RuntimeError("the set of parameters with a gradient, or a gradient's address, changed inside a hipGraph "
+                               "capture; run a warm-up step first and keep the gradient tensors (zero_grad(set_to_none=False))")
+        if len(_clip_tables) >= 8:            # gradients that torch allocates anew every step: do not hoard their tables
+            _clip_tables.clear()
+        table = _clip_tables[sig] = ops.grad_table(grads)
+    return ops.grad_clip_(table, max_norm, norm_type)
+
+
 class _Base(torch.optim.Optimizer):
     """The one ``step()``: closure, groups, parameters with a gradient.  A subclass supplies ``_init_state`` (create what is
     missing from a parameter's state) and ``_update`` (its one kernel call)."""

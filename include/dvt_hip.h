@@ -1308,6 +1308,29 @@ int dvt_lars_step(const dvt_lars_seg* table, int n, int64_t chunks, float* works
                   float dampening, int nesterov, float trust_coefficient, float eps, int64_t* step_dev2, int mirror,
                   int mirror_dtype, dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- global gradient norm and clipping
+ * Additions within ABI v5.  The reference's trainer line, pl.Trainer(..., accumulate_grad_batches=8, precision=16, ...)
+ * (src/main.py:85), is a transformer run under Lightning, whose other knob for such runs is gradient_clip_val:
+ * torch.nn.utils.clip_grad_norm_ over all gradients between backward and the optimizer step.  csrc/optim.hip.
+ * Both entry points take a dvt_lars_seg table (dvt_lars_plan's chunks and chunk_begin) and read `grad` and `numel` of a row
+ * only: `param`, `buf` and `mirror` may be NULL, so the parameters cost no bytes.  ONE norm over the whole table.
+ * norm_kind DVT_NORM_2: total = sum g^2, norm = sqrt(total); DVT_NORM_INF: total = norm = max |g| (a NaN is kept).
+ * `workspace`: the plan's workspace_bytes, 4-byte aligned, no initial content required; it receives one partial per chunk.
+ * No atomics at all: every sum and maximum is taken in an order that numel alone fixes, so identical calls give
+ * bitwise-equal results on every rank and in a hipGraph replay.  No host synchronisation.  n == 0: nothing is launched.
+ *   dvt_grad_norm: TWO launches (partials; one block for the total).  out2 f32 [2] on the device = {norm, total}.
+ *   dvt_grad_clip: TWO launches (partials; scale -- every block forms the total from the partials itself).  coef = min(1, max_norm / (norm * inv_scale + 1e-6)), grad *= coef in
+ *     place, norm_out f32 [1] = norm * inv_scale (the norm before clipping).  inv_scale = 1 when scale_dev is NULL, else
+ *     scale_dev[0] (scale_is_inverse != 0) or 1 / scale_dev[0] (the loss scale itself, as dvt_adamw_step_scaled reads it): the
+ *     threshold applies to the unscaled gradient.  Deviation from torch: a non-finite norm leaves the gradient exactly
+ *     as it is (torch would multiply it by NaN), so that dvt_adamw_step_scaled's own found_inf check still sees the values
+ *     that overflowed and skips the step; norm_out then holds the non-finite value.  coef == 1 writes nothing either. */
+enum dvt_norm_kind { DVT_NORM_2 = 0, DVT_NORM_INF = 1 };
+int dvt_grad_norm(const dvt_lars_seg* table, int n, int64_t chunks, float* workspace, int norm_kind, float* out2,
+                  dvt_stream_t stream);
+int dvt_grad_clip(const dvt_lars_seg* table, int n, int64_t chunks, float* workspace, int norm_kind, float max_norm,
+                  const float* scale_dev, int scale_is_inverse, float* norm_out, dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- VGGish audio expert: log-mel front end, first layer
  * Additions within ABI v5.  The audio network the reference names at pretrained/models.py:13 (torchvggish, commented out:
  * torch.hub needs the network) and calls at :55-57.  csrc/audio.hip; the definition of the front end (16 kHz mono, frames
