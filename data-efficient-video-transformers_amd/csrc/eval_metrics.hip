@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "rank_layout.h"   // to_class_major_kernel, offsets_kernel
 
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -80,23 +81,6 @@ __global__ void ap_rows_kernel(const float* __restrict__ probs, const unsigned c
     }
   }
   ap_rows[n] = (float)ap;
-}
-
-// [N, C] -> class-major keys [C, N] (f32) and labels [C, N] (u8)
-__global__ void to_class_major_kernel(const float* __restrict__ probs, const unsigned char* __restrict__ labels,
-                                      int64_t N, int C, float* __restrict__ keys, unsigned char* __restrict__ vals) {
-  const int64_t total = N * C;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t n = i / C;
-    const int c = (int)(i % C);
-    keys[(int64_t)c * N + n] = probs[i];
-    vals[(int64_t)c * N + n] = labels[i] != 0;
-  }
-}
-
-__global__ void offsets_kernel(int* __restrict__ off, int C, int64_t N) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c <= C) off[c] = (int)(c * N);
 }
 
 // one thread per class over its descending-sorted scores; also the support-weighted and the samples average

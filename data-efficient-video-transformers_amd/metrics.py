@@ -16,6 +16,12 @@ an ``SSLEvaluator`` on the detached embedding (three launches, csrc/probe.hip), 
 the probe's probabilities, and at the end of the validation epoch it logs weighted F1 / recall / precision / average
 precision of the binarised predictions at six thresholds, from one launch of integer counts
 (``ops.multilabel_sweep_counts``) and float64 ratios on the host.
+
+``AUROC``, ``F1`` and ``ConfusionMatrix`` carry the torchmetrics-0.6 names the reference imports next to
+``AveragePrecision`` (frame_transformer.py:8, basicmlp.py:20; scikit-learn's ``confusion_matrix``, callbacks.py:14): AUROC
+from one sort and a parallel rank pass over stored rows (``ops.rank_metrics``), F1 and the confusion matrix from integer
+counts that reduce over the ranks with one all-reduce (``reduce_counts``).  ``MITEval`` (callbacks.py:85-98) is the accuracy
+callback of the MIT runs.
 """
 from __future__ import annotations
 
@@ -364,6 +370,263 @@ class AveragePrecision:
 
     def reset(self) -> None:
         self.preds, self.target = [], []
+
+
+def reduce_counts(state: torch.Tensor, group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
+    """Sum an integer state over the ranks with ONE all-reduce (a few C^2 integers instead of ``gather_rows`` of every
+    prediction); returns a new tensor and leaves ``state`` as it is, so ``compute()`` can be called again.  Device or CPU
+    tensors (gloo); without an initialised process group, or alone in it, the state itself comes back."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return state
+    total = state.clone()
+    dist.all_reduce(total, op=dist.ReduceOp.SUM, group=group)
+    return total
+
+
+_AUROC_AVERAGES = ("macro", "weighted", "micro", "samples", "none")
+_F1_AVERAGES = ("micro", "macro", "weighted", "samples", "none")
+
+
+def _average(average, allowed, who: str) -> str:
+    average = "none" if average is None else average
+    if average not in allowed:
+        raise ValueError(f"{who}: average must be one of {allowed}, got {average!r}")
+    return average
+
+
+def _num_classes(num_classes, who: str) -> int:
+    if not isinstance(num_classes, int) or isinstance(num_classes, bool) or num_classes < 1:
+        raise ValueError(f"{who}: num_classes must be a positive integer, got {num_classes!r}")
+    return num_classes
+
+
+def _auroc_of(r: "ops.RankMetrics", average: str) -> torch.Tensor:
+    if average == "samples":
+        return r.samples_sum / r.valid_rows                       # the mean over the rows that have both kinds
+    return {"macro": r.macro, "weighted": r.weighted, "micro": r.micro, "none": r.auroc}[average]
+
+
+class AUROC:
+    """Stand-in for ``torchmetrics.AUROC(num_classes=C, average=...)`` on multilabel rows (frame_transformer.py:8,
+    :114-115 and the commented log lines :276-343): calling the object with ``(preds, target)`` accumulates a batch on
+    the device, ``compute()`` returns a float64 DEVICE scalar (``average="none"``: the [C] vector) without a host
+    synchronisation and ``reset()`` clears it.  One descending sort per class and a parallel tie-aware rank pass
+    (``ops.rank_metrics``); rank-based, so logits and probabilities give the same value.
+
+    average: ``macro`` / ``weighted`` over the classes that have both kinds, ``micro`` over all N C elements, ``samples``
+    over the rows that have both kinds (C <= 64), ``none``.  A class without positives or without negatives is NaN in
+    ``none`` and left out of the averages (torchmetrics raises there, which would need a host read)."""
+
+    def __init__(self, num_classes: int, average: Optional[str] = "macro"):
+        self.num_classes = _num_classes(num_classes, "AUROC")
+        self.average = _average(average, _AUROC_AVERAGES, "AUROC")
+        self.preds: List[torch.Tensor] = []
+        self.target: List[torch.Tensor] = []
+
+    def __call__(self, preds: torch.Tensor, target: torch.Tensor) -> None:
+        self.update(preds, target)
+
+    def update(self, preds: torch.Tensor, target: torch.Tensor) -> None:
+        if preds.shape[-1] != self.num_classes or target.shape[-1] != self.num_classes:
+            raise ValueError(f"expected {self.num_classes} classes")
+        self.preds.append(preds.detach().reshape(-1, self.num_classes))
+        self.target.append(target.detach().reshape(-1, self.num_classes))
+
+    def compute(self, group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
+        if not self.preds:
+            raise RuntimeError("AUROC.compute() before any update")
+        p = gather_rows(torch.cat(self.preds), group)
+        t = gather_rows(torch.cat(self.target), group)
+        return _auroc_of(ops.rank_metrics(p, t, micro=self.average == "micro", samples=self.average == "samples"),
+                         self.average)
+
+    def reset(self) -> None:
+        self.preds, self.target = [], []
+
+
+def auroc(preds: torch.Tensor, target: torch.Tensor, num_classes: Optional[int] = None, average: Optional[str] = "macro"
+          ) -> torch.Tensor:
+    """Functional form of ``AUROC``: preds / target [N, C] on the device -> float64 device scalar ([C] for ``none``)."""
+    m = AUROC(preds.shape[-1] if num_classes is None else num_classes, average)
+    m.update(preds, target)
+    return m.compute()
+
+
+def f1_from_counts(tp: torch.Tensor, fp: torch.Tensor, fn: torch.Tensor, average: str) -> torch.Tensor:
+    """Per-class TP / FP / FN (int64 [C], on the host) -> ``f1_score(..., average=average, zero_division=0)`` in float64."""
+    tp, fp, fn = tp.double(), fp.double(), fn.double()
+
+    def ratio(num, den):
+        return torch.where(den > 0, num / den.clamp(min=1.0), torch.zeros_like(num))
+
+    per = ratio(2 * tp, 2 * tp + fp + fn)
+    if average == "none":
+        return per
+    if average == "micro":
+        return ratio(2 * tp.sum(), 2 * tp.sum() + fp.sum() + fn.sum())
+    if average == "macro":
+        return per.mean()
+    sup = tp + fn                                                 # weighted
+    return ratio((per * sup).sum(), sup.sum())
+
+
+class _CountMetric:
+    """Shared update of ``F1`` and ``ConfusionMatrix``: the state is integer counts on the device, never stored rows --
+    ``cm`` int64 [C, C] (+ the skipped rows) for multiclass input, ``counts`` int64 [4, C] (TP / FP / FN / TN) for
+    multilabel input.  The mode comes from the target: [N] integers -> multiclass (preds: [N, C] logits, the row's argmax,
+    or [N] integers), [N, C] -> multilabel (``preds > threshold``)."""
+
+    def __init__(self, num_classes: int, threshold: float, who: str):
+        self.num_classes = _num_classes(num_classes, who)
+        self.threshold = float(threshold)
+        self._who = who
+        self.reset()
+
+    def reset(self) -> None:
+        self.mode: Optional[str] = None
+        self.cm = self.ignored = self.counts = None
+
+    def __call__(self, preds: torch.Tensor, target: torch.Tensor) -> None:
+        self.update(preds, target)
+
+    def _mode_of(self, preds: torch.Tensor, target: torch.Tensor) -> str:
+        C = self.num_classes
+        if target.dim() == 1 and not target.is_floating_point():
+            if (preds.dim() == 2 and preds.shape[1] != C) or preds.dim() not in (1, 2) or preds.shape[0] != target.shape[0]:
+                raise ValueError(f"{self._who}: preds {tuple(preds.shape)} for {target.shape[0]} targets of {C} classes")
+            return "multiclass"
+        if target.dim() == 2 and tuple(preds.shape) == tuple(target.shape):
+            if target.shape[1] != C:
+                raise ValueError(f"{self._who}: expected {C} classes, got {target.shape[1]}")
+            return "multilabel"
+        raise ValueError(f"{self._who}: target {tuple(target.shape)} {target.dtype} with preds {tuple(preds.shape)}: give "
+                         "[N] integer targets (multiclass) or [N, C] targets with [N, C] scores (multilabel)")
+
+    def update(self, preds: torch.Tensor, target: torch.Tensor) -> None:
+        preds, target = preds.detach(), target.detach()
+        mode = self._mode_of(preds, target)
+        if self.mode not in (None, mode):
+            raise ValueError(f"{self._who}: {mode} input after {self.mode} input; reset() first")
+        C, dev = self.num_classes, preds.device
+        if mode == "multiclass":
+            if self.cm is None:
+                self.cm, self.ignored = ops.zeros((C, C), torch.int64, dev), ops.zeros((1,), torch.int64, dev)
+            ops.confusion_matrix(preds, target, C, self.cm, self.ignored)
+        else:
+            if self.counts is None:
+                self.counts = ops.zeros((4, C), torch.int64, dev)
+            ops.multilabel_counts(preds, target, self.threshold, self.counts)
+        self.mode = mode
+
+    def _state(self, group) -> torch.Tensor:
+        if self.mode is None:
+            raise RuntimeError(f"{self._who}.compute() before any update")
+        return reduce_counts(self.cm if self.mode == "multiclass" else self.counts, group)
+
+
+class F1(_CountMetric):
+    """Stand-in for ``torchmetrics.F1(num_classes=C, threshold=0.5, average="micro")`` (basicmlp.py:20,
+    frame_transformer.py:8): a user assigns ``model.f1 = metrics.F1(22)``.  The state is the integer counts of
+    ``_CountMetric`` (under data parallelism one small all-reduce, ``reduce_counts``); ``compute()`` copies them to the host
+    once and forms the ratios in float64 there (zero_division = 0, as scikit-learn's ``f1_score``) -> a CPU float64 scalar,
+    [C] for ``none``.  ``samples`` is multilabel only: the float64 sum over rows of the per-row F1 (the row sums of
+    ``ops.multilabel_report_counts``) and the row count join the state."""
+
+    def __init__(self, num_classes: int, threshold: float = 0.5, average: Optional[str] = "micro"):
+        self.average = _average(average, _F1_AVERAGES, "F1")
+        super().__init__(num_classes, threshold, "F1")
+
+    def reset(self) -> None:
+        super().reset()
+        self.row_f1 = None                                        # f64 [2] on the device: sum of the per-row F1, rows
+
+    def update(self, preds: torch.Tensor, target: torch.Tensor) -> None:
+        if self.average == "samples" and self._mode_of(preds, target) != "multilabel":
+            raise ValueError("F1: average='samples' is defined for multilabel input only")
+        super().update(preds, target)
+        if self.average != "samples":
+            return
+        _, sums = ops.multilabel_report_counts(preds.detach(), target.detach(), self.threshold)
+        add = torch.stack((sums[2], torch.full_like(sums[2], float(preds.shape[0]))))
+        self.row_f1 = add if self.row_f1 is None else self.row_f1 + add
+
+    def compute(self, group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
+        state = self._state(group)
+        if self.average == "samples":
+            s = reduce_counts(self.row_f1, group).cpu()
+            return s[0] / s[1]
+        state = state.cpu()                                       # the one device->host copy
+        if self.mode == "multiclass":
+            tp = state.diagonal()
+            fp, fn = state.sum(0) - tp, state.sum(1) - tp
+        else:
+            tp, fp, fn = state[0], state[1], state[2]
+        return f1_from_counts(tp, fp, fn, self.average)
+
+
+class ConfusionMatrix(_CountMetric):
+    """Stand-in for ``torchmetrics.ConfusionMatrix(num_classes=C, multilabel=False, threshold=0.5)`` and scikit-learn's
+    ``confusion_matrix`` (callbacks.py:14): ``compute()`` returns the int64 DEVICE tensor [C, C] (rows = target, columns =
+    prediction), or [C, 2, 2] = [[TN, FP], [FN, TP]] per class for multilabel input (``multilabel_confusion_matrix``).
+    ``ignored`` counts the rows whose target was outside [0, C)."""
+
+    def __init__(self, num_classes: int, multilabel: bool = False, threshold: float = 0.5):
+        self.multilabel = bool(multilabel)
+        super().__init__(num_classes, threshold, "ConfusionMatrix")
+
+    def update(self, preds: torch.Tensor, target: torch.Tensor) -> None:
+        mode = self._mode_of(preds.detach(), target.detach())
+        if (mode == "multilabel") != self.multilabel:
+            raise ValueError(f"ConfusionMatrix(multilabel={self.multilabel}) got {mode} input")
+        super().update(preds, target)
+
+    def compute(self, group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
+        state = self._state(group)
+        if self.mode == "multiclass":
+            return state
+        tp, fp, fn, tn = state.unbind(0)
+        return torch.stack((torch.stack((tn, fp), 1), torch.stack((fn, tp), 1)), 1)
+
+
+def f1(preds: torch.Tensor, target: torch.Tensor, num_classes: int, threshold: float = 0.5,
+       average: Optional[str] = "micro") -> torch.Tensor:
+    """Functional form of ``F1``."""
+    m = F1(num_classes, threshold, average)
+    m.update(preds, target)
+    return m.compute()
+
+
+def confusion_matrix(preds: torch.Tensor, target: torch.Tensor, num_classes: int, multilabel: bool = False,
+                     threshold: float = 0.5) -> torch.Tensor:
+    """Functional form of ``ConfusionMatrix``."""
+    m = ConfusionMatrix(num_classes, multilabel, threshold)
+    m.update(preds, target)
+    return m.compute()
+
+
+class MITEval:
+    """callbacks.py:85-98, the accuracy callback src/main.py:46-50 attaches to every MIT run: at the end of a validation epoch
+    ``acc = sum(running_logits == running_labels) / len(running_labels)`` is logged under ``"val/accuracy/epoch"`` and the
+    accumulators are reset.  The comparison is counted on the device (``ops.count_equal``), under data parallelism the two
+    integers (matches, rows) are summed over the ranks (``reduce_counts``), and one device->host copy fetches them for the
+    logged scalar.  ``best_acc`` is kept as the reference keeps it (its update is commented out there); the reference's
+    ``print`` of element 0 is not reproduced."""
+
+    def __init__(self, group: Optional[dist.ProcessGroup] = None):
+        self.best_acc = 0
+        self.group = group
+
+    def on_validation_epoch_end(self, trainer, pl_module) -> float:
+        labels = torch.cat(pl_module.running_labels)
+        preds = torch.cat(pl_module.running_logits)
+        state = torch.cat((ops.count_equal(preds, labels),
+                           torch.tensor([labels.shape[0]], dtype=torch.int64).to(labels.device)))
+        matches, rows = reduce_counts(state, self.group).cpu().tolist()
+        acc = matches / (rows * 1.0)
+        pl_module.log("val/accuracy/epoch", acc, on_step=False, on_epoch=True)
+        pl_module.running_labels = []
+        pl_module.running_logits = []
+        return acc
 
 
 class CosineSimilarity:

@@ -12,7 +12,7 @@ All arithmetic is HIP (``functional.mlp_chain``: GEMMs with bias / ReLU epilogue
 ``dvt_ce_labels_*``).  ``compute_dtype`` (attribute, default bf16) sets the activation dtype; fp32 is exact fp32 arithmetic.
 
 Deliberate deviations: the torchmetrics ``f1`` / ``acc`` objects, unused by the reference's steps, are
-not built; ``validation_step`` does not print the outputs and labels.
+not constructed here (``metrics.F1`` is the device-side stand-in: ``model.f1 = metrics.F1(22)``); ``validation_step`` does not print the outputs and labels.
 """
 from __future__ import annotations
 

@@ -2838,6 +2838,158 @@ def multilabel_sweep_counts(probs: Tensor, labels: Tensor, thresholds) -> Tuple[
     return counts, support
 
 
+# ------------------------------------------------------------------ rank metrics and counts (csrc/rank_metrics.hip)
+class RankMetrics(NamedTuple):
+    """What ``rank_metrics`` returns: device tensors, no host synchronisation.  ``micro`` / ``micro_two_u`` /
+    ``micro_positives`` are NaN / -1 / -1 without ``micro=True``; ``samples_sum`` / ``valid_rows`` NaN / -1 without
+    ``samples=True``."""
+    auroc: Tensor              # f64 [C], NaN for a class without both kinds
+    ap: Tensor                 # f64 [C], 0 for a class without positives
+    positives: Tensor          # int64 [C]
+    two_u: Tensor              # int64 [C]: twice the Mann-Whitney U of the class (ties count half)
+    macro: Tensor              # f64 []: mean AUROC over the valid classes
+    weighted: Tensor           # f64 []: support-weighted AUROC over the valid classes
+    micro: Tensor              # f64 []: AUROC of all N C elements as one column
+    samples_sum: Tensor        # f64 []: sum over the valid rows of the per-row AUROC
+    valid_classes: Tensor      # int64 []
+    valid_rows: Tensor         # int64 []
+    micro_two_u: Tensor        # int64 []
+    micro_positives: Tensor    # int64 []
+
+
+RANK_BLOCK = None
+
+
+def rank_metrics_block() -> int:
+    """Elements of a sorted column that one workgroup of the rank pass reduces (dvt_rank_metrics_block)."""
+    global RANK_BLOCK
+    if RANK_BLOCK is None:
+        RANK_BLOCK = int(L.load().dvt_rank_metrics_block())
+    return RANK_BLOCK
+
+
+def _scores_and_mask(name: str, probs: Tensor, labels: Tensor) -> Tuple[Tensor, Tensor]:
+    """The dtype plumbing of ``average_precision``: a 16-bit score is cast to f32 (exact, so ties stay ties), a label mask
+    becomes u8."""
+    _need_cuda(probs, labels)
+    if probs.dim() != 2 or tuple(labels.shape) != tuple(probs.shape):
+        raise ValueError(f"{name}: probs {tuple(probs.shape)} and labels {tuple(labels.shape)} must be the same [N, C]")
+    probs = probs.contiguous() if probs.dtype == torch.float32 else cast(probs.contiguous(), torch.float32)
+    lab = labels.contiguous()
+    if lab.dtype != torch.uint8:
+        lab = (lab != 0).to(torch.uint8)
+    return probs, lab
+
+
+def rank_metrics(probs: Tensor, labels: Tensor, micro: bool = False, samples: bool = False) -> RankMetrics:
+    """AUROC and average precision per class from one descending sort and a parallel tie-aware rank pass
+    (dvt_rank_metrics), with the macro / weighted averages and, on request, the micro AUROC and the per-row ("samples",
+    C <= 64) sum."""
+    probs, lab = _scores_and_mask("rank_metrics", probs, labels)
+    N, Cn = probs.shape
+    lib = L.load()
+    flags = (L.ENUMS["dvt_rank_flags"]["DVT_RANK_MICRO"] if micro else 0) | (
+        L.ENUMS["dvt_rank_flags"]["DVT_RANK_SAMPLES"] if samples else 0)
+    nbytes = lib.dvt_rank_metrics_workspace_bytes(N, Cn, flags)
+    if nbytes == 0:
+        raise ValueError("rank_metrics: empty input or N*C >= 2^31")
+    ws = workspace(nbytes, probs.device)
+    na, nc = L.MACROS["DVT_RANK_N_AVERAGES"], L.MACROS["DVT_RANK_N_COUNTS"]
+    f = torch.empty((2 * Cn + na,), dtype=torch.float64, device=probs.device)
+    i = torch.empty((2 * Cn + nc,), dtype=torch.int64, device=probs.device)
+    L.check(lib.dvt_rank_metrics(probs.data_ptr(), lab.data_ptr(), N, Cn, flags, f.data_ptr(), f[Cn:].data_ptr(),
+                                 i.data_ptr(), i[Cn:].data_ptr(), f[2 * Cn:].data_ptr(), i[2 * Cn:].data_ptr(),
+                                 ws.data_ptr(), _stream()), "dvt_rank_metrics")
+    A, K = L.ENUMS["dvt_rank_average"], L.ENUMS["dvt_rank_count"]
+    avg, cnt = f[2 * Cn:], i[2 * Cn:]
+    return RankMetrics(f[:Cn], f[Cn:2 * Cn], i[:Cn], i[Cn:2 * Cn], avg[A["DVT_RANK_AVG_MACRO"]],
+                       avg[A["DVT_RANK_AVG_WEIGHTED"]], avg[A["DVT_RANK_AVG_MICRO"]], avg[A["DVT_RANK_AVG_SAMPLES_SUM"]],
+                       cnt[K["DVT_RANK_CNT_VALID_CLASSES"]], cnt[K["DVT_RANK_CNT_VALID_ROWS"]],
+                       cnt[K["DVT_RANK_CNT_MICRO_TWO_U"]], cnt[K["DVT_RANK_CNT_MICRO_POSITIVES"]])
+
+
+def confusion_matrix(preds: Tensor, target: Tensor, num_classes: int, cm: Optional[Tensor] = None,
+                     ignored: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """cm int64 [C, C] (rows = target, columns = prediction) and the count of skipped rows, int64 [1]
+    (dvt_confusion_matrix).  ``preds``: logits [N, C] (f32 / bf16 / fp16; the row's argmax, lowest index among equal
+    maxima) or integer classes [N].  With ``cm`` and ``ignored`` given the counts are ADDED to them in place."""
+    _need_cuda(preds, target)
+    Cn = int(num_classes)
+    target = target.contiguous().to(torch.int64)
+    N = target.shape[0]
+    if target.dim() != 1:
+        raise ValueError(f"confusion_matrix: target {tuple(target.shape)} must be [N]")
+    logits = None
+    if preds.dim() == 2:
+        if tuple(preds.shape) != (N, Cn) or preds.dtype not in _DT:
+            raise ValueError(f"confusion_matrix: logits {tuple(preds.shape)} {preds.dtype} for N = {N}, C = {Cn}")
+        logits = preds.contiguous()
+    elif preds.dim() == 1 and preds.shape[0] == N and not preds.is_floating_point():
+        preds = preds.contiguous().to(torch.int64)
+    else:
+        raise ValueError(f"confusion_matrix: preds {tuple(preds.shape)} {preds.dtype} must be [N, C] logits or [N] integers")
+    if (cm is None) != (ignored is None):
+        raise ValueError("confusion_matrix: give both cm and ignored, or neither")
+    accumulate = cm is not None
+    if accumulate:
+        if (cm.dtype, ignored.dtype) != (torch.int64, torch.int64) or tuple(cm.shape) != (Cn, Cn) or ignored.numel() != 1 \
+                or not (cm.is_contiguous() and cm.is_cuda and ignored.is_cuda):
+            raise ValueError("confusion_matrix: cm must be a contiguous int64 [C, C] and ignored an int64 [1] on the device")
+    else:
+        cm = torch.empty((Cn, Cn), dtype=torch.int64, device=target.device)
+        ignored = torch.empty((1,), dtype=torch.int64, device=target.device)
+    if N == 0:                                                    # nothing to count (an empty tensor has no address)
+        return (cm, ignored) if accumulate else (zeros((Cn, Cn), torch.int64, target.device),
+                                                 zeros((1,), torch.int64, target.device))
+    L.check(L.load().dvt_confusion_matrix(_p(logits), dt(logits) if logits is not None else L.F32,
+                                          None if logits is not None else preds.data_ptr(), target.data_ptr(), N, Cn,
+                                          int(accumulate), cm.data_ptr(), ignored.data_ptr(), _stream()),
+            "dvt_confusion_matrix")
+    return cm, ignored
+
+
+def multilabel_counts(probs: Tensor, labels: Tensor, threshold: float, state: Optional[Tensor] = None) -> Tensor:
+    """state int64 [4, C] = TP / FP / FN / TN per class of ``probs > threshold`` (strict, compared in f32) against the
+    multilabel targets (dvt_multilabel_counts).  With ``state`` given the counts are ADDED to it in place."""
+    probs, lab = _scores_and_mask("multilabel_counts", probs, labels)
+    N, Cn = probs.shape
+    accumulate = state is not None
+    if accumulate:
+        if state.dtype != torch.int64 or tuple(state.shape) != (4, Cn) or not (state.is_contiguous() and state.is_cuda):
+            raise ValueError("multilabel_counts: state must be a contiguous int64 [4, C] on the device")
+    else:
+        state = torch.empty((4, Cn), dtype=torch.int64, device=probs.device)
+    if N == 0:
+        return state if accumulate else zeros((4, Cn), torch.int64, probs.device)
+    L.check(L.load().dvt_multilabel_counts(probs.data_ptr(), lab.data_ptr(), N, Cn, float(threshold), int(accumulate),
+                                           state.data_ptr(), _stream()), "dvt_multilabel_counts")
+    return state
+
+
+def count_equal(a: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """int64 [1]: the number of positions where ``a == b`` (dvt_count_equal); integer tensors are compared as int64,
+    anything else as f32.  With ``out`` given the count is ADDED to it in place."""
+    _need_cuda(a, b)
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"count_equal: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    ints = not (a.is_floating_point() or b.is_floating_point())
+    if ints:
+        a, b = a.contiguous().to(torch.int64), b.contiguous().to(torch.int64)
+    else:
+        a, b = (t.contiguous() if t.dtype == torch.float32 else
+                (cast(t.contiguous(), torch.float32) if t.dtype in _DT else t.contiguous().to(torch.float32)) for t in (a, b))
+    accumulate = out is not None
+    if accumulate:
+        if out.dtype != torch.int64 or out.numel() != 1 or not out.is_cuda:
+            raise ValueError("count_equal: out must be an int64 [1] on the device")
+    else:
+        out = torch.empty((1,), dtype=torch.int64, device=a.device)
+    n = a.numel()
+    L.check(L.load().dvt_count_equal(a.data_ptr() if n else None, b.data_ptr() if n else None, n, int(ints), int(accumulate),
+                                     out.data_ptr(), _stream()), "dvt_count_equal")
+    return out
+
+
 # ------------------------------------------------------------------ VGGish audio expert (csrc/audio.hip)
 LOGMEL_VARIANTS = {name[len("DVT_LOGMEL_"):].lower(): v for name, v in L.ENUMS["dvt_logmel_variant"].items()}
 # The spectrum dvt_logmel_examples computes by default; DESIGN 4.16 has the grounds and both forms' measured times and errors.

@@ -1398,6 +1398,57 @@ int dvt_cam_render(const float* scaled, int64_t N, int Ti, int Hi, int Wi, int T
                    const void* frames, int frames_f32, const uint8_t* jet, uint8_t* overlay, float image_weight, int use_rgb,
                    dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- rank metrics and counts (AUROC, AP, F1, confusion matrix)
+ * Additions within ABI v5: new entry points only, no existing layout or meaning changed.  What the reference names next to
+ * AveragePrecision: `from torchmetrics import AUROC, F1, AveragePrecision` (src/models/frame_transformer.py:8; val_auroc /
+ * train_auroc at :114-115, the log lines at :276-343), torchmetrics.F1(num_classes=22) (src/models/basicmlp.py:20), and
+ * scikit-learn's confusion_matrix with the MITEval accuracy callback (src/callbacks/callbacks.py:14, :85-98; attached to every
+ * MIT run at src/main.py:46-50).  csrc/rank_metrics.hip.  Everything runs asynchronously on `stream` with no host
+ * synchronisation; integer results are exact and floating-point sums go in a fixed order without atomics, so identical calls
+ * give bitwise-equal results.
+ *
+ *   dvt_rank_metrics: probs f32 [N][C], labels u8 [N][C] (non-zero = positive), N * C < 2^31.  One class-major layout and ONE
+ *     descending segmented radix sort per call (as dvt_average_precision), then a tie-aware parallel reduction of every sorted
+ *     column in blocks of dvt_rank_metrics_block() elements (host only; three launches: per-block aggregates, the pass with
+ *     carries read from the aggregates, the totals -- no workgroup waits on another inside a launch).  A tie group is a
+ *     maximal run of equal scores (-0.0 == +0.0); with tp the inclusive count of positives, P the positives and Nn = N - P,
+ *     per group g = [b, e]: pos_g = tp[e] - tp[b-1], neg_g = (e - b + 1) - pos_g,
+ *         two_u[c]  = sum_g neg_g (2 tp[b-1] + pos_g)                  (int64, exact)
+ *         auroc[c]  = two_u / (2 P Nn) in float64; NaN for a class without positives or without negatives
+ *         ap[c]     = sum_g (pos_g / P) (tp[e] / (e + 1)) in float64; 0 for a class without positives
+ *     (roc_auc_score / average_precision_score of scikit-learn with average=None, to about 1e-16).
+ *     averages f64 [DVT_RANK_N_AVERAGES], indexed by dvt_rank_average: macro and support-weighted AUROC over the VALID
+ *     classes (both kinds present; NaN when there is none), micro AUROC (the same pass over all N C elements as one column:
+ *     only with DVT_RANK_MICRO, else NaN), and with DVT_RANK_SAMPLES (C <= 64 then) the fixed-order SUM of the per-row AUROC
+ *     over the valid rows, else NaN.  counts int64 [DVT_RANK_N_COUNTS], indexed by dvt_rank_count: valid classes, valid rows,
+ *     the micro column's 2U and positives (-1 where the flag is off).  Scikit-learn and torchmetrics raise on a column
+ *     without both kinds; raising needs a host read, hence NaN.  NaN scores are undefined behaviour of the metric.
+ *     workspace >= dvt_rank_metrics_workspace_bytes(N, C, flags) (0: empty input or N * C >= 2^31).
+ *   dvt_confusion_matrix: cm int64 [C][C], rows = target, columns = prediction.  Predictions are `logits` [N][C] of `dtype`
+ *     (the row's argmax, the lowest index among equal maxima) or `preds` int64 [N]; exactly one of the two is non-NULL.
+ *     target int64 [N].  accumulate != 0 ADDS to cm and cm_ignored, 0 overwrites them.  A row whose target (or integer
+ *     prediction) is outside [0, C) is skipped and counted in cm_ignored[1].  N == 0 is allowed.
+ *   dvt_multilabel_counts: state int64 [4][C] = TP, FP, FN, TN per class of `probs > threshold` (strict, compared in fp32 as
+ *     dvt_multilabel_sweep_counts does) against labels u8 [N][C]; same `accumulate`; C <= 1024; N == 0 is allowed.
+ *   dvt_count_equal: out int64 [1] = the number of i < n with a[i] == b[i], both int64 (is_int64 != 0) or both f32: the
+ *     `torch.sum(running_logits == running_labels)` of MITEval (callbacks.py:91); same `accumulate`; n == 0 is allowed. */
+enum dvt_rank_flags { DVT_RANK_MICRO = 1, DVT_RANK_SAMPLES = 2 };
+enum dvt_rank_average { DVT_RANK_AVG_MACRO = 0, DVT_RANK_AVG_WEIGHTED = 1, DVT_RANK_AVG_MICRO = 2, DVT_RANK_AVG_SAMPLES_SUM = 3 };
+enum dvt_rank_count { DVT_RANK_CNT_VALID_CLASSES = 0, DVT_RANK_CNT_VALID_ROWS = 1, DVT_RANK_CNT_MICRO_TWO_U = 2,
+                      DVT_RANK_CNT_MICRO_POSITIVES = 3 };
+#define DVT_RANK_N_AVERAGES 4
+#define DVT_RANK_N_COUNTS 4
+int dvt_rank_metrics_block(void);
+size_t dvt_rank_metrics_workspace_bytes(int64_t N, int C, int flags);
+int dvt_rank_metrics(const float* probs, const unsigned char* labels, int64_t N, int C, int flags, double* auroc, double* ap,
+                     int64_t* positives, int64_t* two_u, double* averages, int64_t* counts, void* workspace,
+                     dvt_stream_t stream);
+int dvt_confusion_matrix(const void* logits, int dtype, const int64_t* preds, const int64_t* target, int64_t N, int C,
+                         int accumulate, int64_t* cm, int64_t* cm_ignored, dvt_stream_t stream);
+int dvt_multilabel_counts(const float* probs, const unsigned char* labels, int64_t N, int C, float threshold, int accumulate,
+                          int64_t* state, dvt_stream_t stream);
+int dvt_count_equal(const void* a, const void* b, int64_t n, int is_int64, int accumulate, int64_t* out, dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- data-parallel gradient exchange
  * The reference is single-GPU (pl.Trainer(gpus=1), src/main.py:87); north_star partitions the clips of the global
  * batch over the 8 GPUs of a node, and the only exchange of the path is the SUM of the parameter gradients.  RCCL over
