@@ -540,7 +540,8 @@ __global__ void bce_bwd_kernel(const T* __restrict__ z, const float* __restrict_
   }
 }
 
-// One wave per row: lse(student) - student[argmax teacher]; first max wins (torch.argmax).
+// One wave per row: lse(student) - student[argmax teacher]; first max wins (torch.argmax).  A lane's first element is
+// taken whatever its value, so a teacher row that is all -inf yields index 0 as torch.argmax does, never C.
 template <typename T, bool FWD>
 __global__ void ce_argmax_kernel(const T* __restrict__ st, const T* __restrict__ te,
                                  const float* __restrict__ gloss, float* __restrict__ loss,
@@ -558,7 +559,7 @@ __global__ void ce_argmax_kernel(const T* __restrict__ st, const T* __restrict__
     for (int64_t c = lane; c < C; c += 64) {
       m = fmaxf(m, to_f32<T>(s[c]));
       const float tv = to_f32<T>(t[c]);
-      if (tv > tm) { tm = tv; ti = c; }
+      if (tv > tm || ti == C) { tm = tv; ti = c; }
     }
     m = wave_max(m);
 #pragma unroll

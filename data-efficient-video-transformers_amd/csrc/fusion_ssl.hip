@@ -44,7 +44,8 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const T* __restrict__ d
   }
 }
 
-// out[r] = <a[r], b[r]> / max(||a[r]|| * ||b[r]||, eps)     (nn.CosineSimilarity(dim=1), frame_transformer.py:121,257)
+// out[r] = <a[r], b[r]> / (max(||a[r]||, eps) * max(||b[r]||, eps)): each norm is clamped on its own, as torch's
+// nn.CosineSimilarity(dim=1) does (frame_transformer.py:121,257) and as l2norm_fwd_kernel above does for NT-Xent
 template <typename T>
 __global__ __launch_bounds__(256) void cosine_rows_kernel(const T* __restrict__ a, const T* __restrict__ b,
                                                           float* __restrict__ out, int64_t rows, int D, float eps) {
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(256) void cosine_rows_kernel(const T* __restrict__ 
     ab = fmaf(x, y, ab); aa = fmaf(x, x, aa); bb = fmaf(y, y, bb);
   }
   ab = wave_sum(ab); aa = wave_sum(aa); bb = wave_sum(bb);
-  if (lane == 0) out[r] = ab / fmaxf(sqrtf(aa) * sqrtf(bb), eps);
+  if (lane == 0) out[r] = ab / (fmaxf(sqrtf(aa), eps) * fmaxf(sqrtf(bb), eps));
 }
 
 // y = a * sigmoid(b)

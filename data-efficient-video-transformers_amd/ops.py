@@ -1257,7 +1257,8 @@ def l2norm_rows_bwd(dy: Tensor, y: Tensor, inv: Tensor, eps: float) -> Tensor:
 
 
 def cosine_rows(a: Tensor, b: Tensor, eps: float = 1e-8) -> Tensor:
-    """nn.CosineSimilarity(dim=1): [rows, D] x [rows, D] -> f32 [rows] (no gradient)."""
+    """nn.CosineSimilarity(dim=1): [rows, D] x [rows, D] -> f32 [rows] (no gradient):
+    <a, b> / (max(||a||, eps) * max(||b||, eps)), each norm clamped on its own as torch does."""
     _need_cuda(a, b)
     a, b = a.detach().contiguous(), b.detach().contiguous()
     assert a.shape == b.shape and a.dim() == 2 and a.dtype == b.dtype

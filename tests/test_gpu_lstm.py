@@ -1,7 +1,13 @@
 """LSTM baseline on the MI355X against CPU fp32 torch (nn.LSTM / nn.Linear / nn.BCELoss: the arithmetic the reference's
 src/models/LSTM.py executes).  fp32 within 1e-4 relative L2; bf16 within 1e-2 against the same CPU fp32 computation on
-bf16-rounded inputs and weights (the yardstick of test_gpu_ops.py)."""
+bf16-rounded inputs and weights (the yardstick of test_gpu_ops.py); fp16 within four times the error of the CPU fp32
+restatement that rounds G, h_t, dG and dx to fp16 where the kernels do (tests/rowwise_ref.py lstm_layer_restated).
+
+The chain's two entry points are also called directly (float64 recurrence, NaN-poisoned buffers), and the forward step's
+K loop gets a two-step run whose second step sums tau * (+-1) per 8-wide group: tests/test_rowwise_cpu.py proves that
+operand set sees a dropped, doubled or moved group, chunk or wave share."""
 import copy
+import math
 
 import pytest
 import torch
@@ -13,6 +19,11 @@ pytestmark = pytest.mark.gpu
 
 F32_TOL = 1e-4
 BF16_TOL = 1e-2
+# fp16: 4 x the restatement's own relative L2 error against CPU fp32 torch, measured on the CPU over every (B, T, F, H) of
+# test_one_layer_fwd_bwd_matches_torch: outputs 1.92e-4 .. 2.76e-4, gradients 2.27e-4 .. 4.05e-4
+FP16_TOL_OUT = 4 * 2.76e-4
+FP16_TOL_GRAD = 4 * 4.05e-4
+KSTEP_TOL = 1e-4    # tests/test_rowwise_cpu.py: a fault moves some gate by >= 0.64, the reference's fp32 evaluation by <= 3.5e-8
 
 
 @pytest.fixture(scope="module")
@@ -24,7 +35,9 @@ def dvt():
     return dvt_amd
 
 
-def _tol(dtype):
+def _tol(dtype, grad=False):
+    if dtype == torch.float16:
+        return FP16_TOL_GRAD if grad else FP16_TOL_OUT
     return F32_TOL if dtype == torch.float32 else BF16_TOL
 
 
@@ -37,8 +50,10 @@ def _layer_params(Fdim, H, gen):
     return [((torch.rand(shape, generator=gen) * 2 - 1) * s) for shape in ((4 * H, Fdim), (4 * H, H), (4 * H,), (4 * H,))]
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("B,T,Fdim,H", [(4, 16, 64, 32), (64, 200, 512, 512), (3, 7, 48, 64), (5, 1, 32, 16)])
+# (17, 3, 32, 48): a ragged second batch tile, wave 1 gets half a chunk; (16, 5, 8, 160): wave 0 takes a second pass
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+@pytest.mark.parametrize("B,T,Fdim,H", [(4, 16, 64, 32), (64, 200, 512, 512), (3, 7, 48, 64), (5, 1, 32, 16),
+                                        (17, 3, 32, 48), (33, 2, 16, 80), (16, 5, 8, 160), (1, 4, 16, 16)])
 def test_one_layer_fwd_bwd_matches_torch(dvt, dtype, B, T, Fdim, H):
     gen = torch.Generator().manual_seed(B * 1000 + T * 10 + H)
     w_ih, w_hh, b_ih, b_hh = _layer_params(Fdim, H, gen)
@@ -62,15 +77,15 @@ def test_one_layer_fwd_bwd_matches_torch(dvt, dtype, B, T, Fdim, H):
     torch.autograd.backward([out, last], [gout.cuda().to(dtype), glast.cuda().to(dtype)])
     torch.cuda.synchronize()
 
-    tol = _tol(dtype)
+    tol, gtol = _tol(dtype), _tol(dtype, grad=True)
     assert rel_l2(out.float(), out_r) < tol
     assert rel_l2(last.float(), out_r[:, -1]) < tol
-    assert rel_l2(xg.grad.float(), xr.grad) < tol
+    assert rel_l2(xg.grad.float(), xr.grad) < gtol
     for p, r, name in zip(ps, (ref.weight_ih_l0, ref.weight_hh_l0, ref.bias_ih_l0, ref.bias_hh_l0),
                           ("dW_ih", "dW_hh", "db_ih", "db_hh")):
         assert p.grad.dtype == torch.float32
         e = rel_l2(p.grad, r.grad)
-        assert e < tol, f"{name} rel {e:.2e}"
+        assert e < gtol, f"{name} rel {e:.2e}"
 
 
 def _reference_model(n_features, hidden, layers, dropout):
@@ -206,7 +221,7 @@ def test_three_adam_steps_match_torch(dvt):
         assert rel_l2(p.detach().cpu() - init[n], r - init[n]) < 1e-3, n
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
 def test_training_step_is_bitwise_reproducible(dvt, dtype):
     torch.manual_seed(3)
     ref = _reference_model(256, 128, 2, 0.0)
@@ -239,3 +254,90 @@ def test_validation_step_collects_sigmoid_outputs(dvt):
     assert torch.equal(m.running_labels[0].cpu(), y)
     assert abs(float(loss) - float(nn.BCELoss()(p_r, y))) < 1e-4
     assert "val_loss" in m.logged if hasattr(m, "logged") else True
+
+
+# ---------------------------------------------------------------- the chain's entry points, called directly
+def _poison(*ts):
+    for t in ts:
+        if t is not None:
+            t.fill_(math.nan)
+
+
+def _seq_fwd_poisoned(dvt, G, w_hh, b_ih, b_hh, B, T, want_last):
+    """ops.lstm_seq_fwd with every output NaN before the launch (torch.empty inside ops hands out NaN-filled memory)"""
+    from tests.test_gpu_rowwise import guarded
+    with guarded(dvt.ops):
+        return dvt.ops.lstm_seq_fwd(G, w_hh, b_ih, b_hh, B, T, want_last=want_last)
+
+
+@pytest.mark.parametrize("variant", ["no_bias", "dh_seq", "dh_last", "both"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+def test_lstm_seq_fwd_bwd_direct(dvt, dtype, variant):
+    from tests import rowwise_ref as R
+    from tests.test_gpu_rowwise import guarded
+    B, T, H = 17, 3, 48
+    gen = torch.Generator().manual_seed(77)
+    G = (torch.randn(B * T, 4 * H, generator=gen, dtype=torch.float64)).to(dtype)
+    w_hh = ((torch.rand(4 * H, H, generator=gen, dtype=torch.float64) * 2 - 1) / H ** 0.5).to(dtype)
+    b_ih = b_hh = None
+    if variant != "no_bias":
+        b_ih, b_hh = (torch.randn(4 * H, generator=gen) * 0.1 for _ in range(2))
+    dh_seq = torch.randn(B, T, H, generator=gen, dtype=torch.float64).to(dtype) if variant in ("no_bias", "dh_seq", "both") else None
+    dh_last = torch.randn(B, H, generator=gen, dtype=torch.float64).to(dtype) if variant in ("dh_last", "both") else None
+    dev = lambda t: None if t is None else t.cuda()
+
+    h_out, h_prev, gates, c, h_last = _seq_fwd_poisoned(dvt, dev(G), dev(w_hh), dev(b_ih), dev(b_hh), B, T, True)
+    torch.cuda.synchronize()
+    assert not torch.isnan(gates).any() and not torch.isnan(c).any() and not torch.isnan(h_out.float()).any()
+    assert not torch.isnan(h_prev.float()).any() and not torch.isnan(h_last.float()).any()
+    assert torch.equal(h_prev[:, 0], torch.zeros_like(h_prev[:, 0]))
+    assert torch.equal(h_prev[:, 1:], h_out[:, :-1])
+    assert torch.equal(h_last, h_out[:, -1])
+    # every step against the float64 step from the state the kernel itself carried into it (h_prev, c of the step before):
+    # a 16-bit h_t that lands on the other side of a rounding boundary than float64's does not leak into the next check
+    G3, hp, ck = G.reshape(B, T, 4 * H), h_prev.cpu(), c.cpu()
+    gmag = float(G.double().abs().max())
+    for t in range(T):
+        cprev = ck[:, t - 1] if t > 0 else torch.zeros(B, H)
+        args = (G3[:, t], hp[:, t], cprev, w_hh, b_ih, b_hh)
+        rg, rc, rh = R.ref64(R.lstm_step, *args)
+        cg, cc, ch = R.fp32_chain(R.lstm_step, *args)
+        R.assert_close(gates.cpu()[:, t], rg, cg, gmag, f"gates {variant} t={t}")
+        R.assert_close(ck[:, t], rc, cc, 1.0, f"c {variant} t={t}")
+        R.assert_close(h_out.cpu()[:, t], rh, ch, 1.0, f"h_out {variant} t={t}")
+
+    # backward from the contract's own gates and c (the CPU fp32 chain of the whole recurrence): the exact float64 chain is
+    # the reference, the fp32 chain that stores every step's dG in the dtype is the yardstick
+    _, cg, cc = R.lstm_recurrence(G.float(), w_hh.float(), b_ih, b_hh, B, T, h_dtype=None if dtype == torch.float32 else dtype)
+    cg, cc = cg.detach().contiguous(), cc.detach().contiguous()
+    with guarded(dvt.ops):
+        dG = dvt.ops.lstm_seq_bwd(dev(w_hh), dev(cg), dev(cc), dev(dh_seq), dev(dh_last))
+    torch.cuda.synchronize()
+    ref = R.ref64(R.lstm_bwd_chain, w_hh, cg, cc, dh_seq, dh_last)
+    chain = R.fp32_chain(R.lstm_bwd_chain, w_hh, cg, cc, dh_seq, dh_last, store_dtype=None if dtype == torch.float32 else dtype)
+    mag = max(float(t.double().abs().max()) for t in (dh_seq, dh_last) if t is not None)
+    R.assert_close(dG.cpu(), ref, chain, mag, f"dG {variant}")
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+def test_forward_step_k_loop_sums_every_group_once(dvt, dtype):
+    """step 0 leaves h_0 = +-tau at one unit of every 8-wide group (tau = tanh(1) in the dtype) and exactly 0 elsewhere;
+    step 1 then sums tau * (+-1) over the groups: gates[:, 1] = act(tau n) with the integer n of rowwise_ref.kstep_operands"""
+    from tests import rowwise_ref as R
+    B, H = R.KSTEP_B, R.KSTEP_H
+    G, w_hh, n = R.kstep_operands(dtype)
+    h_out, h_prev, gates, c, _ = _seq_fwd_poisoned(dvt, G.cuda(), w_hh.cuda(), None, None, B, 2, False)
+    torch.cuda.synchronize()
+    h0 = h_out[:, 0].cpu().double()
+    taus = h0.abs()[h0 != 0].unique()
+    assert taus.numel() == 1, taus
+    tau = float(taus)
+    want = torch.tensor(math.tanh(1.0), dtype=torch.float64).to(dtype)
+    got = torch.tensor(tau, dtype=torch.float64).to(dtype)
+    if dtype == torch.float32:
+        assert abs(tau - math.tanh(1.0)) <= 2.0 ** -24                      # one fp32 ulp at 0.76
+    else:
+        assert abs(int(R.ordinal(got.reshape(1))) - int(R.ordinal(want.reshape(1)))) <= 1
+    assert torch.equal((h0 != 0).reshape(B, H // 8, 8).sum(2), torch.ones(B, H // 8, dtype=torch.int64))
+    err = float((gates[:, 1].cpu().double() - R.kstep_gates(n, tau)).abs().max())
+    assert err <= KSTEP_TOL, err
