@@ -112,6 +112,8 @@ BnAffine = STRUCTS["dvt_bn_affine"]
 PackEntry = STRUCTS["dvt_pack_entry"]
 HeadBceDesc = STRUCTS["dvt_head_bce_desc"]
 EmitEntry = STRUCTS["dvt_emit_entry"]
+RolloutDesc = STRUCTS["dvt_rollout_desc"]
+RolloutPlanInfo = STRUCTS["dvt_rollout_plan_info"]
 
 ABI_VERSION = MACROS["DVT_ABI_VERSION"]            # bumped with every descriptor layout change; load() refuses another
 F32, BF16, F16 = (ENUMS["dvt_dtype"][n] for n in ("DVT_F32", "DVT_BF16", "DVT_F16"))

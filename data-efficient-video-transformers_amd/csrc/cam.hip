@@ -19,6 +19,7 @@
 // Every sum is fp32 in a fixed order, the extrema are order-free, nothing is atomic: identical calls give bitwise-equal
 // results.  All pointers are the caller's; everything runs on the caller's stream.
 #include "common.h"
+#include "cam_scale.h"          // block_extrema and the scaling itself (shared with attn_rollout.hip)
 
 #include <cmath>
 
@@ -141,21 +142,6 @@ __device__ __forceinline__ void clip_rows(const T* __restrict__ A, int C, int p0
   __syncthreads();
 }
 
-// minimum and maximum of the workgroup's (mn, mx) -> every thread
-__device__ __forceinline__ void block_extrema(float& mn, float& mx, float* red, int waves) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, o, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  }
-  if (lane == 0) { red[2 * wid] = mn; red[2 * wid + 1] = mx; }
-  __syncthreads();
-  mn = red[0]; mx = red[1];
-  for (int w = 1; w < waves; ++w) { mn = fminf(mn, red[2 * w]); mx = fmaxf(mx, red[2 * w + 1]); }
-  __syncthreads();
-}
-
 template <typename T>
 __global__ __launch_bounds__(kNT) void cam_map_fused_kernel(const T* __restrict__ A, const T* __restrict__ G, int P, int C,
                                                             int method, float* __restrict__ weights, float* __restrict__ raw,
@@ -170,11 +156,11 @@ __global__ __launch_bounds__(kNT) void cam_map_fused_kernel(const T* __restrict_
   float mn = INFINITY, mx = -INFINITY;
   for (int p = threadIdx.x; p < P; p += kNT) { mn = fminf(mn, rawv[p]); mx = fmaxf(mx, rawv[p]); }
   block_extrema(mn, mx, s.red, kWaves);
-  const float den = 1e-7f + (mx - mn);
+  const float den = cam_scale_den(mn, mx);
   for (int p = threadIdx.x; p < P; p += kNT) {
     const float r = rawv[p];
     if (raw) raw[n * P + p] = r;
-    scaled[n * P + p] = (r - mn) / den;
+    scaled[n * P + p] = cam_scale_value(r, mn, den);
   }
 }
 
@@ -225,9 +211,9 @@ __global__ __launch_bounds__(kChunk) void cam_scale_kernel(const float* __restri
     mx = fmaxf(mx, ext[(n * gridDim.y + ch) * 2 + 1]);
   }
   block_extrema(mn, mx, red, kChunk / 64);
-  const float den = 1e-7f + (mx - mn);
+  const float den = cam_scale_den(mn, mx);
   const int p = blockIdx.y * kChunk + threadIdx.x;
-  if (p < P) scaled[n * P + p] = (scaled[n * P + p] - mn) / den;
+  if (p < P) scaled[n * P + p] = cam_scale_value(scaled[n * P + p], mn, den);
 }
 
 inline bool fused_form(int64_t P, int64_t C) { return P <= DVT_CAM_FUSED_MAX_P && P * C <= DVT_CAM_FUSED_MAX_ELEMS; }

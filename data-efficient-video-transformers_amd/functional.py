@@ -14,6 +14,7 @@ into ``x`` inside the LayerNorm backward kernel.
 """
 from __future__ import annotations
 
+import contextlib
 from collections import namedtuple
 from typing import Optional
 
@@ -534,6 +535,30 @@ def attention_core(q: Tensor, k: Tensor, v: Tensor, scale: float) -> Tensor:
 # ---------------------------------------------------------------------------
 # Residual branches of the pre-norm Transformer (vit.py:30-75)
 # ---------------------------------------------------------------------------
+# What attention rollout (rollout.py) needs of one attention layer, kept by reference while ``attention_tap()`` is active:
+# kind "dense" (q, k of every token), "cls" (the last layer's single query against all keys: q is [S, H, 1, dh]) or "folded"
+# (the single query with folded K / V projections: P [S, N, 8], the normalised probabilities; q, k, lse are None).  q, k
+# are the [S, H, L, dh] views the attention launch read (of ``packed``, the qkv / kv buffer that owns the memory), lse
+# [S, H, Lq] the one it wrote; seq_first tells the packed rows' order ((n s) instead of (s n)).
+AttnTap = namedtuple("AttnTap", "kind q k lse heads dh seq_first packed P")
+_attn_tap = None
+
+
+@contextlib.contextmanager
+def attention_tap():
+    """``with attention_tap() as layers:`` -- every ``attn_block`` / ``attn_block_cls`` forward inside appends one AttnTap to
+    ``layers``, in execution order.  The tensors exist in those forwards anyway; the tap keeps references and launches
+    nothing.  With no tap active nothing is kept.  Taps nest (the inner one records); leaving restores the outer one, also
+    when the body raises."""
+    global _attn_tap
+    outer, layers = _attn_tap, []
+    _attn_tap = layers
+    try:
+        yield layers
+    finally:
+        _attn_tap = outer
+
+
 def _split_qkv(qkv: Tensor, S: int, N: int, heads: int, dh: int, seq_first: bool):
     """Packed [rows, 3*h*dh] -> three [S(batch), H, N(seq), dh] strided views (no copies).
     Rows are (s n) for batch-first input and (n s) for seq-first input."""
@@ -592,6 +617,8 @@ class _AttnBlock(torch.autograd.Function):
         if attn_dropout > 0.0:                        # nn.MultiheadAttention(dropout=p): Philox mask on the probabilities
             drop = (attn_dropout, _rng.tensor(x.device), _rng.take(S * heads * N * N))
         lse = ops.attention_fwd(q, k, v, _heads_view(o_mem, seq_first), dh ** -0.5, drop)
+        if _attn_tap is not None:
+            _attn_tap.append(AttnTap("dense", q, k, lse, heads, dh, seq_first, qkv, None))
         ctx.drop = drop
         o2 = o_mem.view(M, inner)
         if w_out is not None:
@@ -702,6 +729,8 @@ class _AttnBlockCls(torch.autograd.Function):
             q = ops.linear_fwd(xn0, wqkv[:inner])                                                  # [S, inner]
             R = ops.heads_expand(q, wqkv[inner:2 * inner], heads, dh ** -0.5)                      # r_h = scale Wk_h^T q_h
             A, lse, P, mean, rstd = ops.attn_cls_fwd(x3, g, bb, eps, R)                            # one pass over x
+            if _attn_tap is not None:
+                _attn_tap.append(AttnTap("folded", None, None, None, heads, dh, False, None, P))
             o = ops.heads_contract(A, wqkv[2 * inner:], 1.0, g, bb)                                # o_h = Wv_h (gamma A_h + beta)
             y = ops.linear_fwd(o, wo, _f32(b_out), epilogue=L.EPI_RESIDUAL, residual=x3[:, 0])
             ctx.save_for_backward(x2, g, bb, mean0, rstd0, xn0, wqkv, wo, q, o, R, A, lse, P, mean, rstd)
@@ -716,6 +745,8 @@ class _AttnBlockCls(torch.autograd.Function):
         o = torch.empty((S, inner), dtype=T, device=x.device)
         lse = ops.attention_fwd(q.view(S, 1, heads, dh).permute(0, 2, 1, 3), k4, v4,
                                 o.view(S, 1, heads, dh).permute(0, 2, 1, 3), dh ** -0.5)
+        if _attn_tap is not None:
+            _attn_tap.append(AttnTap("cls", q.view(S, 1, heads, dh).permute(0, 2, 1, 3), k4, lse, heads, dh, False, kv, None))
         y = ops.linear_fwd(o, wo, _f32(b_out), epilogue=L.EPI_RESIDUAL, residual=x3[:, 0],
                            out_dtype=torch.float32 if mixed else None)
         ctx.save_for_backward(x2, g, mean, rstd, xn, wqkv, wo, q, kv, o, lse)

@@ -3144,3 +3144,117 @@ def cam_render(scaled: Tensor, size, frames: Optional[Tensor] = None, use_rgb: b
                                         int(frames is not None and frames.dtype == torch.float32), _p(jet), _p(overlay),
                                         float(image_weight), int(bool(use_rgb)), _stream()), "dvt_cam_render")
     return mask, overlay
+
+
+# ------------------------------------------------------------------ attention rollout (csrc/attn_rollout.hip)
+ROLLOUT_FORMS = _enum_names("dvt_rollout_form", "DVT_ROLLOUT_F_")
+ROLLOUT_UNIFORM = L.MACROS["DVT_ROLLOUT_UNIFORM"]
+
+
+class RolloutPlan(NamedTuple):
+    """What one dvt_rollout_step call launches (dvt_rollout_plan): the form (ROLLOUT_FORMS), waves per workgroup, the MFMA
+    form's 32-key steps and query parts (0 otherwise) and the dynamic LDS bytes."""
+    form: str
+    waves: int = 0
+    key_steps: int = 0
+    query_parts: int = 0
+    lds: int = 0
+
+
+def _rollout_desc(q: Tensor, k: Tensor, lse: Optional[Tensor], r_in: Optional[Tensor], r_out: Optional[Tensor],
+                  query: int, residual: float, scale: Optional[float]):
+    """q [S, H, Lq, dh] and k [S, H, N, dh]: strided views with unit stride in the last dim, one dtype; Lq is N or 1."""
+    if q.dim() != 4 or k.dim() != 4 or q.stride(3) != 1 or k.stride(3) != 1 or q.dtype != k.dtype:
+        raise TypeError("rollout_step: q and k must be [S, H, L, dh] views of one dtype, dh contiguous")
+    S, H, Lq, dh = q.shape
+    N = k.shape[2]
+    if tuple(k.shape) != (S, H, N, dh) or Lq not in (N, 1):
+        raise TypeError(f"rollout_step: q {tuple(q.shape)} and k {tuple(k.shape)} do not pair (Lq is N or 1)")
+    if lse is not None and (lse.dtype != torch.float32 or lse.numel() != S * H * Lq or not lse.is_contiguous()):
+        raise TypeError("rollout_step: lse must be a contiguous f32 tensor [S, H, Lq]")
+    if r_in is not None and (r_in.dtype != torch.float32 or tuple(r_in.shape) != (S, N) or not r_in.is_contiguous()):
+        raise TypeError("rollout_step: r_in must be a contiguous f32 tensor [S, N]")
+    if r_in is None and not (query == ROLLOUT_UNIFORM or 0 <= query < N):
+        raise ValueError(f"rollout_step: without r_in, query = {query} must be a token index below {N} or ROLLOUT_UNIFORM")
+    if r_in is not None and Lq == 1:
+        raise ValueError("rollout_step: a layer with one query row takes the one-hot start (r_in None, query >= 0)")
+    if not 0.0 <= residual <= 1.0:
+        raise ValueError(f"rollout_step: residual = {residual} is outside [0, 1]")
+    d = L.RolloutDesc()
+    d.q, d.k, d.lse, d.r_in, d.r_out = q.data_ptr(), k.data_ptr(), _p(lse), _p(r_in), _p(r_out)
+    d.S, d.H, d.N, d.Lq, d.dh = S, H, N, Lq, dh
+    d.q_sb, d.q_sh, d.q_sl = q.stride(0), q.stride(1), q.stride(2)
+    d.k_sb, d.k_sh, d.k_sl = k.stride(0), k.stride(1), k.stride(2)
+    d.query, d.rho, d.scale, d.dtype = int(query), float(residual), float(dh ** -0.5 if scale is None else scale), dt(q)
+    return d
+
+
+def rollout_plan(q: Tensor, k: Tensor, r_in: Optional[Tensor] = None, *, query: int = 0, residual: float = 0.5,
+                 scale: Optional[float] = None) -> RolloutPlan:
+    """What ``rollout_step`` launches for the same views (dvt_rollout_plan: the launcher's own decisions, no launch, no
+    device needed -- shapes, strides, addresses and types count; CPU tensors are fine).  Raises where the launcher refuses."""
+    d = _rollout_desc(q, k, None, r_in, None, query, residual, scale)
+    d.lse = d.r_out = 256                       # looked at for NULL-ness only
+    r = L.RolloutPlanInfo()
+    L.check(L.load().dvt_rollout_plan(C.byref(d), C.byref(r)), "dvt_rollout_plan")
+    return RolloutPlan(ROLLOUT_FORMS[r.form], r.waves, r.key_steps, r.query_parts, r.lds)
+
+
+def rollout_step(q: Tensor, k: Tensor, lse: Tensor, r_in: Optional[Tensor] = None, *, query: int = 0,
+                 residual: float = 0.5, scale: Optional[float] = None) -> Tensor:
+    """One layer of the rollout recurrence (dvt_rollout_step): r_out[s, j] = residual r_in[s, j] + (1 - residual) / H
+    sum_h sum_i r_in[s, i] softmax(scale q k^T)[s, h, i, j], with q [S, H, Lq, dh] / k [S, H, N, dh] the strided views and
+    lse [S, H, Lq] the log-sum-exp ``attention_fwd`` took and returned.  r_in f32 [S, N], or None for a start vector that is
+    never stored: the one-hot of token ``query``, or 1 / N with query = ROLLOUT_UNIFORM.  Lq == 1: a layer that ran for token
+    ``query`` alone (r_in None).  scale defaults to dh^-1/2, the model's.  -> r_out f32 [S, N]."""
+    _need_cuda(q, k, lse, r_in)
+    if lse is None:
+        raise TypeError("rollout_step: lse is required")
+    r_out = torch.empty((q.shape[0], k.shape[2]), dtype=torch.float32, device=q.device)
+    d = _rollout_desc(q, k, lse, r_in, r_out, query, residual, scale)
+    with _timed("rollout_step", (q.numel() + k.numel()) * q.element_size()):
+        L.check(L.load().dvt_rollout_step(C.byref(d), _stream()), "dvt_rollout_step")
+    return r_out
+
+
+def rollout_from_probs(P: Tensor, heads: int, *, query: int = 0, residual: float = 0.5) -> Tensor:
+    """The start of the recurrence from the folded single-query layer (dvt_rollout_from_probs): P f32 [S, N, 8] as
+    ``attn_cls_fwd`` returns it (normalised probabilities of the query, head h of key j at P[s, j, h]) ->
+    r f32 [S, N] = residual e_query + (1 - residual) mean over the first ``heads`` heads."""
+    _need_cuda(P)
+    if P.dim() != 3 or P.shape[2] != 8 or P.dtype != torch.float32:
+        raise TypeError("rollout_from_probs: expected P f32 [S, N, 8]")
+    S, N, _ = P.shape
+    if not 1 <= heads <= 8:
+        raise ValueError(f"rollout_from_probs: heads = {heads} is outside 1 .. 8")
+    if not 0 <= query < max(N, 1):
+        raise ValueError(f"rollout_from_probs: query = {query} is no token index below {N}")
+    if not 0.0 <= residual <= 1.0:
+        raise ValueError(f"rollout_from_probs: residual = {residual} is outside [0, 1]")
+    P = P.contiguous()
+    r = torch.empty((S, N), dtype=torch.float32, device=P.device)
+    if S == 0 or N == 0:
+        return r
+    L.check(L.load().dvt_rollout_from_probs(P.data_ptr(), S, N, int(heads), int(query), float(residual), r.data_ptr(),
+                                            _stream()), "dvt_rollout_from_probs")
+    return r
+
+
+def rollout_video(r_space: Tensor, r_time: Tensor, want_raw: bool = True):
+    """r_space f32 [B*T, n + 1] (sequence b*T + f) and r_time f32 [B, T + 1], CLS entries first -> (raw, scaled) f32
+    [B, T, n]: raw[b, f, p] = r_time[b, 1 + f] r_space[b*T + f, 1 + p] (None unless want_raw) and the same scaled per clip as
+    ``cam_map`` scales its maps (dvt_rollout_video, one launch)."""
+    _need_cuda(r_space, r_time)
+    if r_space.dim() != 2 or r_time.dim() != 2 or r_space.dtype != torch.float32 or r_time.dtype != torch.float32:
+        raise TypeError("rollout_video: expected f32 r_space [B*T, n + 1] and r_time [B, T + 1]")
+    B, T, n = r_time.shape[0], r_time.shape[1] - 1, r_space.shape[1] - 1
+    if T <= 0 or n <= 0 or r_space.shape[0] != B * T:
+        raise ValueError(f"rollout_video: r_space {tuple(r_space.shape)} is not B*T rows for r_time {tuple(r_time.shape)}")
+    r_space, r_time = r_space.contiguous(), r_time.contiguous()
+    scaled = torch.empty((B, T, n), dtype=torch.float32, device=r_space.device)
+    raw = torch.empty((B, T, n), dtype=torch.float32, device=r_space.device) if want_raw else None
+    if B == 0:
+        return raw, scaled
+    L.check(L.load().dvt_rollout_video(r_space.data_ptr(), r_time.data_ptr(), B, T, n, _p(raw), scaled.data_ptr(), _stream()),
+            "dvt_rollout_video")
+    return raw, scaled

@@ -1449,6 +1449,65 @@ int dvt_multilabel_counts(const float* probs, const unsigned char* labels, int64
                           int64_t* state, dvt_stream_t stream);
 int dvt_count_equal(const void* a, const void* b, int64_t n, int is_int64, int accumulate, int64_t* out, dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- attention rollout (Abnar & Zuidema, 2020)
+ * Additions within ABI v5: new entry points only.  What a transformer attends to, from the attention the model already
+ * computes at src/models/vit.py:51-53 (P = softmax(scale q k^T) per head; nn.MultiheadAttention inside
+ * nn.TransformerEncoderLayer for the FrameTransformer, frame_transformer.py:41-44); csrc/attn_rollout.hip.  With
+ * A_l = rho I + (1 - rho) mean_h P_l^h the rollout of a start vector r0 is r0^T A_L ... A_1: only that ROW is formed, one
+ * vector-matrix product per layer, and no N x N tensor exists anywhere:
+ *     r_out[s, j] = rho r_in[s, j] + (1 - rho) / H sum_h sum_i r_in[s, i] exp(scale q_i . k_j - lse[s, h, i])
+ * Probabilities and r are fp32 throughout (nothing is rounded to 16 bits after the exponential); every sum has a fixed
+ * order and nothing is atomic, so identical calls give bitwise-equal results.  Everything runs asynchronously on `stream`
+ * with the caller's buffers; S == 0 launches nothing.
+ *   dvt_rollout_step: q [S][H][Lq][dh] and k [S][H][N][dh] as strided views (element (s, h, l, e) at q[s*q_sb + h*q_sh +
+ *     l*q_sl + e], the fields of dvt_attn_desc), lse f32 [S][H][Lq] as dvt_attention_fwd wrote it, r_in f32 [S][N] or NULL,
+ *     r_out f32 [S][N] (not r_in).  r_in == NULL stands for a start vector that is never stored: the one-hot of token
+ *     `query` (>= 0), or the uniform vector 1 / N (query == DVT_ROLLOUT_UNIFORM: the mean-pooled temporal stack).  Lq is N,
+ *     or 1 for a layer that ran for one query only (dvt_attention_fwd with Lq == 1: row 0 of q IS token `query`; r_in must be
+ *     NULL and query >= 0 then).  Two forms (dvt_rollout_plan names the one a descriptor takes):
+ *       MFMA     16-bit dtypes, dh == 64, N <= 512, Lq == N, a stored or uniform r_in, 16-byte aligned q / k and strides that
+ *                are multiples of 8: one workgroup per sequence, S^T = K Q^T on mfma_f32_16x16x32 with the query on the lane;
+ *       GENERIC  any dtype, dh and N that fits LDS, on the fp32 FMA; every one-hot start (one query row) takes it.
+ *     What neither form takes is refused (DVT_ERR_UNSUPPORTED), never computed wrongly.
+ *   dvt_rollout_from_probs: the start of the recurrence where the last layer ran on the folded single-query path: P f32
+ *     [S][N][8] as dvt_attn_cls_fwd returns it (normalised probabilities of the CLS query, head h of key j at P[(s*N + j)*8
+ *     + h]) -> r_out[s, j] = rho [j == query] + (1 - rho) / H sum_h P[s, j, h].
+ *   dvt_rollout_video: r_space f32 [B*T][n + 1] (sequence b*T + f: frame f of clip b) and r_time f32 [B][T + 1], both with
+ *     the CLS entry first -> raw[b, f, p] = r_time[b, 1 + f] r_space[b*T + f, 1 + p] (optional) and `scaled`, the same map
+ *     scaled per clip exactly as dvt_cam_map scales its maps; both f32 [B][T][n].  One launch, one workgroup per clip. */
+#define DVT_ROLLOUT_UNIFORM -1
+#define DVT_ROLLOUT_MFMA_MAX_N 512
+typedef struct dvt_rollout_desc {
+  const void* q;
+  const void* k;
+  const float* lse;
+  const float* r_in;
+  float* r_out;
+  int64_t S, H, N, Lq, dh;
+  int64_t q_sb, q_sh, q_sl;
+  int64_t k_sb, k_sh, k_sl;
+  int64_t query;
+  float rho;
+  float scale;
+  int32_t dtype;
+} dvt_rollout_desc;
+enum dvt_rollout_form { DVT_ROLLOUT_F_NONE = 0, DVT_ROLLOUT_F_MFMA = 1, DVT_ROLLOUT_F_GENERIC = 2 };
+typedef struct dvt_rollout_plan_info {
+  int32_t form;       /* enum dvt_rollout_form; NONE when S == 0 */
+  int32_t waves;      /* waves per workgroup */
+  int32_t key_steps;  /* MFMA: 32-key steps, one per wave column; else 0 */
+  int32_t query_parts; /* MFMA: wave rows the 16-query tiles are dealt to; else 0 */
+  int64_t lds;        /* dynamic LDS bytes */
+} dvt_rollout_plan_info;
+/* What dvt_rollout_step would launch for desc, from the launcher's own decisions (host only, runs without a device; the
+ * pointers are looked at for NULL-ness and alignment only).  Returns what the launcher returns for a descriptor it refuses. */
+int dvt_rollout_plan(const dvt_rollout_desc* desc, dvt_rollout_plan_info* info);
+int dvt_rollout_step(const dvt_rollout_desc* desc, dvt_stream_t stream);
+int dvt_rollout_from_probs(const float* P, int64_t S, int64_t N, int64_t H, int64_t query, float rho, float* r_out,
+                           dvt_stream_t stream);
+int dvt_rollout_video(const float* r_space, const float* r_time, int64_t B, int64_t T, int64_t n, float* raw, float* scaled,
+                      dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- data-parallel gradient exchange
  * The reference is single-GPU (pl.Trainer(gpus=1), src/main.py:87); north_star partitions the clips of the global
  * batch over the 8 GPUs of a node, and the only exchange of the path is the SUM of the parameter gradients.  RCCL over
