@@ -365,7 +365,7 @@ class AveragePrecision:
             raise RuntimeError("AveragePrecision.compute() before any update")
         p = gather_rows(torch.cat(self.preds), group)
         t = gather_rows(torch.cat(self.target), group)
-        _, _, per_class = ops.average_precision(p.float() if p.dtype != torch.float32 else p, t)
+        _, _, per_class = ops.average_precision(p, t)
         return list(per_class.unbind(0))
 
     def reset(self) -> None:

@@ -1178,13 +1178,22 @@ def frames_autoaugment(frames_u8: Tensor, table, mean=None, std=None, out_dtype:
     return out
 
 
-def f1_samples(probs: Tensor, labels: Tensor, thresholds) -> Tensor:
-    """samples-averaged F1 of ``probs > t`` for every t (callbacks.py:38-41) -> f32 [T] on the device."""
+def _scores_and_mask(name: str, probs: Tensor, labels: Tensor) -> Tuple[Tensor, Tensor]:
+    """The dtype plumbing of every metrics wrapper: a 16-bit score is cast to f32 (exact, so ties stay ties), a label mask
+    becomes u8."""
     _need_cuda(probs, labels)
+    if probs.dim() != 2 or tuple(labels.shape) != tuple(probs.shape):
+        raise ValueError(f"{name}: probs {tuple(probs.shape)} and labels {tuple(labels.shape)} must be the same [N, C]")
     probs = probs.contiguous() if probs.dtype == torch.float32 else cast(probs.contiguous(), torch.float32)
     lab = labels.contiguous()
     if lab.dtype != torch.uint8:
-        lab = (lab != 0).to(torch.uint8)          # dtype plumbing of a label mask
+        lab = (lab != 0).to(torch.uint8)
+    return probs, lab
+
+
+def f1_samples(probs: Tensor, labels: Tensor, thresholds) -> Tensor:
+    """samples-averaged F1 of ``probs > t`` for every t (callbacks.py:38-41) -> f32 [T] on the device."""
+    probs, lab = _scores_and_mask("f1_samples", probs, labels)
     N, Cn = probs.shape
     th = [float(t) for t in thresholds]
     lib = L.load()
@@ -1199,11 +1208,7 @@ def f1_samples(probs: Tensor, labels: Tensor, thresholds) -> Tensor:
 def average_precision(probs: Tensor, labels: Tensor):
     """-> (samples-averaged AP [1], support-weighted AP [1], per-class AP [C]) f32 device tensors
     (``average_precision_score`` of callbacks.py:48-54)."""
-    _need_cuda(probs, labels)
-    probs = probs.contiguous() if probs.dtype == torch.float32 else cast(probs.contiguous(), torch.float32)
-    lab = labels.contiguous()
-    if lab.dtype != torch.uint8:
-        lab = (lab != 0).to(torch.uint8)
+    probs, lab = _scores_and_mask("average_precision", probs, labels)
     N, Cn = probs.shape
     lib = L.load()
     nbytes = lib.dvt_average_precision_workspace_bytes(N, Cn)
@@ -1219,14 +1224,8 @@ def average_precision(probs: Tensor, labels: Tensor):
 def multilabel_report_counts(probs: Tensor, labels: Tensor, threshold: float):
     """``classification_report(labels, probs > threshold)`` as exact counts (dvt_multilabel_report) -> (counts int64 [4, C]:
     TP / FP / FN / support per class, row_sums f64 [3]: the sums over rows of the per-row precision / recall / F1)."""
-    _need_cuda(probs, labels)
-    probs = probs.contiguous() if probs.dtype == torch.float32 else cast(probs.contiguous(), torch.float32)
-    lab = labels.contiguous()
-    if lab.dtype != torch.uint8:
-        lab = (lab != 0).to(torch.uint8)          # dtype plumbing of a label mask
+    probs, lab = _scores_and_mask("multilabel_report_counts", probs, labels)
     N, Cn = probs.shape
-    if tuple(lab.shape) != (N, Cn):
-        raise ValueError(f"multilabel_report_counts: labels {tuple(lab.shape)} != probs {(N, Cn)}")
     lib = L.load()
     ws = workspace(lib.dvt_multilabel_report_workspace_bytes(N), probs.device)
     counts = torch.empty((4, Cn), dtype=torch.int64, device=probs.device)
@@ -2822,14 +2821,8 @@ def probe_bwd_step(d, keep, g_w1: Tensor, g_gamma: Tensor, g_beta: Tensor, g_w2:
 def multilabel_sweep_counts(probs: Tensor, labels: Tensor, thresholds) -> Tuple[Tensor, Tensor]:
     """TP / FP / FN per class of ``probs > t`` for every t of ``thresholds`` in one launch (dvt_multilabel_sweep_counts)
     -> (counts int64 [T, 3, C], support int64 [C])."""
-    _need_cuda(probs, labels)
-    probs = probs.contiguous() if probs.dtype == torch.float32 else cast(probs.contiguous(), torch.float32)
-    lab = labels.contiguous()
-    if lab.dtype != torch.uint8:
-        lab = (lab != 0).to(torch.uint8)          # dtype plumbing of a label mask
+    probs, lab = _scores_and_mask("multilabel_sweep_counts", probs, labels)
     N, Cn = probs.shape
-    if tuple(lab.shape) != (N, Cn):
-        raise ValueError(f"multilabel_sweep_counts: labels {tuple(lab.shape)} != probs {(N, Cn)}")
     th = torch.tensor([float(t) for t in thresholds], dtype=torch.float32).to(probs.device)
     counts = torch.empty((th.numel(), 3, Cn), dtype=torch.int64, device=probs.device)
     support = torch.empty((Cn,), dtype=torch.int64, device=probs.device)
@@ -2839,7 +2832,7 @@ def multilabel_sweep_counts(probs: Tensor, labels: Tensor, thresholds) -> Tuple[
     return counts, support
 
 
-# ------------------------------------------------------------------ rank metrics and counts (csrc/rank_metrics.hip)
+# ------------------------------------------------------------------ rank metrics and counts (csrc/eval_metrics.hip)
 class RankMetrics(NamedTuple):
     """What ``rank_metrics`` returns: device tensors, no host synchronisation.  ``micro`` / ``micro_two_u`` /
     ``micro_positives`` are NaN / -1 / -1 without ``micro=True``; ``samples_sum`` / ``valid_rows`` NaN / -1 without
@@ -2867,19 +2860,6 @@ def rank_metrics_block() -> int:
     if RANK_BLOCK is None:
         RANK_BLOCK = int(L.load().dvt_rank_metrics_block())
     return RANK_BLOCK
-
-
-def _scores_and_mask(name: str, probs: Tensor, labels: Tensor) -> Tuple[Tensor, Tensor]:
-    """The dtype plumbing of ``average_precision``: a 16-bit score is cast to f32 (exact, so ties stay ties), a label mask
-    becomes u8."""
-    _need_cuda(probs, labels)
-    if probs.dim() != 2 or tuple(labels.shape) != tuple(probs.shape):
-        raise ValueError(f"{name}: probs {tuple(probs.shape)} and labels {tuple(labels.shape)} must be the same [N, C]")
-    probs = probs.contiguous() if probs.dtype == torch.float32 else cast(probs.contiguous(), torch.float32)
-    lab = labels.contiguous()
-    if lab.dtype != torch.uint8:
-        lab = (lab != 0).to(torch.uint8)
-    return probs, lab
 
 
 def rank_metrics(probs: Tensor, labels: Tensor, micro: bool = False, samples: bool = False) -> RankMetrics:

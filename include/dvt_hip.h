@@ -624,7 +624,8 @@ int dvt_contrastive_bwd(const float* sim, const float* row_lse, int M, float tem
  * dvt_f1_samples: out[j] = f1_score(labels, probs > thresholds[j], average="samples", zero_division=0);
  * thresholds is a host array of T <= 16 values (callbacks.py:38: 0, 0.1 .. 0.8).
  * dvt_average_precision: average_precision_score(labels, probs, average="samples" / "weighted" / None) ->
- * out_samples[1], out_weighted[1], out_per_class[C] (device f32); C <= 64. */
+ * out_samples[1], out_weighted[1], out_per_class[C] (device f32); C <= 64.  The per-class values are the rank pass of
+ * dvt_rank_metrics (its f64 AP rounded to f32), the weighted one their support-weighted mean. */
 size_t dvt_f1_samples_workspace_bytes(int64_t N, int T);
 int dvt_f1_samples(const float* probs, const unsigned char* labels, int64_t N, int C, const float* thresholds, int T,
                    float* out, void* workspace, dvt_stream_t stream);
@@ -1403,7 +1404,7 @@ int dvt_cam_render(const float* scaled, int64_t N, int Ti, int Hi, int Wi, int T
  * AveragePrecision: `from torchmetrics import AUROC, F1, AveragePrecision` (src/models/frame_transformer.py:8; val_auroc /
  * train_auroc at :114-115, the log lines at :276-343), torchmetrics.F1(num_classes=22) (src/models/basicmlp.py:20), and
  * scikit-learn's confusion_matrix with the MITEval accuracy callback (src/callbacks/callbacks.py:14, :85-98; attached to every
- * MIT run at src/main.py:46-50).  csrc/rank_metrics.hip.  Everything runs asynchronously on `stream` with no host
+ * MIT run at src/main.py:46-50).  csrc/eval_metrics.hip.  Everything runs asynchronously on `stream` with no host
  * synchronisation; integer results are exact and floating-point sums go in a fixed order without atomics, so identical calls
  * give bitwise-equal results.
  *

@@ -1,4 +1,4 @@
-"""numpy restatement of the rank metrics and counts of csrc/rank_metrics.hip (test infrastructure, like tests/lars_ref.py).
+"""numpy restatement of the rank metrics and counts of csrc/eval_metrics.hip (test infrastructure, like tests/lars_ref.py).
 
 A tie group is a maximal run of equal scores of a column sorted descending; element i ends a group when it is the last one
 or s[i+1] != s[i] (-0.0 == +0.0).  With tp the inclusive count of positives, P the positives, Nn = N - P, and per group

@@ -1,4 +1,4 @@
-"""GPU checks of csrc/rank_metrics.hip through ops / metrics: the rank pass (AUROC, AP, averages) at sizes on the edges of
+"""GPU checks of csrc/eval_metrics.hip through ops / metrics: the rank pass (AUROC, AP, averages) at sizes on the edges of
 its block, the confusion-matrix and multilabel counts, and the torchmetrics-named objects, against the numpy restatement
 (tests/rank_metrics_ref.py) and the scikit-learn fixture (tests/golden/rank_metrics.npz); never against scikit-learn itself.
 
@@ -163,6 +163,64 @@ def test_repeated_call_is_bitwise_equal_and_average_precision_is_unchanged(devic
     _, w2, per2 = ops.average_precision(p, l)
     assert torch.equal(per1, per2) and torch.equal(w1, w2)
     assert np.abs(per1.cpu().numpy().astype(np.float64) - b.ap.cpu().numpy()).max() <= 1e-6
+
+
+@pytest.mark.parametrize("N", (1, 2, 257, 2049))
+def test_average_precision_is_the_rank_pass_rounded_to_f32(device, N):
+    """ops.average_precision takes its per-class values from the rank pass: the f64 AP of ops.rank_metrics rounded to f32,
+    bit for bit, and the weighted value formed from those f32 values and the integer supports in class order."""
+    from dvt_amd import ops
+    assert 2049 == _block() + 1
+    for C in CLASSES:
+        for blank in sorted({C // 2, C - 1}) + ([None] if C == 1 else []):     # a class without positives (C = 1: also with)
+            rng = np.random.default_rng([N, C, 8])
+            probs, lab = make_scores(rng, N, C, "q8")[1], make_labels(rng, N, C)
+            if blank is not None:
+                lab[:, blank] = 0
+            p, l = torch.from_numpy(probs).to(device), torch.from_numpy(lab).to(device)
+            _, w1, per1 = (t.clone() for t in ops.average_precision(p, l))
+            _, w2, per2 = ops.average_precision(p, l)
+            assert torch.equal(per1.view(torch.int32), per2.view(torch.int32))
+            assert torch.equal(w1.view(torch.int32), w2.view(torch.int32))
+            r = ops.rank_metrics(p, l)
+            assert torch.equal(per1.view(torch.int32), r.ap.float().view(torch.int32)), (N, C, blank)
+            ap32, pos = per1.cpu().numpy(), r.positives.cpu().numpy()
+            assert np.array_equal(pos, lab.sum(0)) and (blank is None or (pos[blank] == 0 and ap32[blank] == 0.0))
+            num = den = 0.0
+            for c in range(C):                                                  # the kernel's order: class by class, in f64
+                num += float(ap32[c]) * float(pos[c])
+                den += float(pos[c])
+            want = np.float32(num / den) if den > 0 else np.float32(0.0)
+            assert w1.cpu().numpy()[0].tobytes() == want.tobytes(), (N, C, blank, w1, want)
+
+
+@pytest.mark.parametrize("N", (1, 255, 257, 4097))
+def test_report_counts_are_the_sweep_counts_at_one_threshold(device, N):
+    from dvt_amd import ops
+    th = 0.5
+    for C in (1, 19):
+        rng = np.random.default_rng([N, C, 5])
+        probs, lab = rng.random((N, C)).astype(np.float32), make_labels(rng, N, C)
+        probs[::3, 0] = th                                    # equal to the threshold: strict > leaves them negative
+        p, l = torch.from_numpy(probs).to(device), torch.from_numpy(lab).to(device)
+        counts, _ = ops.multilabel_report_counts(p, l, th)
+        sweep, support = ops.multilabel_sweep_counts(p, l, [th])
+        assert counts.dtype == sweep.dtype == support.dtype == torch.int64
+        assert torch.equal(counts[:3], sweep[0]) and torch.equal(counts[3], support)
+        pred, truth = probs > np.float32(th), lab != 0
+        want = np.stack([(pred & truth).sum(0), (pred & ~truth).sum(0), (~pred & truth).sum(0), truth.sum(0)])
+        assert not pred[::3, 0].any() and np.array_equal(counts.cpu().numpy(), want)
+
+
+def test_f1_samples_and_average_precision_refuse_mismatched_shapes(device):
+    from dvt_amd import ops
+    p = torch.zeros((8, 19), dtype=torch.float32, device=device)
+    for bad in (torch.zeros((8, 18), dtype=torch.uint8, device=device), torch.zeros((7, 19), dtype=torch.uint8, device=device),
+                torch.zeros((8 * 19,), dtype=torch.uint8, device=device)):
+        with pytest.raises(ValueError, match="f1_samples"):
+            ops.f1_samples(p, bad, (0.5,))
+        with pytest.raises(ValueError, match="average_precision"):
+            ops.average_precision(p, bad)
 
 
 # ------------------------------------------------------------------ counts

@@ -1,15 +1,15 @@
-"""AUROC + AP in one rank pass (ops.rank_metrics) against the AP-only call it sits next to (ops.average_precision, whose
-entry point this tree leaves as it was), and the counts kernels against their bytes-moved floor, on the MI355X.
+"""The ranked metrics (ops.average_precision, ops.rank_metrics: one descending sort per class and the parallel rank pass
+of csrc/eval_metrics.hip behind both) and the counts kernels against their bytes-moved floor, on the MI355X.
 
     python tools/bench_rank_metrics.py [--rounds 3] [--warmup 5] [--steps 30] [--sizes 653,6047,65536,1048576]
     python tools/bench_rank_metrics.py --one rank --n 65536        # one timing in this process (what the driver spawns)
 
 Rows are [N, 19]: N = 653 and 6047 are the reference's validation and training splits (MMX_Light_dl.py:137-139).  The
-driver runs ONE PROCESS PER TIMING, each under its own time limit, and alternates the yardstick and the new call round by
-round on the same GPU; a timing is hipEvents around one call after a warm-up, the median over the steps, and the driver
-reports the median and the spread (min .. max) of the per-round medians.  One JSON line on stdout.
+driver runs ONE PROCESS PER TIMING, each under its own time limit, and takes the three calls in turn round by round on
+the same GPU; a timing is hipEvents around one call after a warm-up, the median over the steps, and the driver reports
+the median and the spread (min .. max) of the per-round medians.  One JSON line on stdout.
 
-  ap            ops.average_precision: per-row AP, layout, segmented sort, ONE THREAD PER CLASS walking N rows, weighted
+  ap            ops.average_precision: per-row AP and its mean, layout, segmented sort, aggregates, class pass, f32 outputs
   rank          ops.rank_metrics: layout, the same sort, aggregates, class pass, totals (AP + AUROC, macro / weighted)
   rank_all      the same with micro (a second, device-wide sort and pass over N C elements) and samples on
   confusion     ops.confusion_matrix from f32 logits [N, 305] (the MIT label set); floor = logits + targets read once
@@ -17,9 +17,9 @@ reports the median and the spread (min .. max) of the per-round medians.  One JS
   ml_counts     ops.multilabel_counts [N, 19]; floor = probabilities + labels read once
   sklearn       roc_auc_score + average_precision_score(average=None) on the host, where scikit-learn is installed
 
-The phases of a call (layout, sort, aggregates, class pass; the yardstick's ap_class_kernel alone) are kernel times: run
-`--one rank --n N` and `--one ap --n N` under a kernel trace (`rocprofv3 --kernel-trace --stats -- python ...`) in a run of
-its own; tracing slows the host, so the end-to-end numbers come from the plain run."""
+The phases of a call (layout, sort, aggregates, class pass) are kernel times: run `--one rank --n N` under a kernel trace
+(`rocprofv3 --kernel-trace --stats -- python ...`) in a run of its own; tracing slows the host, so the end-to-end numbers
+come from the plain run."""
 from __future__ import annotations
 
 import argparse
@@ -131,11 +131,10 @@ def main():
     res = {"classes": C_ROWS, "rounds": a.rounds, "warmup": a.warmup, "steps": a.steps, "rank": {}}
     for n in (int(s) for s in a.sizes.split(",")):
         per = {k: [] for k in ("ap", "rank", "rank_all")}
-        for _ in range(a.rounds):                      # yardstick and new call alternate, a process each
+        for _ in range(a.rounds):                      # the calls take turns, a process each
             for k in per:
                 per[k].append(_child(k, n, a)["median_us"])
         row = {k: {"median_us": round(_median(v), 2), "min_us": min(v), "max_us": max(v)} for k, v in per.items()}
-        row["rank_over_ap"] = round(row["rank"]["median_us"] / row["ap"]["median_us"], 3)
         res["rank"][str(n)] = row
         print(f"[bench_rank_metrics] N = {n}: {row}", file=sys.stderr, flush=True)
     res["counts"] = {"n": a.counts_n}

@@ -22,7 +22,7 @@ from isa_listing import kernel_listings  # noqa: E402
 
 GENERIC_LIMIT = 12
 ALLOWED_GENERIC = ("patchify_generic",)   # real null checks of optional global pointers in an unrolled loop (any-patch-size fallback)
-ALLOWED = ("rocprim",)          # kernel-name substrings that may keep FLAT accesses (library code: the segmented sort of eval_metrics.hip)
+ALLOWED = ("rocprim",)          # kernel-name substrings that may keep FLAT accesses (library code: the sorts of eval_metrics.hip)
 
 
 def flat_ops(so_path, generic=None):
