@@ -12,7 +12,12 @@ there is no torch arithmetic and no CPU path.
 Build-side additions (keyword-only, defaults keep reference behaviour):
 ``compute_dtype`` -- activation / GEMM dtype (torch.bfloat16 default, torch.float32
 for the fp32 parity mode); ``activation_checkpointing`` -- keep one activation per
-transformer block and recompute the block in backward (BASELINE configs[4]).
+transformer block and recompute the block in backward (BASELINE configs[4]);
+``tubelet_size`` -- pt > 1 replaces the per-frame tokeniser by the ViViT paper's tubelet embedding (a pt x P x P patch
+across pt consecutive frames, csrc/tubelet.hip): the space stack runs on ``num_frames / pt`` temporal tokens.  The
+state-dict keys stay the reference's; ``to_patch_embedding.1.weight`` is ``[dim, pt*P*P*C]`` and ``pos_embedding``
+``[1, num_frames // pt, n + 1, dim]``.  ``ViViT.load_frame_checkpoint`` carries a per-frame checkpoint into such a model
+(``inflate_patch_embedding``).
 """
 from __future__ import annotations
 
@@ -26,15 +31,40 @@ class Patchify(nn.Module):
     """Position 0 of ``to_patch_embedding`` (the reference's einops ``Rearrange``,
     vit.py:90).  Parameter-free; the gather itself is fused into ``F.patch_embed``."""
 
-    def __init__(self, patch_size: int):
+    def __init__(self, patch_size: int, tubelet_size: int = 1):
         super().__init__()
         self.patch_size = patch_size
+        self.tubelet_size = tubelet_size
 
     def forward(self, x):  # only reached when used stand-alone
         from .. import ops
         b, t = x.shape[0], x.shape[1]
-        out = ops.patchify(x, self.patch_size, x.dtype)
-        return out.view(b, t, -1, out.shape[-1])
+        if self.tubelet_size == 1:
+            out = ops.patchify(x, self.patch_size, x.dtype)
+            return out.view(b, t, -1, out.shape[-1])
+        out = ops.tubelet_patchify(x, self.patch_size, self.tubelet_size, x.dtype)
+        return out.view(b, t // self.tubelet_size, -1, out.shape[-1])
+
+
+def inflate_patch_embedding(weight2d, tubelet_size: int, mode: str = "central"):
+    """Per-frame patch-embedding weight [dim, P*P*C] -> tubelet weight [dim, pt*P*P*C] (block k = columns
+    ``k*P*P*C : (k+1)*P*P*C``, the frame k of a tubelet).  ``"central"``: the weight in block ``pt // 2``, zeros elsewhere
+    -- on a clip x the tubelet embedding then equals the per-frame embedding of ``x[:, pt//2::pt]``.  ``"average"``:
+    ``weight / pt`` in every block -- the per-frame embedding of the mean frame of each tubelet.  Host-side, init-time."""
+    if mode not in ("central", "average"):
+        raise ValueError(f"inflate_patch_embedding: mode must be 'central' or 'average', got {mode!r}")
+    if int(tubelet_size) != tubelet_size or tubelet_size < 1:
+        raise ValueError(f"inflate_patch_embedding: tubelet_size must be an integer >= 1, got {tubelet_size!r}")
+    if weight2d.dim() != 2:
+        raise ValueError(f"inflate_patch_embedding: expected a weight [dim, P*P*C], got shape {tuple(weight2d.shape)}")
+    pt = int(tubelet_size)
+    d, pd = weight2d.shape
+    w = weight2d.detach()
+    if mode == "average":
+        return (w / pt).repeat(1, pt)
+    out = torch.zeros((d, pt * pd), dtype=w.dtype, device=w.device)
+    out[:, (pt // 2) * pd:(pt // 2 + 1) * pd] = w
+    return out
 
 
 class GELU(nn.Module):
@@ -204,17 +234,22 @@ class ViViT(nn.Module):
 
     def __init__(self, image_size, patch_size, num_classes, num_frames, dim=192, depth=4, heads=3,
                  pool='cls', in_channels=3, dim_head=64, dropout=0., emb_dropout=0., scale_dim=4, *,
-                 compute_dtype: torch.dtype = torch.bfloat16, activation_checkpointing: bool = False):
+                 compute_dtype: torch.dtype = torch.bfloat16, activation_checkpointing: bool = False,
+                 tubelet_size: int = 1):
         super().__init__()
         assert pool in {'cls', 'mean'}, 'pool type must be either cls (cls token) or mean (mean pooling)'
         assert image_size % patch_size == 0, 'Image dimensions must be divisible by the patch size.'
+        if isinstance(tubelet_size, bool) or not isinstance(tubelet_size, int) or tubelet_size < 1:
+            raise ValueError(f"tubelet_size must be an integer >= 1, got {tubelet_size!r}")
+        if num_frames % tubelet_size != 0:
+            raise ValueError(f"num_frames = {num_frames} is not a multiple of tubelet_size = {tubelet_size}")
         num_patches = (image_size // patch_size) ** 2
-        patch_dim = in_channels * patch_size ** 2
+        patch_dim = tubelet_size * in_channels * patch_size ** 2
         self.to_patch_embedding = nn.Sequential(
-            Patchify(patch_size),
+            Patchify(patch_size, tubelet_size),
             nn.Linear(patch_dim, dim),
         )
-        self.pos_embedding = nn.Parameter(torch.randn(1, num_frames, num_patches + 1, dim))
+        self.pos_embedding = nn.Parameter(torch.randn(1, num_frames // tubelet_size, num_patches + 1, dim))
         self.space_token = nn.Parameter(torch.randn(1, 1, dim))
         self.space_transformer = Transformer(dim, depth, heads, dim_head, dim * scale_dim, dropout)
         self.temporal_token = nn.Parameter(torch.randn(1, 1, dim))
@@ -227,7 +262,8 @@ class ViViT(nn.Module):
         )
         self.patch_size = patch_size
         self.num_patches = num_patches
-        self.num_frames = num_frames
+        self.num_frames = num_frames          # pixel frames of a clip; the stacks see num_frames // tubelet_size of them
+        self.tubelet_size = tubelet_size
         self.emb_dropout_p = emb_dropout
         self.compute_dtype = compute_dtype
         self.zone_f32 = True          # fp32 residual stream in the temporal stack / heads under 16-bit kernels (see forward)
@@ -256,6 +292,47 @@ class ViViT(nn.Module):
         logits = F.linear(F.layernorm(pooled, hn.weight, hn.bias, hn.eps), hl.weight, hl.bias, out_f32=True)
         return F.bce_with_logits(logits, target), logits
 
+    def load_frame_checkpoint(self, state_dict, mode: str = "central"):
+        """Load the state dict of a per-frame ``ViViT`` (``tubelet_size=1``) of the same geometry and ``num_frames`` into
+        this tubelet model: ``to_patch_embedding.1.weight`` is inflated (``inflate_patch_embedding``), ``pos_embedding``
+        is reduced over time -- rows ``pt//2::pt`` for ``"central"``, the mean over each group of pt rows for
+        ``"average"`` -- and every other tensor is copied strictly.  ValueError, naming the key, on any key or shape
+        mismatch; nothing is written before every tensor has been checked."""
+        if mode not in ("central", "average"):
+            raise ValueError(f"load_frame_checkpoint: mode must be 'central' or 'average', got {mode!r}")
+        pt = self.tubelet_size
+        own = self.state_dict()
+        for k in own:
+            if k not in state_dict:
+                raise ValueError(f"load_frame_checkpoint: key {k!r} is missing from the checkpoint")
+        for k in state_dict:
+            if k not in own:
+                raise ValueError(f"load_frame_checkpoint: unexpected key {k!r} in the checkpoint")
+        new = {}
+        for k, dst in own.items():
+            src = state_dict[k].detach()
+            if k == "to_patch_embedding.1.weight":
+                if src.dim() != 2 or (src.shape[0], src.shape[1] * pt) != tuple(dst.shape):
+                    raise ValueError(f"load_frame_checkpoint: {k!r} has shape {tuple(src.shape)}; a per-frame weight "
+                                     f"[{dst.shape[0]}, {dst.shape[1] // pt}] is expected")
+                src = inflate_patch_embedding(src, pt, mode)
+            elif k == "pos_embedding":
+                want = (1, self.num_frames) + tuple(dst.shape[2:])
+                if tuple(src.shape) != want:
+                    raise ValueError(f"load_frame_checkpoint: {k!r} has shape {tuple(src.shape)}; the per-frame table "
+                                     f"{want} is expected")
+                if mode == "central":
+                    src = src[:, pt // 2::pt]
+                else:
+                    src = src.reshape(1, self.num_frames // pt, pt, *src.shape[2:]).mean(2)
+            elif tuple(src.shape) != tuple(dst.shape):
+                raise ValueError(f"load_frame_checkpoint: {k!r} has shape {tuple(src.shape)}, the model's is "
+                                 f"{tuple(dst.shape)}")
+            new[k] = src
+        with torch.no_grad():
+            for k, dst in own.items():
+                dst.copy_(new[k])
+
     def _trunk(self, x):
         """-> (pooled [b, dim], the LayerNorm still to be applied to it or None)."""
         if x.dim() != 5:
@@ -264,11 +341,12 @@ class ViViT(nn.Module):
         if t != self.num_frames:
             raise ValueError(f"clip has {t} frames but pos_embedding was built for {self.num_frames} "
                              "(vit.py:94,115 broadcast)")
+        t //= self.tubelet_size                 # temporal tokens: everything below sees a clip of t tubelets
         T = self.compute_dtype
         F.lp_clear()            # 16-bit gradient copies a previous step's backward left untaken (functional._lp_hand)
         n = (x.shape[3] // self.patch_size) * (x.shape[4] // self.patch_size)
         pe = self.to_patch_embedding[1]
-        emb = F.patch_embed(x, pe.weight, pe.bias, self.patch_size, T)              # vit.py:110
+        emb = F.patch_embed(x, pe.weight, pe.bias, self.patch_size, T, tubelet=self.tubelet_size)   # vit.py:110
         tok = F.tokens_assemble(emb, self.space_token, self.pos_embedding, b * t, t, n)   # :113-115
         tok = F.dropout(tok, self.emb_dropout_p, self.training)                            # :116
         st, tt = self.space_transformer, self.temporal_transformer

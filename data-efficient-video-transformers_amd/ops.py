@@ -239,6 +239,50 @@ def patchify_bwd(dout: Tensor, shape, patch: int, dx_dtype: torch.dtype) -> Tens
     return dx
 
 
+def _tubelet_geometry(shape, patch: int, tubelet: int, what: str):
+    """(frames, C, H, W) of a clip shape [..., t, C, H, W] whose t frames split into whole tubelets."""
+    if len(shape) < 4:
+        raise ValueError(f"{what}: expected a clip [..., t, C, H, W], got shape {tuple(shape)}")
+    if int(tubelet) != tubelet or tubelet < 1:
+        raise ValueError(f"{what}: tubelet must be an integer >= 1, got {tubelet!r}")
+    t, Cc, H, W = (int(s) for s in shape[-4:])
+    if t % tubelet:
+        raise ValueError(f"{what}: {t} frames per clip are not whole tubelets of {tubelet}")
+    frames = 1
+    for s in shape[:-3]:
+        frames *= int(s)
+    return frames, Cc, H, W
+
+
+def tubelet_patchify(x: Tensor, patch: int, tubelet: int, out_dtype: torch.dtype) -> Tensor:
+    """[..., t, C, H, W] -> [(frames / tubelet) * n, tubelet*P*P*C]: 'b (tau k) c (h p1) (w p2) -> (b tau h w) (k p1 p2 c)'
+    (csrc/tubelet.hip; tubelet == 1 is ``patchify``)."""
+    _need_cuda(x)
+    frames, Cc, H, W = _tubelet_geometry(x.shape, patch, tubelet, "tubelet_patchify")
+    x = x.contiguous()
+    n = (H // patch) * (W // patch)
+    out = torch.empty((frames // tubelet * n, tubelet * patch * patch * Cc), dtype=out_dtype, device=x.device)
+    with _timed(("hbm", "tubelet_patchify", x.numel()), x.numel() * x.element_size() + out.numel() * out.element_size()):
+        L.check(L.load().dvt_tubelet_patchify(x.data_ptr(), dt(x), out.data_ptr(), _DT[out_dtype], frames, Cc, H, W, patch,
+                                              tubelet, _stream()), "dvt_tubelet_patchify")
+    return out
+
+
+def tubelet_patchify_bwd(dout: Tensor, shape, patch: int, tubelet: int, dx_dtype: torch.dtype) -> Tensor:
+    """The adjoint (inverse) of ``tubelet_patchify``: dout [(frames / tubelet) * n, tubelet*P*P*C] -> dx of ``shape``."""
+    _need_cuda(dout)
+    frames, Cc, H, W = _tubelet_geometry(shape, patch, tubelet, "tubelet_patchify_bwd")
+    dout = dout.contiguous()
+    if dout.numel() != frames * Cc * H * W:
+        raise ValueError(f"tubelet_patchify_bwd: dout {tuple(dout.shape)} does not hold a clip of shape {tuple(shape)}")
+    dx = torch.empty(tuple(shape), dtype=dx_dtype, device=dout.device)
+    with _timed(("hbm", "tubelet_patchify_bwd", dout.numel()),
+                dout.numel() * dout.element_size() + dx.numel() * dx.element_size()):
+        L.check(L.load().dvt_tubelet_patchify_bwd(dout.data_ptr(), dt(dout), dx.data_ptr(), _DT[dx_dtype], frames, Cc, H, W,
+                                                  patch, tubelet, _stream()), "dvt_tubelet_patchify_bwd")
+    return dx
+
+
 def tokens_assemble_fwd(emb: Tensor, cls: Tensor, pos: Tensor, S: int, T: int, n: int) -> Tensor:
     """emb [S*n, d]; cls [d] f32; pos [T, rows>=n+1, d] f32 -> [S, n+1, d]."""
     _need_cuda(emb, cls, pos)

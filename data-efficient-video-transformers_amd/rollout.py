@@ -18,7 +18,9 @@ layers run for the CLS query alone exactly as in any eval forward), then per sta
 maps) and ``ops.cam_render``.  No host synchronisation, no torch arithmetic, no N x N tensor.
 
 ViViT: ``space[b, f]`` is the h x w map of frame f's patches under the space stack, ``time[b, f]`` the weight of frame f
-under the temporal stack, ``video = time * space``.  FrameTransformer ("vid" mode): ``ro.maps(vid)`` and ``ro(vid)`` return
+under the temporal stack, ``video = time * space``.  On a tubelet model (``ViViT(..., tubelet_size=pt)``) "frame" reads
+"tubelet": the maps are ``[b, t / pt, h, w]`` over the temporal tokens, and the rendered volume is still the clip's own
+``(t, H, W)`` (the trilinear render upsamples time as it does space).  FrameTransformer ("vid" mode): ``ro.maps(vid)`` and ``ro(vid)`` return
 ``chunks [B, 13]``, the CLS row over the 4-layer encoder without the CLS entry (14 tokens have nothing to upsample).
 
 Deviations: the heads are fused by their mean only (no max / min fusion), there is no ``discard_ratio``, and the rollout is
@@ -107,7 +109,8 @@ class AttentionRollout:
         return clip.shape[3] // p, clip.shape[4] // p
 
     def maps(self, x: Tensor):
-        """ViViT: clip [b, t, c, H, W] -> raw (space [b, t, h, w], time [b, t], video [b, t, h, w]), f32.
+        """ViViT: clip [b, t, c, H, W] -> raw (space [b, t, h, w], time [b, t], video [b, t, h, w]), f32 (t / tubelet_size
+        temporal tokens in place of t on a tubelet model).
         FrameTransformer: vid [B, 13, ...] -> chunks [B, 13]."""
         if self.kind == "frame":
             layers = self._forward(None, x)
@@ -129,7 +132,7 @@ class AttentionRollout:
         b, t = r_time.shape[0], r_time.shape[1] - 1
         h, w = self._grid(x)
         raw, scaled = ops.rollout_video(r_space, r_time, want_raw=not scale)
-        size = (t, x.shape[3], x.shape[4]) if size is None else tuple(size)
+        size = (x.shape[1], x.shape[3], x.shape[4]) if size is None else tuple(size)
         return ops.cam_render((scaled if scale else raw).view(b, t, h, w), size)[0]
 
     forward = __call__

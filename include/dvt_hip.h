@@ -128,6 +128,22 @@ int dvt_patchify(const void* x, int x_dtype, void* out, int out_dtype, int64_t f
  * src/models/frame_transformer.py:105,195). */
 int dvt_patchify_bwd(const void* dout, int dout_dtype, void* dx, int dx_dtype, int64_t frames,
                      int C, int H, int W, int P, dvt_stream_t stream);
+/* Tubelet embedding gather: the 3-D counterpart of the per-frame Rearrange + Linear tokeniser of
+ * src/models/vit.py:89-92 (the ViViT paper's own embedding; the reference builds the per-frame one only).
+ * 'b (tau k) c (h p1) (w p2) -> (b tau h w) (k p1 p2 c)':  x: [frames, C, H, W] in x_dtype, frames = b * t flattened,
+ * every pt consecutive frames form a tubelet (the caller guarantees t % pt == 0); out: [(frames / pt) * (H/P) * (W/P),
+ * pt*P*P*C] in out_dtype,
+ *   out[((bi*(t/pt) + tau)*nh + ph)*nw + pw, ((k*P + p1)*P + p2)*C + c] = x[bi, tau*pt + k, c, ph*P + p1, pw*P + p2]
+ * with nh = H/P, nw = W/P: k slowest, c fastest -- a row is the pt per-frame patch vectors of dvt_patchify's order,
+ * concatenated; pt == 1 is dvt_patchify bit for bit.  DVT_ERR_BAD_ARG for a null pointer, pt < 1, frames % pt != 0,
+ * H % P != 0 or W % P != 0, before any HIP call. */
+int dvt_tubelet_patchify(const void* x, int x_dtype, void* out, int out_dtype, int64_t frames, int C, int H, int W, int P,
+                         int pt, dvt_stream_t stream);
+/* Adjoint (= inverse: the gather is a permutation) of dvt_tubelet_patchify, the scatter back to [frames, C, H, W]:
+ *   dx[bi, tau*pt + k, c, ph*P + p1, pw*P + p2] = dout[((bi*(t/pt) + tau)*nh + ph)*nw + pw, ((k*P + p1)*P + p2)*C + c]
+ * (src/models/vit.py:89-92 in backward, when the clip itself carries a gradient).  Same argument checks. */
+int dvt_tubelet_patchify_bwd(const void* dout, int dout_dtype, void* dx, int dx_dtype, int64_t frames, int C, int H, int W,
+                             int P, int pt, dvt_stream_t stream);
 
 /* ---------------------------------------------------------------- token assembly
  * ViViT.forward token plumbing, src/models/vit.py:113-115:
