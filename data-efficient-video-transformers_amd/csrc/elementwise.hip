@@ -1,7 +1,8 @@
 // elementwise.hip -- HBM-bound data-movement kernels of the clip path:
-// casts, residual add, patchify gather, token assembly (CLS + positional add),
-// CLS row gather, losses, dropout.  All are streaming kernels: 16-byte accesses
-// per lane, grid-stride over at most 256 CUs x 8 blocks.
+// casts, residual add, token assembly (CLS + positional add), CLS row gather,
+// losses, dropout.  All are streaming kernels: 16-byte accesses per lane,
+// grid-stride over at most 256 CUs x 8 blocks.  (The patch gather is a unit of
+// its own.)
 #include "common.h"
 
 namespace {
@@ -137,156 +138,6 @@ __global__ void act_kernel(const T* __restrict__ dy, const T* __restrict__ x, T*
     } else if (FWD) r = act == 1 ? gelu_erf_f(v) : fmaxf(v, 0.f);
     else r = to_f32<T>(dy[i]) * (act == 1 ? gelu_erf_grad_f(v) : (v > 0.f ? 1.f : 0.f));
     out[i] = from_f32<T>(r);
-  }
-}
-
-// ------------------------------------------------------------------ patchify
-// out[(f*nh + ph)*nw + pw, (p1*P + p2)*C + c] = x[f, c, ph*P + p1, pw*P + p2]
-// LDS operations of one wave complete in order; this only keeps the compiler from moving them across the point
-__device__ __forceinline__ void wave_lds_fence_ew() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// Work item = one patch row (frame, ph, p1, pw): C runs of P contiguous pixels in,
-// one run of P*C contiguous patch-vector elements out.  pw is the fastest index so
-// a wave reads 64 adjacent pixel runs (a contiguous span of the image row per channel).
-template <int P, int C, typename S, typename D, bool FWD>
-__global__ void patchify_vec_kernel(const S* __restrict__ x, D* __restrict__ out, S* __restrict__ dx,
-                                    const D* __restrict__ dout, int64_t frames, int H, int W) {
-  const int nh = H / P, nw = W / P;
-  const int64_t items = frames * nh * P * nw;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  constexpr int64_t pd = (int64_t)P * P * C;
-  for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
-    const int pw = (int)(it % nw);
-    int64_t r = it / nw;
-    const int p1 = (int)(r % P);
-    r /= P;
-    const int ph = (int)(r % nh);
-    const int64_t f = r / nh;
-    const int64_t orow = (f * nh + ph) * nw + pw;
-    const int64_t ooff = orow * pd + (int64_t)p1 * P * C;
-    const int64_t xoff = ((f * C) * H + (int64_t)ph * P + p1) * W + (int64_t)pw * P;
-    float pix[C][P];
-    float vec[P * C];
-    if (FWD) {
-#pragma unroll
-      for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int q = 0; q < P / 8; ++q) {
-          float t[8];
-          load8<S>(x + xoff + (int64_t)c * H * W + q * 8, t);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) pix[c][q * 8 + k] = t[k];
-        }
-#pragma unroll
-      for (int p2 = 0; p2 < P; ++p2)
-#pragma unroll
-        for (int c = 0; c < C; ++c) vec[p2 * C + c] = pix[c][p2];
-#pragma unroll
-      for (int q = 0; q < P * C / 8; ++q) {
-        float t[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t[k] = vec[q * 8 + k];
-        store8<D>(out + ooff + q * 8, t);
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < P * C / 8; ++q) {
-        float t[8];
-        load8<D>(dout + ooff + q * 8, t);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) vec[q * 8 + k] = t[k];
-      }
-#pragma unroll
-      for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int q = 0; q < P / 8; ++q) {
-          float t[8];
-#pragma unroll
-          for (int k = 0; k < 8; ++k) t[k] = vec[(q * 8 + k) * C + c];
-          store8<S>(dx + xoff + (int64_t)c * H * W + q * 8, t);
-        }
-    }
-  }
-}
-
-// Forward, 16 x 16 patches of 3 channels, 16-bit patch vectors (the metric shape): lane = (patch & 3) * 16 + p1, so a wave
-// owns FOUR consecutive patch vectors = 6 KiB of contiguous output.  The lane's 96 output bytes (one patch row: 16 pixels
-// x 3 channels) go through a wave-private LDS patch and leave as six fully contiguous 1-KiB store instructions; the
-// per-lane form above stores 16-byte pieces at a 1,536-byte stride (one 64-byte segment per piece: 3.3 TB/s).
-template <typename S, typename D>
-__global__ __launch_bounds__(256) void patchify16_fwd_kernel(const S* __restrict__ x, D* __restrict__ out, int64_t npatches,
-                                                             int H, int W, int nh, int nw) {
-  constexpr int P = 16, C = 3, ROWB = P * C * 2;              // 96 bytes per patch row
-  __shared__ __attribute__((aligned(16))) char lds[4][64 * ROWB];
-  typedef D v8 __attribute__((ext_vector_type(8)));
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t ngroups = (npatches + 3) >> 2, nwaves = (int64_t)gridDim.x * 4;
-  char* mine = lds[wid];
-  for (int64_t g = (int64_t)blockIdx.x * 4 + wid; g < ngroups; g += nwaves) {
-    const int64_t patch = min(g * 4 + (lane >> 4), npatches - 1);
-    const int p1 = lane & 15;
-    const int pw = (int)(patch % nw);
-    const int64_t r = patch / nw;
-    const int ph = (int)(r % nh);
-    const int64_t f = r / nh;
-    const int64_t xoff = ((f * C) * H + (int64_t)ph * P + p1) * W + (int64_t)pw * P;
-    float pix[C][P];
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-#pragma unroll
-      for (int q = 0; q < P / 8; ++q) {
-        float t[8];
-        load8<S>(x + xoff + (int64_t)c * H * W + q * 8, t);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) pix[c][q * 8 + k] = t[k];
-      }
-#pragma unroll
-    for (int q = 0; q < P * C / 8; ++q) {
-      v8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int e = q * 8 + k;                                // e = p2 * C + c
-        o[k] = (D)pix[e % C][e / C];
-      }
-      *reinterpret_cast<v8*>(mine + lane * ROWB + q * 16) = o;
-    }
-    wave_lds_fence_ew();
-    char* dst = reinterpret_cast<char*>(out) + g * 4 * (int64_t)(P * ROWB);
-    const int64_t lim = (npatches - g * 4) * (int64_t)(P * ROWB);  // bytes of this group that exist
-#pragma unroll
-    for (int q = 0; q < P * C / 8; ++q) {
-      const int off = (q * 64 + lane) * 16;
-      const v8 o = *reinterpret_cast<const v8*>(mine + off);
-      if (off < lim) *reinterpret_cast<v8*>(dst + off) = o;
-    }
-    wave_lds_fence_ew();
-  }
-}
-
-// Any P, C, alignment: scalar accesses.
-template <typename S, typename D, bool FWD>
-__global__ void patchify_generic_kernel(const S* __restrict__ x, D* __restrict__ out,
-                                        S* __restrict__ dx, const D* __restrict__ dout,
-                                        int64_t frames, int C, int H, int W, int P) {
-  const int nh = H / P, nw = W / P;
-  const int64_t pd = (int64_t)P * P * C;
-  const int64_t total = frames * nh * nw * pd;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t e = i % pd;
-    const int64_t orow = i / pd;
-    const int c = (int)(e % C);
-    const int p2 = (int)((e / C) % P);
-    const int p1 = (int)(e / ((int64_t)C * P));
-    const int pw = (int)(orow % nw);
-    const int ph = (int)((orow / nw) % nh);
-    const int64_t f = orow / ((int64_t)nw * nh);
-    const int64_t xi = ((f * C + c) * H + (int64_t)ph * P + p1) * W + (int64_t)pw * P + p2;
-    if (FWD) out[i] = from_f32<D>(to_f32<S>(x[xi]));
-    else dx[xi] = from_f32<S>(to_f32<D>(dout[i]));
   }
 }
 
@@ -640,67 +491,6 @@ __global__ void dropout_fused_kernel(const T* __restrict__ x, const T* __restric
 }
 
 __global__ void rng_advance_kernel(uint64_t* state, uint64_t delta) { state[1] += delta; }
-
-template <typename S, typename D, bool FWD>
-int patchify_dispatch(const void* x, void* out, void* dx, const void* dout, int64_t frames, int C,
-                      int H, int W, int P, hipStream_t st, const char* name) {
-  const int nh = H / P, nw = W / P;
-  const int64_t items = frames * nh * P * nw;
-  const void* pix = FWD ? x : (const void*)dx;
-  const void* vecp = FWD ? (const void*)out : dout;
-  const bool vec_ok = (W % 8 == 0) && (P % 8 == 0) && ((P * C) % 8 == 0) && dvt_aligned16(pix) &&
-                      dvt_aligned16(vecp) && ((int64_t)H * W % 8 == 0);
-  if constexpr (FWD && sizeof(D) == 2) {
-    if (vec_ok && P == 16 && C == 3) {
-      const int64_t npatches = frames * nh * nw;
-      int64_t blocks = dvt_cdiv(dvt_cdiv(npatches, 4), 4);
-      const int64_t cap = (int64_t)dvt_num_cus() * 16;
-      if (blocks > cap) blocks = cap;
-      hipLaunchKernelGGL((patchify16_fwd_kernel<S, D>), dim3((unsigned)blocks), dim3(256), 0, st, (const S*)x, (D*)out,
-                         npatches, H, W, nh, nw);
-      DVT_LAUNCH_CHECK(name);
-      return DVT_OK;
-    }
-  }
-  if (vec_ok && P == 16 && C == 3) {
-    hipLaunchKernelGGL((patchify_vec_kernel<16, 3, S, D, FWD>), dim3(grid_for(items)), dim3(kBlock),
-                       0, st, (const S*)x, (D*)out, (S*)dx, (const D*)dout, frames, H, W);
-  } else if (vec_ok && P == 8 && C == 3) {
-    hipLaunchKernelGGL((patchify_vec_kernel<8, 3, S, D, FWD>), dim3(grid_for(items)), dim3(kBlock),
-                       0, st, (const S*)x, (D*)out, (S*)dx, (const D*)dout, frames, H, W);
-  } else {
-    const int64_t total = frames * nh * nw * (int64_t)P * P * C;
-    hipLaunchKernelGGL((patchify_generic_kernel<S, D, FWD>), dim3(grid_for(total)), dim3(kBlock), 0,
-                       st, (const S*)x, (D*)out, (S*)dx, (const D*)dout, frames, C, H, W, P);
-  }
-  DVT_LAUNCH_CHECK(name);
-  return DVT_OK;
-}
-
-template <bool FWD>
-int patchify_entry(const void* pix, int pix_dtype, const void* vec, int vec_dtype, int64_t frames,
-                   int C, int H, int W, int P, dvt_stream_t stream, const char* name) {
-  DVT_REQUIRE(pix && vec, "%s: null pointer", name);
-  DVT_REQUIRE(frames >= 0 && C > 0 && H > 0 && W > 0 && P > 0, "%s: bad sizes", name);
-  DVT_REQUIRE(H % P == 0 && W % P == 0, "%s: image %dx%d not divisible by patch %d", name, H, W, P);
-  if (frames == 0) return DVT_OK;
-  hipStream_t st = (hipStream_t)stream;
-  // pixel tensor: x (fwd, const) / dx (bwd, written); vector tensor: out (fwd) / dout (bwd)
-#define DVT_PATCH_CASE(PD, S, VD, D)                                                            \
-  if (pix_dtype == PD && vec_dtype == VD)                                                       \
-    return patchify_dispatch<S, D, FWD>(FWD ? pix : nullptr, FWD ? (void*)vec : nullptr,        \
-                                        FWD ? nullptr : (void*)pix, FWD ? nullptr : vec, frames, \
-                                        C, H, W, P, st, name);
-  DVT_PATCH_CASE(DVT_F32, float, DVT_F32, float)
-  DVT_PATCH_CASE(DVT_F32, float, DVT_BF16, bf16)
-  DVT_PATCH_CASE(DVT_F32, float, DVT_F16, f16)
-  DVT_PATCH_CASE(DVT_BF16, bf16, DVT_BF16, bf16)
-  DVT_PATCH_CASE(DVT_F16, f16, DVT_F16, f16)
-  DVT_PATCH_CASE(DVT_BF16, bf16, DVT_F32, float)
-  DVT_PATCH_CASE(DVT_F16, f16, DVT_F32, float)
-#undef DVT_PATCH_CASE
-  DVT_UNSUPPORTED("%s: dtype pair (%d, %d) not supported", name, pix_dtype, vec_dtype);
-}
 }  // namespace
 
 extern "C" {
@@ -834,17 +624,6 @@ int dvt_axpby_f32(const void* src, int src_dtype, float alpha, float* dst, float
                                         (const T*)src, alpha, dst, beta, n));
   DVT_LAUNCH_CHECK("dvt_axpby_f32");
   return DVT_OK;
-}
-
-int dvt_patchify(const void* x, int x_dtype, void* out, int out_dtype, int64_t frames, int C, int H,
-                 int W, int P, dvt_stream_t stream) {
-  return patchify_entry<true>(x, x_dtype, out, out_dtype, frames, C, H, W, P, stream, "dvt_patchify");
-}
-
-int dvt_patchify_bwd(const void* dout, int dout_dtype, void* dx, int dx_dtype, int64_t frames, int C,
-                     int H, int W, int P, dvt_stream_t stream) {
-  return patchify_entry<false>(dx, dx_dtype, dout, dout_dtype, frames, C, H, W, P, stream,
-                               "dvt_patchify_bwd");
 }
 
 int dvt_tokens_assemble_fwd(const void* emb, const float* cls, const float* pos, void* out,

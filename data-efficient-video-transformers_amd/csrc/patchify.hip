@@ -1,32 +1,38 @@
-// tubelet.hip -- tubelet embedding gather (the ViViT paper's 3-D patches) and its adjoint.
+// patchify.hip -- the patch gather of the tokenisers and its adjoint: the one place that knows the index map.
 //
 // The reference tokenises one frame at a time: 'b t c (h p1) (w p2) -> b t (h w) (p1 p2 c)' + Linear
-// (src/models/vit.py:89-92).  A tubelet is a pt x P x P patch across pt consecutive frames.  For x [frames, C, H, W],
-// frames = b t, t % pt == 0, nh = H / P, nw = W / P and f = tau' pt + k (tau' = bi (t / pt) + tau):
+// (src/models/vit.py:89-92).  A tubelet (the ViViT paper's 3-D patch) is a pt x P x P patch across pt consecutive frames.
+// For x [frames, C, H, W], frames = b t, t % pt == 0, nh = H / P, nw = W / P and f = tau' pt + k (tau' = bi (t / pt) + tau):
 //     out[(tau' nh + ph) nw + pw, ((k P + p1) P + p2) C + c] = x[tau' pt + k, c, ph P + p1, pw P + p2]
 // i.e. 'b (tau k) c (h p1) (w p2) -> (b tau h w) (k p1 p2 c)': k slowest, c fastest, so an output row is the pt per-frame
-// patch vectors of the reference order, concatenated, and pt == 1 is dvt_patchify bit for bit.  The operation is a
-// permutation: the adjoint is the inverse (the same index map with source and destination exchanged).
+// patch vectors of the reference order, concatenated.  The per-frame gather is pt == 1 (k = 0, tau' = f): dvt_patchify and
+// dvt_patchify_bwd are the tubelet entry at pt = 1, the same kernels and launches.  The operation is a permutation: the
+// adjoint is the inverse (the same index map with source and destination exchanged).
 //
-//   tubelet_p16_fwd_kernel   forward, P = 16, C = 3, 16-bit patch vectors (the metric shape).
-//       Lane mapping: the work list is the PER-FRAME patch list (frame f, ph, pw), exactly patchify16_fwd_kernel's;
-//       lane = (patch & 3) * 16 + p1, a wave owns four consecutive patches of (normally) one frame.  Only the destination
-//       moves: the patch vector of frame tau' pt + k lands at byte k * 1536 of the pt * 1536-byte row (tau', ph, pw), so
-//       the wave's four vectors are four 1.5 KiB runs at a pt * 1536-byte stride.
+//   patchify_p16_fwd_kernel   forward, P = 16, C = 3, 16-bit patch vectors (the metric shape).
+//       Lane mapping: the work list is the per-frame patch list (frame f, ph, pw) at every pt;
+//       lane = (patch & 3) * 16 + p1, a wave owns four consecutive patches of (normally) one frame.  The lane's 96 output
+//       bytes (one patch row: 16 pixels x 3 channels) go through a wave-private LDS patch and leave as six 1-KiB store
+//       instructions; the per-lane form below stores 16-byte pieces at a 1,536-byte stride (one 64-byte segment per
+//       piece: 3.3 TB/s).  pt moves only the destination: the patch vector of frame tau' pt + k lands at byte k * 1536 of
+//       the pt * 1536-byte row (tau', ph, pw), so the wave's four vectors are four 1.5 KiB runs at a pt * 1536-byte stride
+//       (at pt = 1: 6 KiB of contiguous output).
 //       Why: (read side) the four patches are neighbours in pw, so per channel and image row the wave reads one
-//       contiguous span of 64 pixels -- the parent's read pattern unchanged.  Giving a wave the pt vectors of ONE output
-//       row instead (6 KiB contiguous out at pt = 4) would read 16-pixel spans from pt different frames: 32 bytes of a
-//       64-byte segment each in 16 bits.  (write side) 1536 = 24 * 64, the rows start 16-byte aligned at multiples of
+//       contiguous span of 64 pixels at every pt.  Giving a wave the pt vectors of ONE output row instead (6 KiB
+//       contiguous out at pt = 4) would read 16-pixel spans from pt different frames: 32 bytes of a 64-byte segment each
+//       in 16 bits.  (write side) 1536 = 24 * 64, the rows start 16-byte aligned at multiples of
 //       1536: every run is whole 64-byte segments.  The six 1-KiB store instructions of the wave cover the runs as
 //       1024 | 512 + 512 | 1024 | 1024 | 512 + 512 | 1024 bytes, so a store instruction writes one or two contiguous pieces
 //       of at least 512 bytes.  The four run addresses are wave-uniform values read from lanes 0, 16, 32, 48.
 //       A wave usually lives for ONE group (12,544 groups on 3,136 workgroups at the metric clip), so its set-up is on the
-//       critical path: the patch / frame / tubelet indices are 32-bit (fewer than 2^31 patches; more go to the vector
-//       form), the tubelet split f / pt is computed behind the issued loads, and a whole group issues its six LDS reads
-//       together and stores without a branch.
-//   tubelet_vec_kernel       P in {8, 16}, C = 3, any dtype pair, both directions: a lane moves one patch row
+//       critical path: the patch / frame / tubelet indices are 32-bit, the tubelet split f / pt is computed behind the
+//       issued loads, and a whole group issues its six LDS reads together and stores without a branch.  pt is a run-time
+//       value: at pt = 1 this kernel measured 26.26 us against 26.34 us for the per-frame kernel it replaced, whose
+//       destination was g * 4 * 1536 + off in 64-bit arithmetic (profiles/patch_gather.md).
+//       Fewer than 2^31 patches; more go to the vector form (2^31 patch vectors are 3.3 TB, more than the device holds).
+//   patchify_vec_kernel       P in {8, 16}, C = 3, any dtype pair, both directions: a lane moves one patch row
 //       (C runs of P pixels <-> P C contiguous vector elements) with 16-byte accesses; pw is the fastest index.
-//   tubelet_scalar_kernel    any P, C and alignment, both directions, one element per lane and step.
+//   patchify_scalar_kernel    any P, C and alignment, both directions, one element per lane and step.
 // The direction is a template parameter and a kernel takes exactly one pixel and one vector pointer: no pointer is
 // selected at run time.  Grid-stride loops, 64-bit offsets.
 #include "common.h"
@@ -37,7 +43,7 @@ namespace {
 
 constexpr int kBlock = 256;
 
-inline int tubelet_grid(int64_t work_items) {
+inline int patchify_grid(int64_t work_items) {
   int64_t blocks = dvt_cdiv(work_items, kBlock);
   const int64_t cap = (int64_t)dvt_num_cus() * 8;
   if (blocks > cap) blocks = cap;
@@ -49,7 +55,7 @@ inline int tubelet_grid(int64_t work_items) {
 template <bool READS, typename T> using ptr_t = typename std::conditional<READS, const T*, T*>::type;
 
 // LDS operations of one wave complete in order; this only keeps the compiler from moving them across the point
-__device__ __forceinline__ void wave_lds_fence_tb() {
+__device__ __forceinline__ void wave_lds_fence() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
 }
@@ -63,8 +69,8 @@ __device__ __forceinline__ int64_t value_of_lane(int64_t v) {
 }
 
 template <typename S, typename D>
-__global__ __launch_bounds__(256) void tubelet_p16_fwd_kernel(const S* __restrict__ x, D* __restrict__ out, unsigned npatches,
-                                                              int H, int W, unsigned nw, unsigned npf, unsigned pt) {
+__global__ __launch_bounds__(256) void patchify_p16_fwd_kernel(const S* __restrict__ x, D* __restrict__ out, unsigned npatches,
+                                                               int H, int W, unsigned nw, unsigned npf, unsigned pt) {
   constexpr int P = 16, C = 3, ROWB = P * C * 2;              // 96 bytes per patch row
   constexpr int VECB = P * ROWB;                              // 1536 bytes per patch vector
   static_assert(sizeof(D) == 2, "16-bit patch vectors");
@@ -107,7 +113,7 @@ __global__ __launch_bounds__(256) void tubelet_p16_fwd_kernel(const S* __restric
     const int64_t vbase = (((int64_t)tau * npf + sp) * pt + k) * (int64_t)VECB;
     const int64_t b0 = value_of_lane<0>(vbase), b1 = value_of_lane<16>(vbase), b2 = value_of_lane<32>(vbase),
                   b3 = value_of_lane<48>(vbase);
-    wave_lds_fence_tb();
+    wave_lds_fence();
     const unsigned have = npatches - g * 4;                    // patch vectors of this group that exist (>= 1)
     v8 o[P * C / 8];
     int64_t dst[P * C / 8];
@@ -128,15 +134,15 @@ __global__ __launch_bounds__(256) void tubelet_p16_fwd_kernel(const S* __restric
       for (int q = 0; q < P * C / 8; ++q)
         if ((unsigned)((q * 64 + lane) * 16 / VECB) < have) *reinterpret_cast<v8*>(reinterpret_cast<char*>(out) + dst[q]) = o[q];
     }
-    wave_lds_fence_tb();
+    wave_lds_fence();
   }
 }
 
 // Work item = one patch row (frame, ph, p1, pw): C runs of P contiguous pixels on the pixel side, one run of P*C
 // contiguous elements on the vector side.  pw is the fastest index so a wave touches 64 adjacent pixel runs.
 template <int P, int C, typename S, typename D, bool FWD>
-__global__ void tubelet_vec_kernel(ptr_t<FWD, S> __restrict__ pixp, ptr_t<!FWD, D> __restrict__ vecp, int64_t frames, int H,
-                                   int W, int pt) {
+__global__ void patchify_vec_kernel(ptr_t<FWD, S> __restrict__ pixp, ptr_t<!FWD, D> __restrict__ vecp, int64_t frames, int H,
+                                    int W, int pt) {
   const int nh = H / P, nw = W / P;
   const int64_t items = frames * nh * P * nw;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -200,8 +206,8 @@ __global__ void tubelet_vec_kernel(ptr_t<FWD, S> __restrict__ pixp, ptr_t<!FWD, 
 // Any P, C, alignment: a workgroup walks output rows (grid-stride, the one 64-bit division), its lanes the pt*P*P*C
 // elements of the row (32-bit index arithmetic; the launcher refuses a row of 2^31 elements or more).
 template <typename S, typename D, bool FWD>
-__global__ void tubelet_scalar_kernel(ptr_t<FWD, S> __restrict__ pixp, ptr_t<!FWD, D> __restrict__ vecp, int64_t rows,
-                                      int C, int H, int W, int P, int pt) {
+__global__ void patchify_scalar_kernel(ptr_t<FWD, S> __restrict__ pixp, ptr_t<!FWD, D> __restrict__ vecp, int64_t rows,
+                                       int C, int H, int W, int P, int pt) {
   const unsigned nw = W / P, npf = (H / P) * nw;
   const unsigned pd = (unsigned)P * P * C;                     // one frame's share of a row
   const unsigned rowlen = pd * pt, pc = (unsigned)P * C;
@@ -223,8 +229,8 @@ __global__ void tubelet_scalar_kernel(ptr_t<FWD, S> __restrict__ pixp, ptr_t<!FW
 }
 
 template <typename S, typename D, bool FWD>
-int tubelet_dispatch(ptr_t<FWD, void> pix, ptr_t<!FWD, void> vec, int64_t frames, int C, int H, int W, int P, int pt,
-                     hipStream_t st, const char* name) {
+int patchify_dispatch(ptr_t<FWD, void> pix, ptr_t<!FWD, void> vec, int64_t frames, int C, int H, int W, int P, int pt,
+                      hipStream_t st, const char* name) {
   const int nh = H / P, nw = W / P;
   const int64_t items = frames * nh * P * nw;
   const bool vec_ok = (W % 8 == 0) && (P % 8 == 0) && ((P * C) % 8 == 0) && dvt_aligned16(pix) && dvt_aligned16(vec) &&
@@ -237,22 +243,22 @@ int tubelet_dispatch(ptr_t<FWD, void> pix, ptr_t<!FWD, void> vec, int64_t frames
       int64_t blocks = dvt_cdiv(dvt_cdiv(npatches, 4), 4);
       const int64_t cap = (int64_t)dvt_num_cus() * 16;
       if (blocks > cap) blocks = cap;
-      hipLaunchKernelGGL((tubelet_p16_fwd_kernel<S, D>), dim3((unsigned)blocks), dim3(256), 0, st, pixp, vecp,
+      hipLaunchKernelGGL((patchify_p16_fwd_kernel<S, D>), dim3((unsigned)blocks), dim3(256), 0, st, pixp, vecp,
                          (unsigned)npatches, H, W, (unsigned)nw, (unsigned)(nh * nw), (unsigned)pt);
       DVT_LAUNCH_CHECK(name);
       return DVT_OK;
     }
   }
   if (vec_ok && P == 16 && C == 3) {
-    hipLaunchKernelGGL((tubelet_vec_kernel<16, 3, S, D, FWD>), dim3(tubelet_grid(items)), dim3(kBlock), 0, st, pixp, vecp,
+    hipLaunchKernelGGL((patchify_vec_kernel<16, 3, S, D, FWD>), dim3(patchify_grid(items)), dim3(kBlock), 0, st, pixp, vecp,
                        frames, H, W, pt);
   } else if (vec_ok && P == 8 && C == 3) {
-    hipLaunchKernelGGL((tubelet_vec_kernel<8, 3, S, D, FWD>), dim3(tubelet_grid(items)), dim3(kBlock), 0, st, pixp, vecp,
+    hipLaunchKernelGGL((patchify_vec_kernel<8, 3, S, D, FWD>), dim3(patchify_grid(items)), dim3(kBlock), 0, st, pixp, vecp,
                        frames, H, W, pt);
   } else {
     if ((int64_t)P * P * C * pt >= ((int64_t)1 << 31)) DVT_UNSUPPORTED("%s: a row of pt*P*P*C >= 2^31 elements", name);
     const int64_t rows = frames / pt * nh * nw;
-    hipLaunchKernelGGL((tubelet_scalar_kernel<S, D, FWD>), dim3(tubelet_grid(rows * kBlock)), dim3(kBlock), 0, st, pixp, vecp,
+    hipLaunchKernelGGL((patchify_scalar_kernel<S, D, FWD>), dim3(patchify_grid(rows * kBlock)), dim3(kBlock), 0, st, pixp, vecp,
                        rows, C, H, W, P, pt);
   }
   DVT_LAUNCH_CHECK(name);
@@ -261,8 +267,8 @@ int tubelet_dispatch(ptr_t<FWD, void> pix, ptr_t<!FWD, void> vec, int64_t frames
 
 // pix: x (forward, read) / dx (adjoint, written); vec: out (forward, written) / dout (adjoint, read)
 template <bool FWD>
-int tubelet_entry(ptr_t<FWD, void> pix, int pix_dtype, ptr_t<!FWD, void> vec, int vec_dtype, int64_t frames, int C, int H,
-                  int W, int P, int pt, dvt_stream_t stream, const char* name) {
+int patchify_entry(ptr_t<FWD, void> pix, int pix_dtype, ptr_t<!FWD, void> vec, int vec_dtype, int64_t frames, int C, int H,
+                   int W, int P, int pt, dvt_stream_t stream, const char* name) {
   DVT_REQUIRE(pix && vec, "%s: null pointer", name);
   DVT_REQUIRE(pt >= 1, "%s: tubelet length %d < 1", name, pt);
   DVT_REQUIRE(frames >= 0 && C > 0 && H > 0 && W > 0 && P > 0, "%s: bad sizes", name);
@@ -270,30 +276,41 @@ int tubelet_entry(ptr_t<FWD, void> pix, int pix_dtype, ptr_t<!FWD, void> vec, in
   DVT_REQUIRE(H % P == 0 && W % P == 0, "%s: image %dx%d not divisible by patch %d", name, H, W, P);
   if (frames == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
-#define DVT_TUBELET_CASE(PD, S, VD, D) \
-  if (pix_dtype == PD && vec_dtype == VD) return tubelet_dispatch<S, D, FWD>(pix, vec, frames, C, H, W, P, pt, st, name);
-  DVT_TUBELET_CASE(DVT_F32, float, DVT_F32, float)
-  DVT_TUBELET_CASE(DVT_F32, float, DVT_BF16, bf16)
-  DVT_TUBELET_CASE(DVT_F32, float, DVT_F16, f16)
-  DVT_TUBELET_CASE(DVT_BF16, bf16, DVT_BF16, bf16)
-  DVT_TUBELET_CASE(DVT_F16, f16, DVT_F16, f16)
-  DVT_TUBELET_CASE(DVT_BF16, bf16, DVT_F32, float)
-  DVT_TUBELET_CASE(DVT_F16, f16, DVT_F32, float)
-#undef DVT_TUBELET_CASE
+#define DVT_PATCHIFY_CASE(PD, S, VD, D) \
+  if (pix_dtype == PD && vec_dtype == VD) return patchify_dispatch<S, D, FWD>(pix, vec, frames, C, H, W, P, pt, st, name);
+  DVT_PATCHIFY_CASE(DVT_F32, float, DVT_F32, float)
+  DVT_PATCHIFY_CASE(DVT_F32, float, DVT_BF16, bf16)
+  DVT_PATCHIFY_CASE(DVT_F32, float, DVT_F16, f16)
+  DVT_PATCHIFY_CASE(DVT_BF16, bf16, DVT_BF16, bf16)
+  DVT_PATCHIFY_CASE(DVT_F16, f16, DVT_F16, f16)
+  DVT_PATCHIFY_CASE(DVT_BF16, bf16, DVT_F32, float)
+  DVT_PATCHIFY_CASE(DVT_F16, f16, DVT_F32, float)
+#undef DVT_PATCHIFY_CASE
   DVT_UNSUPPORTED("%s: dtype pair (%d, %d) not supported", name, pix_dtype, vec_dtype);
 }
 }  // namespace
 
 extern "C" {
 
+// the per-frame pair: the entry at pt = 1, under its own names
+int dvt_patchify(const void* x, int x_dtype, void* out, int out_dtype, int64_t frames, int C, int H, int W, int P,
+                 dvt_stream_t stream) {
+  return patchify_entry<true>(x, x_dtype, out, out_dtype, frames, C, H, W, P, 1, stream, "dvt_patchify");
+}
+
+int dvt_patchify_bwd(const void* dout, int dout_dtype, void* dx, int dx_dtype, int64_t frames, int C, int H, int W, int P,
+                     dvt_stream_t stream) {
+  return patchify_entry<false>(dx, dx_dtype, dout, dout_dtype, frames, C, H, W, P, 1, stream, "dvt_patchify_bwd");
+}
+
 int dvt_tubelet_patchify(const void* x, int x_dtype, void* out, int out_dtype, int64_t frames, int C, int H, int W, int P,
                          int pt, dvt_stream_t stream) {
-  return tubelet_entry<true>(x, x_dtype, out, out_dtype, frames, C, H, W, P, pt, stream, "dvt_tubelet_patchify");
+  return patchify_entry<true>(x, x_dtype, out, out_dtype, frames, C, H, W, P, pt, stream, "dvt_tubelet_patchify");
 }
 
 int dvt_tubelet_patchify_bwd(const void* dout, int dout_dtype, void* dx, int dx_dtype, int64_t frames, int C, int H, int W,
                              int P, int pt, dvt_stream_t stream) {
-  return tubelet_entry<false>(dx, dx_dtype, dout, dout_dtype, frames, C, H, W, P, pt, stream, "dvt_tubelet_patchify_bwd");
+  return patchify_entry<false>(dx, dx_dtype, dout, dout_dtype, frames, C, H, W, P, pt, stream, "dvt_tubelet_patchify_bwd");
 }
 
 }  // extern "C"

@@ -351,34 +351,15 @@ def layernorm(x: Tensor, w: Tensor, b: Tensor, eps: float = 1e-5) -> Tensor:
 # Patch embedding: patchify gather + Linear  (vit.py:89-92,110)
 # ---------------------------------------------------------------------------
 class _PatchEmbed(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, clip, w, b, patch, dtype):
-        patches = ops.patchify(clip, patch, dtype)          # [frames*n, P*P*C]
-        wc = _wc(w, dtype)
-        emb = ops.linear_fwd(patches, wc, _f32(b))
-        ctx.save_for_backward(patches, wc)
-        ctx.clip_shape, ctx.clip_dtype, ctx.patch = tuple(clip.shape), clip.dtype, patch
-        ctx.sinks = (_sink(w), _sink(b))
-        return emb
-
-    @staticmethod
-    def backward(ctx, demb):
-        patches, wc = ctx.saved_tensors
-        demb = demb.contiguous()
-        dclip = None
-        if ctx.needs_input_grad[0]:
-            dpatch = ops.linear_dgrad(demb, wc)
-            dclip = ops.patchify_bwd(dpatch, ctx.clip_shape, ctx.patch, ctx.clip_dtype)
-        dw, db = _emit_wgrad_bias(ctx.sinks[0], ctx.sinks[1], demb, patches, True)
-        return dclip, dw, db, None, None
-
-
-class _TubeletEmbed(torch.autograd.Function):
-    """Tubelet embedding: one gather of the pt x P x P patches (csrc/tubelet.hip) + Linear at K = pt*P*P*C."""
+    """One gather of the pt x P x P patches (csrc/patchify.hip) + Linear at K = pt*P*P*C.  tubelet == 1 goes by the
+    per-frame op names: their profile key, and a clip that needs no frame axis."""
 
     @staticmethod
     def forward(ctx, clip, w, b, patch, dtype, tubelet):
-        patches = ops.tubelet_patchify(clip, patch, tubelet, dtype)     # [frames/pt * n, pt*P*P*C]
+        if tubelet == 1:
+            patches = ops.patchify(clip, patch, dtype)                      # [frames*n, P*P*C]
+        else:
+            patches = ops.tubelet_patchify(clip, patch, tubelet, dtype)     # [frames/pt * n, pt*P*P*C]
         wc = _wc(w, dtype)
         emb = ops.linear_fwd(patches, wc, _f32(b))
         ctx.save_for_backward(patches, wc)
@@ -393,7 +374,10 @@ class _TubeletEmbed(torch.autograd.Function):
         dclip = None
         if ctx.needs_input_grad[0]:
             dpatch = ops.linear_dgrad(demb, wc)
-            dclip = ops.tubelet_patchify_bwd(dpatch, ctx.clip_shape, ctx.patch, ctx.tubelet, ctx.clip_dtype)
+            if ctx.tubelet == 1:
+                dclip = ops.patchify_bwd(dpatch, ctx.clip_shape, ctx.patch, ctx.clip_dtype)
+            else:
+                dclip = ops.tubelet_patchify_bwd(dpatch, ctx.clip_shape, ctx.patch, ctx.tubelet, ctx.clip_dtype)
         dw, db = _emit_wgrad_bias(ctx.sinks[0], ctx.sinks[1], demb, patches, True)
         return dclip, dw, db, None, None, None
 
@@ -401,9 +385,7 @@ class _TubeletEmbed(torch.autograd.Function):
 def patch_embed(clip: Tensor, w: Tensor, b: Tensor, patch: int, dtype: torch.dtype, tubelet: int = 1) -> Tensor:
     """clip [..., C, H, W] -> [frames * n, d] in ``dtype``; with ``tubelet`` = pt > 1, clip [..., t, C, H, W] ->
     [frames / pt * n, d] from w [d, pt*P*P*C] (k slowest: the pt per-frame patch vectors concatenated)."""
-    if tubelet == 1:
-        return _PatchEmbed.apply(clip, w, b, patch, dtype)
-    return _TubeletEmbed.apply(clip, w, b, patch, dtype, tubelet)
+    return _PatchEmbed.apply(clip, w, b, patch, dtype, tubelet)
 
 
 # ---------------------------------------------------------------------------

@@ -14,7 +14,7 @@ Build-side additions (keyword-only, defaults keep reference behaviour):
 for the fp32 parity mode); ``activation_checkpointing`` -- keep one activation per
 transformer block and recompute the block in backward (BASELINE configs[4]);
 ``tubelet_size`` -- pt > 1 replaces the per-frame tokeniser by the ViViT paper's tubelet embedding (a pt x P x P patch
-across pt consecutive frames, csrc/tubelet.hip): the space stack runs on ``num_frames / pt`` temporal tokens.  The
+across pt consecutive frames, csrc/patchify.hip): the space stack runs on ``num_frames / pt`` temporal tokens.  The
 state-dict keys stay the reference's; ``to_patch_embedding.1.weight`` is ``[dim, pt*P*P*C]`` and ``pos_embedding``
 ``[1, num_frames // pt, n + 1, dim]``.  ``ViViT.load_frame_checkpoint`` carries a per-frame checkpoint into such a model
 (``inflate_patch_embedding``).
@@ -39,9 +39,6 @@ class Patchify(nn.Module):
     def forward(self, x):  # only reached when used stand-alone
         from .. import ops
         b, t = x.shape[0], x.shape[1]
-        if self.tubelet_size == 1:
-            out = ops.patchify(x, self.patch_size, x.dtype)
-            return out.view(b, t, -1, out.shape[-1])
         out = ops.tubelet_patchify(x, self.patch_size, self.tubelet_size, x.dtype)
         return out.view(b, t // self.tubelet_size, -1, out.shape[-1])
 

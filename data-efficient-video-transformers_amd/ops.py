@@ -212,33 +212,6 @@ def act_bwd(dy: Tensor, x: Tensor, act: int) -> Tensor:
     return dx
 
 
-def patchify(x: Tensor, patch: int, out_dtype: torch.dtype) -> Tensor:
-    """[..., C, H, W] -> [frames * n, P*P*C]  (vit.py:90 ordering)."""
-    _need_cuda(x)
-    x = x.contiguous()
-    Cc, H, W = x.shape[-3:]
-    frames = x.numel() // (Cc * H * W)
-    n = (H // patch) * (W // patch)
-    out = torch.empty((frames * n, patch * patch * Cc), dtype=out_dtype, device=x.device)
-    with _timed(("hbm", "patchify", x.numel()), x.numel() * x.element_size() + out.numel() * out.element_size()):
-        L.check(L.load().dvt_patchify(x.data_ptr(), dt(x), out.data_ptr(), _DT[out_dtype], frames, Cc, H, W, patch,
-                                      _stream()), "dvt_patchify")
-    return out
-
-
-def patchify_bwd(dout: Tensor, shape, patch: int, dx_dtype: torch.dtype) -> Tensor:
-    _need_cuda(dout)
-    dout = dout.contiguous()
-    Cc, H, W = shape[-3:]
-    frames = 1
-    for s in shape[:-3]:
-        frames *= s
-    dx = torch.empty(tuple(shape), dtype=dx_dtype, device=dout.device)
-    L.check(L.load().dvt_patchify_bwd(dout.data_ptr(), dt(dout), dx.data_ptr(), _DT[dx_dtype], frames, Cc, H, W,
-                                      patch, _stream()), "dvt_patchify_bwd")
-    return dx
-
-
 def _tubelet_geometry(shape, patch: int, tubelet: int, what: str):
     """(frames, C, H, W) of a clip shape [..., t, C, H, W] whose t frames split into whole tubelets."""
     if len(shape) < 4:
@@ -254,34 +227,48 @@ def _tubelet_geometry(shape, patch: int, tubelet: int, what: str):
     return frames, Cc, H, W
 
 
+def _patch_gather(what: str, src: Tensor, shape, patch: int, tubelet: Optional[int], dtype: torch.dtype) -> Tensor:
+    """The one caller of the patch gather (csrc/patchify.hip) in both directions: allocate, time, launch dvt_<what>.
+    ``shape`` is the clip's; ``src`` is the clip (forward) or dout (``what`` ends in _bwd).  ``tubelet`` None is the
+    per-frame pair: the entry points without a pt argument, a clip [..., C, H, W] that needs no frame axis."""
+    _need_cuda(src)
+    if tubelet is None:
+        frames, Cc, H, W = _tubelet_geometry((1, *shape), patch, 1, what)
+    else:
+        frames, Cc, H, W = _tubelet_geometry(shape, patch, tubelet, what)
+    pt = () if tubelet is None else (tubelet,)
+    src = src.contiguous()
+    if what.endswith("_bwd"):
+        if src.numel() != frames * Cc * H * W:
+            raise ValueError(f"{what}: dout {tuple(src.shape)} does not hold a clip of shape {tuple(shape)}")
+        dst = torch.empty(tuple(shape), dtype=dtype, device=src.device)
+    else:
+        rows = frames // (tubelet or 1) * (H // patch) * (W // patch)
+        dst = torch.empty((rows, (tubelet or 1) * patch * patch * Cc), dtype=dtype, device=src.device)
+    with _timed(("hbm", what, src.numel()), src.numel() * src.element_size() + dst.numel() * dst.element_size()):
+        L.check(getattr(L.load(), "dvt_" + what)(src.data_ptr(), dt(src), dst.data_ptr(), _DT[dtype], frames, Cc, H, W, patch,
+                                                 *pt, _stream()), "dvt_" + what)
+    return dst
+
+
+def patchify(x: Tensor, patch: int, out_dtype: torch.dtype) -> Tensor:
+    """[..., C, H, W] -> [frames * n, P*P*C]  (vit.py:90 ordering): the tubelet gather at pt = 1 under its own name."""
+    return _patch_gather("patchify", x, x.shape, patch, None, out_dtype)
+
+
+def patchify_bwd(dout: Tensor, shape, patch: int, dx_dtype: torch.dtype) -> Tensor:
+    return _patch_gather("patchify_bwd", dout, shape, patch, None, dx_dtype)
+
+
 def tubelet_patchify(x: Tensor, patch: int, tubelet: int, out_dtype: torch.dtype) -> Tensor:
     """[..., t, C, H, W] -> [(frames / tubelet) * n, tubelet*P*P*C]: 'b (tau k) c (h p1) (w p2) -> (b tau h w) (k p1 p2 c)'
-    (csrc/tubelet.hip; tubelet == 1 is ``patchify``)."""
-    _need_cuda(x)
-    frames, Cc, H, W = _tubelet_geometry(x.shape, patch, tubelet, "tubelet_patchify")
-    x = x.contiguous()
-    n = (H // patch) * (W // patch)
-    out = torch.empty((frames // tubelet * n, tubelet * patch * patch * Cc), dtype=out_dtype, device=x.device)
-    with _timed(("hbm", "tubelet_patchify", x.numel()), x.numel() * x.element_size() + out.numel() * out.element_size()):
-        L.check(L.load().dvt_tubelet_patchify(x.data_ptr(), dt(x), out.data_ptr(), _DT[out_dtype], frames, Cc, H, W, patch,
-                                              tubelet, _stream()), "dvt_tubelet_patchify")
-    return out
+    (tubelet == 1 is ``patchify``)."""
+    return _patch_gather("tubelet_patchify", x, x.shape, patch, tubelet, out_dtype)
 
 
 def tubelet_patchify_bwd(dout: Tensor, shape, patch: int, tubelet: int, dx_dtype: torch.dtype) -> Tensor:
     """The adjoint (inverse) of ``tubelet_patchify``: dout [(frames / tubelet) * n, tubelet*P*P*C] -> dx of ``shape``."""
-    _need_cuda(dout)
-    frames, Cc, H, W = _tubelet_geometry(shape, patch, tubelet, "tubelet_patchify_bwd")
-    dout = dout.contiguous()
-    if dout.numel() != frames * Cc * H * W:
-        raise ValueError(f"tubelet_patchify_bwd: dout {tuple(dout.shape)} does not hold a clip of shape {tuple(shape)}")
-    dx = torch.empty(tuple(shape), dtype=dx_dtype, device=dout.device)
-    with _timed(("hbm", "tubelet_patchify_bwd", dout.numel()),
-                dout.numel() * dout.element_size() + dx.numel() * dx.element_size()):
-        L.check(L.load().dvt_tubelet_patchify_bwd(dout.data_ptr(), dt(dout), dx.data_ptr(), _DT[dx_dtype], frames, Cc, H, W,
-                                                  patch, tubelet, _stream()), "dvt_tubelet_patchify_bwd")
-    return dx
-
+    return _patch_gather("tubelet_patchify_bwd", dout, shape, patch, tubelet, dx_dtype)
 
 def tokens_assemble_fwd(emb: Tensor, cls: Tensor, pos: Tensor, S: int, T: int, n: int) -> Tensor:
     """emb [S*n, d]; cls [d] f32; pos [T, rows>=n+1, d] f32 -> [S, n+1, d]."""

@@ -120,7 +120,8 @@ int dvt_rng_advance(uint64_t* rng_state, uint64_t delta, dvt_stream_t stream);
 /* ---------------------------------------------------------------- patchify
  * Rearrange 'b t c (h p1) (w p2) -> b t (h w) (p1 p2 c)'  (src/models/vit.py:90).
  * x: [frames, C, H, W] in x_dtype; out: [frames * (H/P) * (W/P), P*P*C] in
- * out_dtype (patch-vector index = (p1*P + p2)*C + c). */
+ * out_dtype (patch-vector index = (p1*P + p2)*C + c).  This pair is the tubelet pair below at pt = 1: one
+ * implementation (csrc/patchify.hip), the same argument checks, error texts under its own names. */
 int dvt_patchify(const void* x, int x_dtype, void* out, int out_dtype, int64_t frames, int C,
                  int H, int W, int P, dvt_stream_t stream);
 /* Adjoint of dvt_patchify (scatter back to pixel layout): needed when the clip
@@ -135,7 +136,7 @@ int dvt_patchify_bwd(const void* dout, int dout_dtype, void* dx, int dx_dtype, i
  * pt*P*P*C] in out_dtype,
  *   out[((bi*(t/pt) + tau)*nh + ph)*nw + pw, ((k*P + p1)*P + p2)*C + c] = x[bi, tau*pt + k, c, ph*P + p1, pw*P + p2]
  * with nh = H/P, nw = W/P: k slowest, c fastest -- a row is the pt per-frame patch vectors of dvt_patchify's order,
- * concatenated; pt == 1 is dvt_patchify bit for bit.  DVT_ERR_BAD_ARG for a null pointer, pt < 1, frames % pt != 0,
+ * concatenated; pt == 1 is dvt_patchify itself (the same launch).  DVT_ERR_BAD_ARG for a null pointer, pt < 1, frames % pt != 0,
  * H % P != 0 or W % P != 0, before any HIP call. */
 int dvt_tubelet_patchify(const void* x, int x_dtype, void* out, int out_dtype, int64_t frames, int C, int H, int W, int P,
                          int pt, dvt_stream_t stream);

@@ -83,7 +83,7 @@ def test_no_kernel_of_the_library_lost_an_address_space():
     bad = {k: v for k, v in ops.items() if v and not any(a in k for a in mod.ALLOWED)}
     assert not bad, f"kernels with FLAT memory instructions: {bad}"
     # the milder form: ds_* accesses whose address is a generic pointer converted (null check + select) per access
-    badg = {k: v for k, v in gen.items() if v > mod.GENERIC_LIMIT and not any(a in k for a in mod.ALLOWED + mod.ALLOWED_GENERIC)}
+    badg = {k: v for k, v in gen.items() if v > mod.GENERIC_LIMIT and not any(a in k for a in mod.ALLOWED)}
     assert not badg, f"kernels converting generic pointers to LDS addresses in bulk: {badg}"
 
 

@@ -1,4 +1,4 @@
-"""Tubelet embedding on the GPU (csrc/tubelet.hip, ops.tubelet_patchify*, functional._TubeletEmbed, ViViT(tubelet_size=),
+"""Tubelet embedding on the GPU (csrc/patchify.hip, ops.tubelet_patchify*, functional._PatchEmbed, ViViT(tubelet_size=),
 AttentionRollout on a tubelet model) against the CPU restatement tests/tubelet_ref.py.
 
 The gather is a permutation (plus one rounding to the destination type): bit-exact.  Embedding, model and rollout are held
@@ -39,7 +39,7 @@ GPU_SHAPES = R.GATHER_SHAPES + [
     (2, 8, 3, 64, 64, 16, 2),      # 128 rows, more than one wave per workgroup
     (1, 4, 3, 32, 32, 16, 1),      # pt = 1: must equal ops.patchify
 ]
-PAIRS = [("f32", "f32"), ("f32", "bf16"), ("bf16", "bf16"), ("f16", "f16")]
+PAIRS = [("f32", "f32"), ("f32", "bf16"), ("bf16", "bf16"), ("f16", "f16"), ("f32", "f16"), ("bf16", "f32"), ("f16", "f32")]
 
 
 @functools.lru_cache(maxsize=None)

@@ -82,9 +82,8 @@ SCOPE = {
                  "sigmoid_bce_bwd_kernel"},
     "conv.hip": {"transpose_kernel"},
 }
-# the other kernels of elementwise.hip have tests of their own in tests/test_gpu_ops.py (patchify, dropout)
-ELEMENTWISE_ELSEWHERE = {"patchify_vec_kernel", "patchify16_fwd_kernel", "patchify_generic_kernel", "dropout_kernel",
-                         "dropout_fused_kernel", "rng_advance_kernel"}
+# the other kernels of elementwise.hip have tests of their own in tests/test_gpu_ops.py (dropout)
+ELEMENTWISE_ELSEWHERE = {"dropout_kernel", "dropout_fused_kernel", "rng_advance_kernel"}
 
 _GLOBAL = re.compile(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", re.S)
 

@@ -24,8 +24,9 @@ def test_the_two_formulations_agree_exactly(shape):
     from dvt_amd import ops
     frames, *chw = ops._tubelet_geometry(x.shape, P, pt, "tubelet_patchify")
     assert (frames, *chw) == (b * t, C, H, W) and (frames // pt * nh * nw, pt * P * P * C) == a.shape
-    with pytest.raises(ValueError, match="tubelets"):
-        ops._tubelet_geometry((b, pt + 1, C, H, W), P, pt, "tubelet_patchify")       # pt >= 2 in every shape here
+    if pt >= 2:                                # pt + 1 frames are whole tubelets at pt = 1: nothing to refuse there
+        with pytest.raises(ValueError, match="tubelets"):
+            ops._tubelet_geometry((b, pt + 1, C, H, W), P, pt, "tubelet_patchify")
     # the definition, entry by entry, on a few hundred random entries
     g = torch.Generator().manual_seed(5)
     for _ in range(300):
@@ -192,3 +193,12 @@ def test_null_and_bad_arguments_fail_before_any_hip_call():
         assert fn(256, 0, 256, 0, 4, 3, 20, 16, 8, 2, None) == -1 and b"divisible" in lib.dvt_last_error()
         assert fn(256, 0, 256, 0, 4, 3, 16, 20, 8, 2, None) == -1 and b"divisible" in lib.dvt_last_error()
         assert fn(256, 0, 256, 0, 0, 3, 16, 16, 8, 2, None) == 0                   # no frames: nothing is launched
+    # the per-frame pair is the same entry at pt = 1, under its own names and without the pt argument
+    for name in ("dvt_patchify", "dvt_patchify_bwd"):
+        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == 10
+        fn = getattr(lib, name)
+        assert fn(None, 0, None, 0, 4, 3, 16, 16, 8, None) == -1 and lib.dvt_last_error().startswith(name.encode() + b":")
+        assert fn(256, 0, 256, 0, 4, 3, 20, 16, 8, None) == -1 and b"divisible" in lib.dvt_last_error()
+        assert fn(256, 0, 256, 0, 4, 3, 16, 20, 8, None) == -1 and b"divisible" in lib.dvt_last_error()
+        assert lib.dvt_last_error().startswith(name.encode() + b":")
+        assert fn(256, 0, 256, 0, 0, 3, 16, 16, 8, None) == 0

@@ -1,4 +1,4 @@
-"""CPU restatement of the tubelet embedding (csrc/tubelet.hip, functional._TubeletEmbed, models.vit), in two independent
+"""CPU restatement of the tubelet embedding (csrc/patchify.hip, functional._PatchEmbed, models.vit), in two independent
 formulations:
 
   * ``gather`` -- reshape / permute: 'b (tau k) c (h p1) (w p2) -> (b tau h w) (k p1 p2 c)';
@@ -21,6 +21,10 @@ GATHER_SHAPES = [
     (1, 2, 3, 48, 16, 16, 2),      # 3 rows: a partly filled last wave group
     (1, 6, 3, 16, 24, 8, 3),       # odd pt, vector form
     (2, 4, 1, 8, 12, 4, 4),        # scalar form, pt == t
+    # pt = 1, the per-frame gather through the same kernels (ops.patchify is this launch)
+    (1, 3, 3, 48, 16, 16, 1),      # fast form, 9 patches of 3 per frame: wave groups straddle frames, the last holds one
+    (1, 2, 3, 16, 24, 8, 1),       # vector form
+    (2, 2, 1, 8, 12, 4, 1),        # scalar form
 ]
 
 

@@ -9,9 +9,10 @@ variant; the variants alternate within one process, round by round, and a varian
 of its window means.  The spread is what repeated timings of the SAME code show in this run: max - min of the per-frame
 gather's window means.
 
-1. Gather, metric clip [8, 32, 3, 224, 224], bf16 -> bf16: ``ops.patchify`` and ``ops.tubelet_patchify`` at pt 2 and 4.
-   The same bytes move along the same image rows, so the tubelet gather is held to the per-frame kernel: its median may
-   exceed patchify's by no more than that spread (reported as held / missed; exit status 1 when missed).
+1. Gather, metric clip [8, 32, 3, 224, 224], bf16 -> bf16: ``ops.patchify`` and ``ops.tubelet_patchify`` at pt 1, 2 and
+   4 (pt = 1 is the per-frame launch under its other name).  The same bytes move along the same image rows, so the
+   tubelet gather is held to the per-frame one: its median may exceed patchify's by no more than that spread (reported
+   as held / missed; exit status 1 when missed).  The vector form (f32 -> f32) is timed after it and reported only.
 2. Step, ``ViViT.loss`` forward + backward at the metric shape (bf16) and at BASELINE configs[4] (T = 64, 288^2, fp16,
    activation checkpointing), tubelet_size 1 and 2, each replayed from a captured hipGraph: ms / step, space-stack rows,
    peak allocated memory of an eager step above what was allocated before the model was built.  Reported only.
@@ -67,10 +68,11 @@ def bench_gather(rounds, seconds):
     x = torch.randn(8, 32, 3, 224, 224, generator=g).to(torch.bfloat16).cuda()
     nbytes = 2 * x.numel() * x.element_size()
     ref = ops.patchify(x, 16, torch.bfloat16).view(8, 32, 196, 768)
-    for pt in (2, 4):      # the outputs are the per-frame vectors regrouped: checked at the size that is timed
+    for pt in (1, 2, 4):   # the outputs are the per-frame vectors regrouped: checked at the size that is timed
         got = ops.tubelet_patchify(x, 16, pt, torch.bfloat16).view(8, 32 // pt, 196, pt, 768)
         assert torch.equal(got, ref.view(8, 32 // pt, pt, 196, 768).transpose(2, 3)), pt
     variants = {"patchify": lambda: ops.patchify(x, 16, torch.bfloat16),
+                "tubelet pt=1": lambda: ops.tubelet_patchify(x, 16, 1, torch.bfloat16),
                 "tubelet pt=2": lambda: ops.tubelet_patchify(x, 16, 2, torch.bfloat16),
                 "tubelet pt=4": lambda: ops.tubelet_patchify(x, 16, 4, torch.bfloat16)}
     times = _alternate(variants, rounds, seconds)
@@ -89,6 +91,11 @@ def bench_gather(rounds, seconds):
     lines.append(f"Spread of the repeated `patchify` windows in this run (max - min over {rounds} rounds): "
                  f"{spread * 1e6:.3f} us.  Condition (tubelet median - patchify median <= spread): "
                  f"{'held' if held else 'MISSED'}.")
+    # the vector form (what an fp32 destination takes): reported, not gated -- it is on no measured path
+    xf = torch.randn(8, 32, 3, 224, 224, generator=g).cuda()
+    vt = _alternate({"v": lambda: ops.patchify(xf, 16, torch.float32)}, max(3, rounds // 2), seconds)["v"]
+    lines.append(f"Vector form, `patchify` f32 -> f32 on the same shape ({4 * xf.numel() * 2} bytes): median "
+                 f"{statistics.median(vt) * 1e6:.3f} us (min {min(vt) * 1e6:.3f}, max {max(vt) * 1e6:.3f}); reported only.")
     return lines, held
 
 

@@ -21,7 +21,6 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa_listing import kernel_listings  # noqa: E402
 
 GENERIC_LIMIT = 12
-ALLOWED_GENERIC = ("patchify_generic",)   # real null checks of optional global pointers in an unrolled loop (any-patch-size fallback)
 ALLOWED = ("rocprim",)          # kernel-name substrings that may keep FLAT accesses (library code: the sorts of eval_metrics.hip)
 
 
@@ -44,7 +43,7 @@ def main():
     gen = {}
     ops = flat_ops(so, gen)
     bad = {k: v for k, v in ops.items() if v and not any(a in k for a in ALLOWED)}
-    badg = {k: v for k, v in gen.items() if v > GENERIC_LIMIT and not any(a in k for a in ALLOWED + ALLOWED_GENERIC)}
+    badg = {k: v for k, v in gen.items() if v > GENERIC_LIMIT and not any(a in k for a in ALLOWED)}
     print(f"{len(ops)} kernels, {sum(1 for v in ops.values() if v)} with FLAT instructions, "
           f"{len(badg)} with more than {GENERIC_LIMIT} generic-pointer null checks")
     for k, v in sorted(bad.items(), key=lambda kv: -kv[1]):
