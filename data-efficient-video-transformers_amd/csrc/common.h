@@ -43,6 +43,14 @@ static inline bool dvt_is_16bit(int dt) { return dt == DVT_BF16 || dt == DVT_F16
 static inline int64_t dvt_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 int dvt_num_cus();
 
+// Grid of a streaming (grid-stride) kernel over `items`: 256-thread workgroups, at most CUs x 8 of them, at least 1.
+static inline int dvt_grid(int64_t items) {
+  int64_t blocks = dvt_cdiv(items, 256);
+  const int64_t cap = (int64_t)dvt_num_cus() * 8;
+  if (blocks > cap) blocks = cap;
+  return (int)(blocks < 1 ? 1 : blocks);
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is an attribute of a kernel PER DEVICE: one flag per (call site, device),
 // atomic (two host threads racing on a first call both set it: idempotent), the return code recorded -- the launch behind a
 // failed call fails as well and DVT_LAUNCH_CHECK reports it.
@@ -210,6 +218,9 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 #pragma clang diagnostic pop
 
 // ---------------------------------------------------------------- device: activations
+// fp32 sigmoid with the full-precision exponential (gates, probabilities, loss gradients)
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 // Exact-erf GELU evaluated with the Abramowitz-Stegun 7.1.26 rational form
 // (|erf error| <= 1.5e-7 absolute), sharing one exponential between the cdf and
 // the pdf: exp(-x^2/2) is both the tail factor of erf(x/sqrt2) and the Gaussian

@@ -14,13 +14,6 @@ namespace {
 
 constexpr int kB = 256;
 
-inline int cgrid(int64_t items) {
-  int64_t b = dvt_cdiv(items, kB);
-  const int64_t cap = (int64_t)dvt_num_cus() * 8;
-  if (b > cap) b = cap;
-  return (int)(b < 1 ? 1 : b);
-}
-
 // ------------------------------------------------------------------ im2col / col2im
 // out[(n, ho, wo), (ki*kw + kj)*C + c] = x[n, ho*s - p + ki, wo*s - p + kj, c]   (0 outside)
 // columns [kh*kw*C, ld) are zero (K padding for the MFMA kernels).
@@ -1505,7 +1498,7 @@ int dvt_im2col(const void* x, int x_dtype, int x_nchw, void* out, int out_dtype,
   if (x_nchw && C == 3 && kh == 7 && kw == 7 && ld % 8 == 0 && ld < (1 << 20) && dvt_aligned16(out)) {
 #define DVT_STEM_CASE(SD, S, DD, D)                                                                                   \
   if (x_dtype == SD && out_dtype == DD) {                                                                             \
-    hipLaunchKernelGGL((im2col_nchw_stem_kernel<S, D, 3, 7, 7>), dim3(cgrid(rows * (ld >> 3))), dim3(kB), 0, st,      \
+    hipLaunchKernelGGL((im2col_nchw_stem_kernel<S, D, 3, 7, 7>), dim3(dvt_grid(rows * (ld >> 3))), dim3(kB), 0, st,      \
                        (const S*)x, (D*)out, (int)N, H, W, sh, sw, ph, pw, Ho, Wo, (int)ld);                           \
     DVT_LAUNCH_CHECK("dvt_im2col(stem)");                                                                             \
     return DVT_OK;                                                                                                    \
@@ -1520,15 +1513,15 @@ int dvt_im2col(const void* x, int x_dtype, int x_nchw, void* out, int out_dtype,
 #undef DVT_STEM_CASE
   }
   if (vec) {
-    DVT_DISPATCH_DTYPE(x_dtype, T, hipLaunchKernelGGL((im2col_nhwc_vec_kernel<T>), dim3(cgrid(rows * kh * kw * (C >> 3))),
+    DVT_DISPATCH_DTYPE(x_dtype, T, hipLaunchKernelGGL((im2col_nhwc_vec_kernel<T>), dim3(dvt_grid(rows * kh * kw * (C >> 3))),
                                                       dim3(kB), 0, st, (const T*)x, (T*)out, (int)N, C, H, W, kh, kw,
                                                       sh, sw, ph, pw, Ho, Wo, ld));
   } else {
 #define DVT_IM2COL_CASE(SD, S, DD, D)                                                                        \
   if (x_dtype == SD && out_dtype == DD) {                                                                    \
-    if (x_nchw) hipLaunchKernelGGL((im2col_kernel<S, D, true>), dim3(cgrid(rows * ld)), dim3(kB), 0, st,     \
+    if (x_nchw) hipLaunchKernelGGL((im2col_kernel<S, D, true>), dim3(dvt_grid(rows * ld)), dim3(kB), 0, st,     \
                                    (const S*)x, (D*)out, (int)N, C, H, W, kh, kw, sh, sw, ph, pw, Ho, Wo, ld);  \
-    else hipLaunchKernelGGL((im2col_kernel<S, D, false>), dim3(cgrid(rows * ld)), dim3(kB), 0, st,           \
+    else hipLaunchKernelGGL((im2col_kernel<S, D, false>), dim3(dvt_grid(rows * ld)), dim3(kB), 0, st,           \
                             (const S*)x, (D*)out, (int)N, C, H, W, kh, kw, sh, sw, ph, pw, Ho, Wo, ld);         \
     DVT_LAUNCH_CHECK("dvt_im2col");                                                                          \
     return DVT_OK;                                                                                           \
@@ -1553,7 +1546,7 @@ int dvt_col2im_nchw(const void* dcol, int dtype, void* dx, int dx_dtype, int64_t
   const int Ho = (H + 2 * ph - kh) / sh + 1, Wo = (W + 2 * pw - kw) / sw + 1;
   if (N == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(cgrid(N * H * W * C)), block(kB);
+  const dim3 grid(dvt_grid(N * H * W * C)), block(kB);
 #define DVT_C2I_CASE(SD, S, DD, D)                                                                              \
   if (dtype == SD && dx_dtype == DD) {                                                                          \
     hipLaunchKernelGGL((col2im_scalar_kernel<S, D, true>), grid, block, 0, st, (const S*)dcol, (D*)dx, (int)N, C, H, \
@@ -1582,11 +1575,11 @@ int dvt_col2im(const void* dcol, void* dx, int64_t N, int C, int H, int W, int k
   if (N == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
   if (cvec) {
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((col2im_nhwc_kernel<T>), dim3(cgrid(N * H * W * (C >> 3))), dim3(kB), 0,
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((col2im_nhwc_kernel<T>), dim3(dvt_grid(N * H * W * (C >> 3))), dim3(kB), 0,
                                                     st, (const T*)dcol, (T*)dx, (int)N, C, H, W, kh, kw, sh, sw, ph, pw,
                                                     Ho, Wo, ld, (const T*)add, add_stride));
   } else {
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((col2im_scalar_kernel<T, T, false>), dim3(cgrid(N * H * W * C)), dim3(kB), 0,
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((col2im_scalar_kernel<T, T, false>), dim3(dvt_grid(N * H * W * C)), dim3(kB), 0,
                                                     st, (const T*)dcol, (T*)dx, (int)N, C, H, W, kh, kw, sh, sw, ph, pw,
                                                     Ho, Wo, ld));
   }
@@ -1598,7 +1591,7 @@ int dvt_conv_weight_pack(const float* w, void* dst, int dst_dtype, int Cout, int
                          dvt_stream_t stream) {
   DVT_REQUIRE(w && dst && Cout > 0 && Cin > 0 && ld >= (int64_t)Cin * kh * kw, "dvt_conv_weight_pack: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  DVT_DISPATCH_DTYPE(dst_dtype, T, hipLaunchKernelGGL((weight_pack_kernel<T>), dim3(cgrid((int64_t)Cout * ld)), dim3(kB),
+  DVT_DISPATCH_DTYPE(dst_dtype, T, hipLaunchKernelGGL((weight_pack_kernel<T>), dim3(dvt_grid((int64_t)Cout * ld)), dim3(kB),
                                                       0, st, w, (T*)dst, Cout, Cin, kh, kw, ld));
   DVT_LAUNCH_CHECK("dvt_conv_weight_pack");
   return DVT_OK;
@@ -1633,14 +1626,14 @@ int dvt_conv_weight_pack_group(const dvt_pack_entry* entries, int count, dvt_str
 
 int dvt_pad3_f32(const float* src, float* dst, int A, int B, int K, int Ap, int Bp, dvt_stream_t stream) {
   DVT_REQUIRE(src && dst && A > 0 && B > 0 && K > 0 && Ap >= A && Bp >= B, "dvt_pad3_f32: bad arguments");
-  hipLaunchKernelGGL(pad3_kernel, dim3(cgrid((int64_t)Ap * Bp * K)), dim3(kB), 0, (hipStream_t)stream, src, dst, A, B, K, Ap, Bp);
+  hipLaunchKernelGGL(pad3_kernel, dim3(dvt_grid((int64_t)Ap * Bp * K)), dim3(kB), 0, (hipStream_t)stream, src, dst, A, B, K, Ap, Bp);
   DVT_LAUNCH_CHECK("dvt_pad3_f32");
   return DVT_OK;
 }
 
 int dvt_unpad3_f32(const float* src, float* dst, int A, int B, int K, int Bp, int accumulate, dvt_stream_t stream) {
   DVT_REQUIRE(src && dst && A > 0 && B > 0 && K > 0 && Bp >= B, "dvt_unpad3_f32: bad arguments");
-  hipLaunchKernelGGL(unpad3_kernel, dim3(cgrid((int64_t)A * B * K)), dim3(kB), 0, (hipStream_t)stream, src, dst, A, B, K, Bp,
+  hipLaunchKernelGGL(unpad3_kernel, dim3(dvt_grid((int64_t)A * B * K)), dim3(kB), 0, (hipStream_t)stream, src, dst, A, B, K, Bp,
                      accumulate);
   DVT_LAUNCH_CHECK("dvt_unpad3_f32");
   return DVT_OK;
@@ -1649,7 +1642,7 @@ int dvt_unpad3_f32(const float* src, float* dst, int A, int B, int K, int Bp, in
 int dvt_conv_weight_unpack_grad_t(const float* gt, float* dw, int Cout, int Cin, int kh, int kw, int accumulate,
                                   dvt_stream_t stream) {
   DVT_REQUIRE(gt && dw && Cout > 0 && Cin > 0 && kh > 0 && kw > 0, "dvt_conv_weight_unpack_grad_t: bad arguments");
-  hipLaunchKernelGGL(weight_unpack_t_kernel, dim3(cgrid((int64_t)Cout * Cin * kh * kw)), dim3(kB), 0, (hipStream_t)stream, gt,
+  hipLaunchKernelGGL(weight_unpack_t_kernel, dim3(dvt_grid((int64_t)Cout * Cin * kh * kw)), dim3(kB), 0, (hipStream_t)stream, gt,
                      dw, Cout, Cin, kh, kw, accumulate);
   DVT_LAUNCH_CHECK("dvt_conv_weight_unpack_grad_t");
   return DVT_OK;
@@ -1658,7 +1651,7 @@ int dvt_conv_weight_unpack_grad_t(const float* gt, float* dw, int Cout, int Cin,
 int dvt_conv_weight_pack_dgrad(const float* w, void* dst, int dst_dtype, int Cout, int Cin, int kh, int kw,
                                dvt_stream_t stream) {
   DVT_REQUIRE(w && dst && Cout > 0 && Cin > 0 && kh > 0 && kw > 0, "dvt_conv_weight_pack_dgrad: bad arguments");
-  DVT_DISPATCH_DTYPE(dst_dtype, T, hipLaunchKernelGGL((weight_pack_dgrad_kernel<T>), dim3(cgrid((int64_t)Cout * Cin * kh * kw)),
+  DVT_DISPATCH_DTYPE(dst_dtype, T, hipLaunchKernelGGL((weight_pack_dgrad_kernel<T>), dim3(dvt_grid((int64_t)Cout * Cin * kh * kw)),
                                                       dim3(kB), 0, (hipStream_t)stream, w, (T*)dst, Cout, Cin, kh, kw));
   DVT_LAUNCH_CHECK("dvt_conv_weight_pack_dgrad");
   return DVT_OK;
@@ -1667,7 +1660,7 @@ int dvt_conv_weight_pack_dgrad(const float* w, void* dst, int dst_dtype, int Cou
 int dvt_conv_weight_unpack_grad(const float* g, float* dw, int Cout, int Cin, int kh, int kw, int64_t ld,
                                 int accumulate, dvt_stream_t stream) {
   DVT_REQUIRE(g && dw && Cout > 0 && Cin > 0 && ld >= (int64_t)Cin * kh * kw, "dvt_conv_weight_unpack_grad: bad arguments");
-  hipLaunchKernelGGL(weight_unpack_kernel, dim3(cgrid((int64_t)Cout * Cin * kh * kw)), dim3(kB), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(weight_unpack_kernel, dim3(dvt_grid((int64_t)Cout * Cin * kh * kw)), dim3(kB), 0, (hipStream_t)stream,
                      g, dw, Cout, Cin, kh, kw, ld, accumulate);
   DVT_LAUNCH_CHECK("dvt_conv_weight_unpack_grad");
   return DVT_OK;
@@ -1786,7 +1779,7 @@ int dvt_bn_apply_fwd(const void* x, const float* mean, const float* invstd, cons
   hipStream_t st = (hipStream_t)stream;
   if (C % 8 == 0 && dvt_aligned16(x) && dvt_aligned16(y) && dvt_aligned16(residual) && dvt_aligned16(mean) &&
       dvt_aligned16(invstd) && dvt_aligned16(gamma) && dvt_aligned16(beta)) {
-    const dim3 grid(cgrid(dvt_cdiv(rows, kBnU) * (C >> 3)));
+    const dim3 grid(dvt_grid(dvt_cdiv(rows, kBnU) * (C >> 3)));
 #define DVT_BN_FWD(RES, MASK)                                                                                      \
   DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_fwd_kernel<T, RES, MASK>), grid, dim3(kB), 0, st, (const T*)x, mean, \
                                                   invstd, gamma, beta, (const T*)residual, (T*)y, (unsigned char*)relu_mask, \
@@ -1798,7 +1791,7 @@ int dvt_bn_apply_fwd(const void* x, const float* mean, const float* invstd, cons
 #undef DVT_BN_FWD
   } else {
     if (relu_mask || c_valid != C) DVT_UNSUPPORTED("dvt_bn_apply_fwd: the ReLU mask output / channel padding need C %% 8 == 0 and 16-byte aligned buffers");
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_fwd_scalar_kernel<T>), dim3(cgrid(rows * C)), dim3(kB), 0, st,
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_fwd_scalar_kernel<T>), dim3(dvt_grid(rows * C)), dim3(kB), 0, st,
                                                     (const T*)x, mean, invstd, gamma, beta, (const T*)residual, (T*)y,
                                                     rows, C, relu));
   }
@@ -1849,7 +1842,7 @@ int dvt_bn_bwd(const void* dy, const void* x, const void* y, const void* relu_ma
                      c_valid);
   DVT_LAUNCH_CHECK("dvt_bn_bwd(finalize)");
   if (cvec) {
-    const dim3 agrid(cgrid(dvt_cdiv(rows, kBnU) * (C >> 3)));
+    const dim3 agrid(dvt_grid(dvt_cdiv(rows, kBnU) * (C >> 3)));
     const int msrc = !relu ? 0 : (relu_mask ? 2 : (y ? 1 : 0));
 #define DVT_BN_BWD(MSRC, DRES)                                                                                               \
   DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_bwd_kernel<T, MSRC, DRES>), agrid, dim3(kB), 0, st, (const T*)dy,  \
@@ -1864,7 +1857,7 @@ int dvt_bn_bwd(const void* dy, const void* x, const void* y, const void* relu_ma
     else DVT_BN_BWD(0, false);
 #undef DVT_BN_BWD
   } else {
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_bwd_scalar_kernel<T>), dim3(cgrid(rows * C)), dim3(kB), 0, st,
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_bwd_scalar_kernel<T>), dim3(dvt_grid(rows * C)), dim3(kB), 0, st,
                                                     (const T*)dy, (const T*)x, (const T*)y, mean, invstd, gamma, loc,
                                                     loc + C, (T*)dx, (T*)dres, rows, C, relu, training,
                                                     1.0f / (float)rows, beta));
@@ -1882,7 +1875,7 @@ int dvt_bn_relu_maxpool_fwd(const void* z, const float* mean, const float* invst
               "dvt_bn_relu_maxpool_fwd: needs C %% 8 == 0 and 16-byte aligned buffers");
   if (N == 0) return DVT_OK;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_relu_maxpool_k3s2p1_kernel<T>), dim3(cgrid(N * Ho * Wo * (C >> 3))), dim3(kB), 0,
+  DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_relu_maxpool_k3s2p1_kernel<T>), dim3(dvt_grid(N * Ho * Wo * (C >> 3))), dim3(kB), 0,
                                                   (hipStream_t)stream, (const T*)z, mean, invstd, gamma, beta, (T*)y,
                                                   (unsigned char*)idx, (int)N, C, H, W, Ho, Wo, relu));
   DVT_LAUNCH_CHECK("dvt_bn_relu_maxpool_fwd");
@@ -1922,11 +1915,11 @@ int dvt_bn_bwd_pooled(const void* dy_pool, const void* idx, const void* x, const
                      parts, C, 0.f, 0.f, loc, loc + C, (float*)nullptr, (float*)nullptr, 0.f, 0.f, accumulate, dgamma, dbeta);
   DVT_LAUNCH_CHECK("dvt_bn_bwd_pooled(finalize)");
   if (quad) {
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_bwd_pool_quad_kernel<T>), dim3(cgrid(rows / 4 * (C >> 3))), dim3(kB), 0,
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_bwd_pool_quad_kernel<T>), dim3(dvt_grid(rows / 4 * (C >> 3))), dim3(kB), 0,
                                                     st, (const T*)dy_pool, (const T*)x, mean, invstd, gamma, beta, loc, loc + C,
                                                     (T*)dx, N, C, relu, training, 1.0f / (float)rows, pg));
   } else {
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_bwd_pool_kernel<T>), dim3(cgrid(rows * (C >> 3))), dim3(kB), 0, st,
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_bwd_pool_kernel<T>), dim3(dvt_grid(rows * (C >> 3))), dim3(kB), 0, st,
                                                     (const T*)dy_pool, (const T*)x, mean, invstd, gamma, loc, loc + C, (T*)dx,
                                                     rows, C, relu, training, 1.0f / (float)rows, beta, pg));
   }
@@ -1941,11 +1934,11 @@ int dvt_maxpool_fwd(const void* x, void* y, void* idx, int64_t N, int C, int H, 
   if (N == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
   if (C % 8 == 0 && dvt_aligned16(x) && dvt_aligned16(y) && ((uintptr_t)idx & 7) == 0) {
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool_fwd_vec_kernel<T>), dim3(cgrid(N * Ho * Wo * (C >> 3))), dim3(kB),
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool_fwd_vec_kernel<T>), dim3(dvt_grid(N * Ho * Wo * (C >> 3))), dim3(kB),
                                                     0, st, (const T*)x, (T*)y, (unsigned char*)idx, (int)N, C, H, W, k,
                                                     stride, pad, Ho, Wo));
   } else {
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool_fwd_kernel<T>), dim3(cgrid(N * Ho * Wo * C)), dim3(kB), 0, st,
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool_fwd_kernel<T>), dim3(dvt_grid(N * Ho * Wo * C)), dim3(kB), 0, st,
                                                     (const T*)x, (T*)y, (unsigned char*)idx, (int)N, C, H, W, k, stride,
                                                     pad, Ho, Wo));
   }
@@ -1960,14 +1953,14 @@ int dvt_maxpool_bwd(const void* dy, const void* idx, void* dx, int64_t N, int C,
   if (N == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
   if (C % 8 == 0 && dvt_aligned16(dy) && dvt_aligned16(dx) && ((uintptr_t)idx & 7) == 0 && k == 3 && stride == 2 && pad == 1) {
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool_bwd_k3s2p1_kernel<T>), dim3(cgrid(N * H * W * (C >> 3))), dim3(kB), 0,
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool_bwd_k3s2p1_kernel<T>), dim3(dvt_grid(N * H * W * (C >> 3))), dim3(kB), 0,
                                                     st, (const T*)dy, (const unsigned char*)idx, (T*)dx, (int)N, C, H, W, Ho, Wo));
   } else if (C % 8 == 0 && dvt_aligned16(dy) && dvt_aligned16(dx) && ((uintptr_t)idx & 7) == 0) {
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool_bwd_vec_kernel<T>), dim3(cgrid(N * H * W * (C >> 3))), dim3(kB), 0,
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool_bwd_vec_kernel<T>), dim3(dvt_grid(N * H * W * (C >> 3))), dim3(kB), 0,
                                                     st, (const T*)dy, (const unsigned char*)idx, (T*)dx, (int)N, C, H, W,
                                                     k, stride, pad, Ho, Wo));
   } else {
-    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(cgrid(N * H * W * C)), dim3(kB), 0, st,
+    DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(dvt_grid(N * H * W * C)), dim3(kB), 0, st,
                                                     (const T*)dy, (const unsigned char*)idx, (T*)dx, (int)N, C, H, W, k,
                                                     stride, pad, Ho, Wo));
   }
@@ -1987,7 +1980,7 @@ int dvt_nchw_to_nhwc_pad(const void* x, int x_dtype, void* y, int y_dtype, int64
   if (Cpad == 4) {
 #define DVT_PAIR4(SD, S, DD, D)                                                                                      \
   if (x_dtype == SD && y_dtype == DD) {                                                                             \
-    hipLaunchKernelGGL((nchw_to_nhwc_pair4_kernel<S, D>), dim3(cgrid(N * HW / 2)), dim3(kB), 0, st, (const S*)x, (D*)y, N, C, \
+    hipLaunchKernelGGL((nchw_to_nhwc_pair4_kernel<S, D>), dim3(dvt_grid(N * HW / 2)), dim3(kB), 0, st, (const S*)x, (D*)y, N, C, \
                        (int64_t)H, (int64_t)W);                                                                     \
     DVT_LAUNCH_CHECK("dvt_nchw_to_nhwc_pad");                                                                       \
     return DVT_OK;                                                                                                  \
@@ -2003,7 +1996,7 @@ int dvt_nchw_to_nhwc_pad(const void* x, int x_dtype, void* y, int y_dtype, int64
   }
 #define DVT_PAD8(SD, S, DD, D)                                                                                      \
   if (x_dtype == SD && y_dtype == DD) {                                                                             \
-    hipLaunchKernelGGL((nchw_to_nhwc_pad8_kernel<S, D>), dim3(cgrid(N * HW)), dim3(kB), 0, st, (const S*)x, (D*)y, N, C, HW); \
+    hipLaunchKernelGGL((nchw_to_nhwc_pad8_kernel<S, D>), dim3(dvt_grid(N * HW)), dim3(kB), 0, st, (const S*)x, (D*)y, N, C, HW); \
     DVT_LAUNCH_CHECK("dvt_nchw_to_nhwc_pad");                                                                       \
     return DVT_OK;                                                                                                  \
   }
@@ -2021,7 +2014,7 @@ int dvt_conv_weight_pairs(const float* w, float* wp, int Cout, int Cin, int kh, 
   DVT_REQUIRE(w && wp && Cout > 0 && Cin > 0 && Cin <= 4 && kh > 0 && kw > 0 && pw >= 0 && kwp > 0,
               "dvt_conv_weight_pairs: bad arguments");
   DVT_REQUIRE(2 * kwp - (pw & 1) >= kw, "dvt_conv_weight_pairs: kwp pairs do not cover the kernel width");
-  hipLaunchKernelGGL(conv_weight_pairs_kernel, dim3(cgrid((int64_t)Cout * 8 * kh * kwp)), dim3(kB), 0, (hipStream_t)stream, w, wp,
+  hipLaunchKernelGGL(conv_weight_pairs_kernel, dim3(dvt_grid((int64_t)Cout * 8 * kh * kwp)), dim3(kB), 0, (hipStream_t)stream, w, wp,
                      Cout, Cin, kh, kw, kwp, pw & 1);
   DVT_LAUNCH_CHECK("dvt_conv_weight_pairs");
   return DVT_OK;
@@ -2032,7 +2025,7 @@ int dvt_conv_weight_pairs_bwd(const float* dwp, float* dw, int Cout, int Cin, in
   DVT_REQUIRE(dwp && dw && Cout > 0 && Cin > 0 && Cin <= 4 && kh > 0 && kw > 0 && pw >= 0 && kwp > 0,
               "dvt_conv_weight_pairs_bwd: bad arguments");
   DVT_REQUIRE(2 * kwp - (pw & 1) >= kw, "dvt_conv_weight_pairs_bwd: kwp pairs do not cover the kernel width");
-  hipLaunchKernelGGL(conv_weight_pairs_bwd_kernel, dim3(cgrid((int64_t)Cout * Cin * kh * kw)), dim3(kB), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(conv_weight_pairs_bwd_kernel, dim3(dvt_grid((int64_t)Cout * Cin * kh * kw)), dim3(kB), 0, (hipStream_t)stream,
                      dwp, dw, Cout, Cin, kh, kw, kwp, pw & 1, accumulate);
   DVT_LAUNCH_CHECK("dvt_conv_weight_pairs_bwd");
   return DVT_OK;

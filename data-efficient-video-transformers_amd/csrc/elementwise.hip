@@ -1,6 +1,6 @@
 // elementwise.hip -- HBM-bound data-movement kernels of the clip path:
 // casts, residual add, token assembly (CLS + positional add), CLS row gather,
-// losses, dropout.  All are streaming kernels: 16-byte accesses per lane,
+// dropout.  All are streaming kernels: 16-byte accesses per lane,
 // grid-stride over at most 256 CUs x 8 blocks.  (The patch gather is a unit of
 // its own.)
 #include "common.h"
@@ -8,25 +8,6 @@
 namespace {
 
 constexpr int kBlock = 256;
-
-inline int grid_for(int64_t work_items) {
-  int64_t blocks = dvt_cdiv(work_items, kBlock);
-  int64_t cap = (int64_t)dvt_num_cus() * 8;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* smem /* >= 4 floats */) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) smem[w] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += smem[i];
-  return t;
-}
 
 // ------------------------------------------------------------------ cast / add / axpby
 template <typename S, typename D>
@@ -365,79 +346,6 @@ __global__ void mean_rows_kernel(const T* __restrict__ src, T* __restrict__ dst,
   }
 }
 
-// ------------------------------------------------------------------ losses
-template <typename T>
-__global__ void bce_fwd_kernel(const T* __restrict__ z, const float* __restrict__ y,
-                               float* __restrict__ loss, int64_t n) {
-  __shared__ float red[kBlock / 64];
-  float acc = 0.f;
-  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-    const float x = to_f32<T>(z[i]);
-    acc += fmaxf(x, 0.f) - x * y[i] + log1pf(expf(-fabsf(x)));
-  }
-  const float t = block_sum(acc, red);
-  if (threadIdx.x == 0) loss[0] = t / (float)n;
-}
-
-template <typename T>
-__global__ void bce_bwd_kernel(const T* __restrict__ z, const float* __restrict__ y,
-                               const float* __restrict__ gloss, T* __restrict__ dz, int64_t n) {
-  const float g = gloss[0] / (float)n;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float x = to_f32<T>(z[i]);
-    const float s = 1.0f / (1.0f + expf(-x));
-    dz[i] = from_f32<T>(g * (s - y[i]));
-  }
-}
-
-// One wave per row: lse(student) - student[argmax teacher]; first max wins (torch.argmax).  A lane's first element is
-// taken whatever its value, so a teacher row that is all -inf yields index 0 as torch.argmax does, never C.
-template <typename T, bool FWD>
-__global__ void ce_argmax_kernel(const T* __restrict__ st, const T* __restrict__ te,
-                                 const float* __restrict__ gloss, float* __restrict__ loss,
-                                 T* __restrict__ dst, int64_t rows, int64_t C) {
-  __shared__ float red[kBlock / 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int nw = blockDim.x >> 6;
-  float total = 0.f;
-  for (int64_t r = wave; r < rows; r += nw) {
-    const T* s = st + r * C;
-    const T* t = te + r * C;
-    float m = -INFINITY, tm = -INFINITY;
-    int64_t ti = C;
-    for (int64_t c = lane; c < C; c += 64) {
-      m = fmaxf(m, to_f32<T>(s[c]));
-      const float tv = to_f32<T>(t[c]);
-      if (tv > tm || ti == C) { tm = tv; ti = c; }
-    }
-    m = wave_max(m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float om = __shfl_xor(tm, o, 64);
-      const int64_t oi = __shfl_xor((long long)ti, o, 64);
-      if (om > tm || (om == tm && oi < ti)) { tm = om; ti = oi; }
-    }
-    float se = 0.f;
-    for (int64_t c = lane; c < C; c += 64) se += expf(to_f32<T>(s[c]) - m);
-    se = wave_sum(se);
-    if (FWD) {
-      if (lane == 0) total += m + logf(se) - to_f32<T>(s[ti]);
-    } else {
-      const float g = gloss[0] / (float)rows;
-      for (int64_t c = lane; c < C; c += 64) {
-        const float p = expf(to_f32<T>(s[c]) - m) / se;
-        dst[r * C + c] = from_f32<T>(g * (p - (c == ti ? 1.f : 0.f)));
-      }
-    }
-  }
-  if (FWD) {
-    const float t = block_sum(total, red);
-    if (threadIdx.x == 0) loss[0] = t / (float)rows;
-  }
-}
-
 // ---- dropout (nn.Dropout in training mode: frame_transformer.py:22,41-44; TPN.py:92,95; vit.py:23,25,43,104)
 // Counter-based Philox4x32-10: element i draws word (i & 3) of block (offset + i / 4) under the key (seed).  No mask
 // is stored: backward re-draws the same words.  state[0] = seed, state[1] = per-step base offset live on the device
@@ -501,7 +409,7 @@ int dvt_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n
   DVT_REQUIRE(src && dst && n >= 0, "dvt_cast: null pointer or negative size");
   DVT_REQUIRE(dvt_aligned16(src) && dvt_aligned16(dst), "dvt_cast: buffers must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const int g = grid_for((n >> 3) + 1);
+  const int g = dvt_grid((n >> 3) + 1);
 #define DVT_CAST_CASE(SD, S, DD, D)                                                        \
   if (src_dtype == SD && dst_dtype == DD) {                                                \
     hipLaunchKernelGGL((cast_kernel<S, D>), dim3(g), dim3(kBlock), 0, st, (const S*)src, (D*)dst, n); \
@@ -526,7 +434,7 @@ int dvt_add(const void* a, const void* b, void* out, int64_t n, int dtype, dvt_s
               "dvt_add: buffers must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((add_kernel<T>), dim3(grid_for((n >> 3) + 1)), dim3(kBlock),
+                     hipLaunchKernelGGL((add_kernel<T>), dim3(dvt_grid((n >> 3) + 1)), dim3(kBlock),
                                         0, st, (const T*)a, (const T*)b, (T*)out, n));
   DVT_LAUNCH_CHECK("dvt_add");
   return DVT_OK;
@@ -537,7 +445,7 @@ int dvt_act_fwd(const void* x, void* y, int64_t n, int act, int dtype, dvt_strea
   DVT_REQUIRE(x && y && n >= 0 && act >= 1 && act <= 3, "dvt_act_fwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((act_kernel<T, true>), dim3(grid_for(n)), dim3(kBlock), 0, st,
+                     hipLaunchKernelGGL((act_kernel<T, true>), dim3(dvt_grid(n)), dim3(kBlock), 0, st,
                                         (const T*)nullptr, (const T*)x, (T*)y, n, act));
   DVT_LAUNCH_CHECK("dvt_act_fwd");
   return DVT_OK;
@@ -549,7 +457,7 @@ int dvt_act_bwd(const void* dy, const void* x, void* dx, int64_t n, int act, int
   DVT_REQUIRE(dy && x && dx && n >= 0 && act >= 1 && act <= 3, "dvt_act_bwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((act_kernel<T, false>), dim3(grid_for(n)), dim3(kBlock), 0, st,
+                     hipLaunchKernelGGL((act_kernel<T, false>), dim3(dvt_grid(n)), dim3(kBlock), 0, st,
                                         (const T*)dy, (const T*)x, (T*)dx, n, act));
   DVT_LAUNCH_CHECK("dvt_act_bwd");
   return DVT_OK;
@@ -563,7 +471,7 @@ int dvt_add_rowtable(const void* x, const float* table, void* out, int64_t rows,
   if (rows == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
   DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((add_rowtable_kernel<T>), dim3(grid_for(rows * (d >> 3))), dim3(kBlock),
+                     hipLaunchKernelGGL((add_rowtable_kernel<T>), dim3(dvt_grid(rows * (d >> 3))), dim3(kBlock),
                                         0, st, (const T*)x, table, (T*)out, rows, d, rows_per_entry));
   DVT_LAUNCH_CHECK("dvt_add_rowtable");
   return DVT_OK;
@@ -576,7 +484,7 @@ int dvt_copy2d(const void* src, void* dst, int64_t rows, int64_t cols, int64_t s
   hipStream_t st = (hipStream_t)stream;
   const int vec = (cols % 8 == 0) && (src_ld % 8 == 0) && (dst_ld % 8 == 0) && dvt_aligned16(src) && dvt_aligned16(dst);
   DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((copy2d_kernel<T>), dim3(grid_for(rows * (vec ? cols >> 3 : cols))),
+                     hipLaunchKernelGGL((copy2d_kernel<T>), dim3(dvt_grid(rows * (vec ? cols >> 3 : cols))),
                                         dim3(kBlock), 0, st, (const T*)src, (T*)dst, rows, cols, src_ld, dst_ld, vec));
   DVT_LAUNCH_CHECK("dvt_copy2d");
   return DVT_OK;
@@ -590,7 +498,7 @@ int dvt_rows_sum(const void* src, int64_t row_stride, int64_t rows, int64_t cols
   hipStream_t st = (hipStream_t)stream;
   if (rows <= 16 && cols >= 8192) {
     DVT_DISPATCH_DTYPE(dtype, T,
-                       hipLaunchKernelGGL((few_rows_sum_kernel<T>), dim3(grid_for(cols >> 3)), dim3(kBlock), 0, st,
+                       hipLaunchKernelGGL((few_rows_sum_kernel<T>), dim3(dvt_grid(cols >> 3)), dim3(kBlock), 0, st,
                                           (const T*)src, row_stride, rows, cols >> 3, out, accumulate));
   } else {
     DVT_DISPATCH_DTYPE(dtype, T,
@@ -608,7 +516,7 @@ int dvt_permute_021(const void* src, void* dst, int64_t A, int64_t B, int64_t C,
   if (A == 0 || B == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
   DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((permute021_kernel<T>), dim3(grid_for(A * B * (C >> 3))), dim3(kBlock), 0,
+                     hipLaunchKernelGGL((permute021_kernel<T>), dim3(dvt_grid(A * B * (C >> 3))), dim3(kBlock), 0,
                                         st, (const T*)src, (T*)dst, A, B, C));
   DVT_LAUNCH_CHECK("dvt_permute_021");
   return DVT_OK;
@@ -620,7 +528,7 @@ int dvt_axpby_f32(const void* src, int src_dtype, float alpha, float* dst, float
   DVT_REQUIRE(src && dst && n >= 0, "dvt_axpby_f32: null pointer or negative size");
   hipStream_t st = (hipStream_t)stream;
   DVT_DISPATCH_DTYPE(src_dtype, T,
-                     hipLaunchKernelGGL((axpby_kernel<T>), dim3(grid_for(n)), dim3(kBlock), 0, st,
+                     hipLaunchKernelGGL((axpby_kernel<T>), dim3(dvt_grid(n)), dim3(kBlock), 0, st,
                                         (const T*)src, alpha, dst, beta, n));
   DVT_LAUNCH_CHECK("dvt_axpby_f32");
   return DVT_OK;
@@ -640,7 +548,7 @@ int dvt_tokens_assemble_fwd(const void* emb, const float* cls, const float* pos,
   hipStream_t st = (hipStream_t)stream;
   const int64_t items = S * (n + 1) * (d >> 3);
   DVT_DISPATCH_DTYPE(dtype, Tt,
-                     hipLaunchKernelGGL((tokens_fwd_kernel<Tt>), dim3(grid_for(items)), dim3(kBlock),
+                     hipLaunchKernelGGL((tokens_fwd_kernel<Tt>), dim3(dvt_grid(items)), dim3(kBlock),
                                         0, st, (const Tt*)emb, cls, pos, (Tt*)out, S, T, n, d,
                                         pos_rows));
   DVT_LAUNCH_CHECK("dvt_tokens_assemble_fwd");
@@ -660,10 +568,10 @@ int dvt_tokens_assemble_bwd(const void* dout, void* demb, float* dcls, float* dp
   DVT_DISPATCH_DTYPE(dtype, Tt, {
     const bool one_pass = demb && n > 0 && dpos;     // the positional-gradient pass reads all of dout: it writes demb as well
     if (demb && n > 0 && !one_pass)
-      hipLaunchKernelGGL((tokens_bwd_emb_kernel<Tt>), dim3(grid_for(S * n * dv)), dim3(kBlock), 0, st,
+      hipLaunchKernelGGL((tokens_bwd_emb_kernel<Tt>), dim3(dvt_grid(S * n * dv)), dim3(kBlock), 0, st,
                          (const Tt*)dout, (Tt*)demb, S, n, d);
     if (dpos)
-      hipLaunchKernelGGL((tokens_bwd_pos_kernel<Tt>), dim3(grid_for(T * pos_rows * dv)), dim3(kBlock),
+      hipLaunchKernelGGL((tokens_bwd_pos_kernel<Tt>), dim3(dvt_grid(T * pos_rows * dv)), dim3(kBlock),
                          0, st, (const Tt*)dout, dpos, S, T, n, d, pos_rows, accumulate, one_pass ? (Tt*)demb : (Tt*)nullptr);
     if (dcls)
       hipLaunchKernelGGL((strided_rows_sum_kernel<Tt>), dim3((unsigned)dv), dim3(kBlock), 0, st,
@@ -685,7 +593,7 @@ int dvt_rows_gather_fwd(const void* src, int64_t src_row_stride, const float* to
   const int lead = tok ? 1 : 0;
   const int64_t items = B * (T + lead) * (d >> 3);
   DVT_DISPATCH_DTYPE(dtype, Tt,
-                     hipLaunchKernelGGL((rows_gather_fwd_kernel<Tt>), dim3(grid_for(items)),
+                     hipLaunchKernelGGL((rows_gather_fwd_kernel<Tt>), dim3(dvt_grid(items)),
                                         dim3(kBlock), 0, st, (const Tt*)src, src_row_stride, tok,
                                         (Tt*)out, B, T, d, lead));
   DVT_LAUNCH_CHECK("dvt_rows_gather_fwd");
@@ -704,7 +612,7 @@ int dvt_rows_gather_bwd(const void* dout, void* dsrc, int64_t src_row_stride, fl
   const int64_t dv = d >> 3;
   DVT_DISPATCH_DTYPE(dtype, Tt, {
     if (T > 0)
-      hipLaunchKernelGGL((rows_gather_bwd_kernel<Tt>), dim3(grid_for(B * T * dv) + (dtok ? (unsigned)dv : 0u)), dim3(kBlock),
+      hipLaunchKernelGGL((rows_gather_bwd_kernel<Tt>), dim3(dvt_grid(B * T * dv) + (dtok ? (unsigned)dv : 0u)), dim3(kBlock),
                          0, st, (const Tt*)dout, (Tt*)dsrc, src_row_stride, B, T, d, lead, dtok, accumulate,
                          dtok ? (int)dv : 0);
     else if (dtok)
@@ -722,7 +630,7 @@ int dvt_mean_rows_fwd(const void* x, void* out, int64_t B, int64_t L, int64_t d,
   if (B == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
   DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((mean_rows_kernel<T, true>), dim3(grid_for(B * (d >> 3))), dim3(kBlock), 0,
+                     hipLaunchKernelGGL((mean_rows_kernel<T, true>), dim3(dvt_grid(B * (d >> 3))), dim3(kBlock), 0,
                                         st, (const T*)x, (T*)out, B, L, d, scale));
   DVT_LAUNCH_CHECK("dvt_mean_rows_fwd");
   return DVT_OK;
@@ -735,56 +643,9 @@ int dvt_mean_rows_bwd(const void* dout, void* dx, int64_t B, int64_t L, int64_t 
   if (B == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
   DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((mean_rows_kernel<T, false>), dim3(grid_for(B * L * (d >> 3))),
+                     hipLaunchKernelGGL((mean_rows_kernel<T, false>), dim3(dvt_grid(B * L * (d >> 3))),
                                         dim3(kBlock), 0, st, (const T*)dout, (T*)dx, B, L, d, scale));
   DVT_LAUNCH_CHECK("dvt_mean_rows_bwd");
-  return DVT_OK;
-}
-
-int dvt_bce_logits_fwd(const void* z, const float* target, float* loss, int64_t n, int dtype,
-                       dvt_stream_t stream) {
-  DVT_REQUIRE(z && target && loss && n > 0, "dvt_bce_logits_fwd: null pointer or n <= 0");
-  hipStream_t st = (hipStream_t)stream;
-  DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((bce_fwd_kernel<T>), dim3(1), dim3(kBlock), 0, st,
-                                        (const T*)z, target, loss, n));
-  DVT_LAUNCH_CHECK("dvt_bce_logits_fwd");
-  return DVT_OK;
-}
-
-int dvt_bce_logits_bwd(const void* z, const float* target, const float* gloss, void* dz, int64_t n,
-                       int dtype, dvt_stream_t stream) {
-  DVT_REQUIRE(z && target && gloss && dz && n > 0, "dvt_bce_logits_bwd: null pointer or n <= 0");
-  hipStream_t st = (hipStream_t)stream;
-  DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((bce_bwd_kernel<T>), dim3(grid_for(n)), dim3(kBlock), 0, st,
-                                        (const T*)z, target, gloss, (T*)dz, n));
-  DVT_LAUNCH_CHECK("dvt_bce_logits_bwd");
-  return DVT_OK;
-}
-
-int dvt_ce_argmax_fwd(const void* student, const void* teacher, float* loss, int64_t rows, int64_t C,
-                      int dtype, dvt_stream_t stream) {
-  DVT_REQUIRE(student && teacher && loss && rows > 0 && C > 0, "dvt_ce_argmax_fwd: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((ce_argmax_kernel<T, true>), dim3(1), dim3(kBlock), 0, st,
-                                        (const T*)student, (const T*)teacher, (const float*)nullptr,
-                                        loss, (T*)nullptr, rows, C));
-  DVT_LAUNCH_CHECK("dvt_ce_argmax_fwd");
-  return DVT_OK;
-}
-
-int dvt_ce_argmax_bwd(const void* student, const void* teacher, const float* gloss, void* dstudent,
-                      int64_t rows, int64_t C, int dtype, dvt_stream_t stream) {
-  DVT_REQUIRE(student && teacher && gloss && dstudent && rows > 0 && C > 0,
-              "dvt_ce_argmax_bwd: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((ce_argmax_kernel<T, false>), dim3(1), dim3(kBlock), 0, st,
-                                        (const T*)student, (const T*)teacher, gloss, (float*)nullptr,
-                                        (T*)dstudent, rows, C));
-  DVT_LAUNCH_CHECK("dvt_ce_argmax_bwd");
   return DVT_OK;
 }
 
@@ -796,7 +657,7 @@ int dvt_dropout(const void* x, void* y, int64_t n, float p, const uint64_t* rng_
   const double th = (double)p * 4294967296.0;
   const uint32_t threshold = th >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)(th + 0.5);
   const float scale = 1.0f / (1.0f - p);
-  DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((dropout_kernel<T>), dim3(grid_for((n + 3) >> 2)), dim3(kBlock), 0,
+  DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((dropout_kernel<T>), dim3(dvt_grid((n + 3) >> 2)), dim3(kBlock), 0,
                                                   (hipStream_t)stream, (const T*)x, (T*)y, n, threshold, scale, rng_state,
                                                   call_offset));
   DVT_LAUNCH_CHECK("dvt_dropout");
@@ -811,7 +672,7 @@ int dvt_dropout_fused(const void* x, const void* residual, const void* gate, voi
   const double th = (double)p * 4294967296.0;
   const uint32_t threshold = th >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)(th + 0.5);
   const float scale = 1.0f / (1.0f - p);
-  DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((dropout_fused_kernel<T>), dim3(grid_for((n + 3) >> 2)), dim3(kBlock), 0,
+  DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((dropout_fused_kernel<T>), dim3(dvt_grid((n + 3) >> 2)), dim3(kBlock), 0,
                                                   (hipStream_t)stream, (const T*)x, (const T*)residual, (const T*)gate, (T*)y, n,
                                                   threshold, scale, rng_state, call_offset, relu));
   DVT_LAUNCH_CHECK("dvt_dropout_fused");

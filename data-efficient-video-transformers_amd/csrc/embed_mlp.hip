@@ -4,7 +4,6 @@
 // The GEMMs of both stay on dvt_gemm (bias and ReLU in its epilogues, ReLU' in the data-gradient epilogue); what is here:
 //   - BatchNorm1d that READS A RECTIFIED TENSOR (Linear -> ReLU -> BatchNorm1d, contrastivemodel.py:28-30 and
 //     basicmlp.py:35), forward and backward, over S = 1 or 2 row segments ("views") that keep their own batch statistics;
-//   - log-softmax + NLL over integer labels (nn.CrossEntropyLoss(), basicmlp.py:38);
 //   - the gather that turns a list-of-lists expert batch into one [rows, D] input.
 //
 // Reductions run in a fixed order with no atomics: two identical calls give bitwise-equal results.
@@ -134,79 +133,6 @@ __global__ __launch_bounds__(kBnThreads) void bn1d_relu_bwd_kernel(
   }
 }
 
-constexpr int kCeWaves = 16;
-
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = DVT_WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_add(float v) {
-  for (int o = DVT_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// One workgroup: wave w takes rows w, w + 16, ...; per row the log-sum-exp (max, then sum of exp, each butterfly-reduced:
-// the same order on every call), its NLL term summed by the wave in row order, the 16 wave sums in wave order.
-// lse[M] = number of counted rows.  A label outside [0, C) (and not ignore_index) reads class 0 and makes the loss NaN.
-template <typename T>
-__global__ __launch_bounds__(kCeWaves * DVT_WAVE) void ce_labels_fwd_kernel(const T* __restrict__ x, int64_t ld,
-                                                                             const int64_t* __restrict__ labels,
-                                                                             float* __restrict__ loss,
-                                                                             float* __restrict__ lse, int64_t M, int64_t C,
-                                                                             int64_t ignore) {
-  __shared__ float part[kCeWaves];
-  __shared__ int cnt[kCeWaves];
-  const int lane = threadIdx.x % DVT_WAVE, wv = threadIdx.x / DVT_WAVE;
-  float acc = 0.f;
-  int n = 0;
-  for (int64_t r = wv; r < M; r += kCeWaves) {
-    const T* row = x + r * ld;
-    float mx = -INFINITY;
-    for (int64_t c = lane; c < C; c += DVT_WAVE) mx = fmaxf(mx, ldf(row + c));
-    mx = wave_max(mx);
-    float se = 0.f;
-    for (int64_t c = lane; c < C; c += DVT_WAVE) se += expf(ldf(row + c) - mx);
-    se = wave_add(se);
-    const float l = mx + logf(se);
-    if (lane == 0) lse[r] = l;
-    const int64_t y = labels[r];
-    if (y == ignore) continue;
-    const bool bad = y < 0 || y >= C;
-    const float xy = ldf(row + (bad ? 0 : y));
-    acc += bad ? NAN : (l - xy);
-    ++n;
-  }
-  if (lane == 0) { part[wv] = acc; cnt[wv] = n; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    int k = 0;
-    for (int w = 0; w < kCeWaves; ++w) { s += part[w]; k += cnt[w]; }
-    loss[0] = s / (float)k;                              // k == 0: NaN, as torch's mean over no rows
-    lse[M] = (float)k;
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void ce_labels_bwd_kernel(const T* __restrict__ x, int64_t ld,
-                                                            const int64_t* __restrict__ labels,
-                                                            const float* __restrict__ lse, const float* __restrict__ gloss,
-                                                            T* __restrict__ dx, int64_t lddx, int64_t M, int64_t C,
-                                                            int64_t ignore) {
-  const int64_t r = blockIdx.x;
-  const int64_t y = labels[r];
-  const T* row = x + r * ld;
-  T* drow = dx + r * lddx;
-  const float scale = gloss[0] / lse[M];
-  const bool skip = y == ignore, bad = y < 0 || y >= C;
-  const float l = lse[r];
-  for (int64_t c = threadIdx.x; c < C; c += blockDim.x) {
-    float d = 0.f;
-    if (!skip) d = bad ? NAN : scale * (expf(ldf(row + c) - l) - (c == y ? 1.f : 0.f));
-    stf(drow + c, d);
-  }
-}
-
 // out[r, :] = cat_j src_j (cast to the output dtype); entry (r, j) of the table: {address, width, dtype}.
 template <typename T>
 __global__ __launch_bounds__(256) void gather_rows_ptr_kernel(const int64_t* __restrict__ table, int parts,
@@ -282,32 +208,6 @@ int dvt_bn1d_relu_bwd(const void* dy, int64_t lddy, const void* z, int64_t ldz, 
                                         ldz, gamma, save_mean, save_invstd, (T*)dz, lddz, dgamma, dbeta, accumulate, B, C,
                                         S, training));
   DVT_LAUNCH_CHECK("dvt_bn1d_relu_bwd");
-  return DVT_OK;
-}
-
-int dvt_ce_labels_fwd(const void* logits, int64_t ld, const int64_t* labels, float* loss, float* lse, int64_t M, int64_t C,
-                      int64_t ignore_index, int dtype, dvt_stream_t stream) {
-  DVT_REQUIRE(logits && labels && loss && lse && M >= 1 && C >= 1 && ld >= C && (dtype == DVT_F32 || dvt_is_16bit(dtype)),
-              "dvt_ce_labels_fwd: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((ce_labels_fwd_kernel<T>), dim3(1), dim3(kCeWaves * DVT_WAVE), 0, st,
-                                        (const T*)logits, ld, labels, loss, lse, M, C, ignore_index));
-  DVT_LAUNCH_CHECK("dvt_ce_labels_fwd");
-  return DVT_OK;
-}
-
-int dvt_ce_labels_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* lse, const float* gloss,
-                      void* dlogits, int64_t lddl, int64_t M, int64_t C, int64_t ignore_index, int dtype,
-                      dvt_stream_t stream) {
-  DVT_REQUIRE(logits && labels && lse && gloss && dlogits && M >= 1 && C >= 1 && ld >= C && lddl >= C &&
-                  (dtype == DVT_F32 || dvt_is_16bit(dtype)),
-              "dvt_ce_labels_bwd: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((ce_labels_bwd_kernel<T>), dim3((unsigned)M), dim3(256), 0, st, (const T*)logits,
-                                        ld, labels, lse, gloss, (T*)dlogits, lddl, M, C, ignore_index));
-  DVT_LAUNCH_CHECK("dvt_ce_labels_bwd");
   return DVT_OK;
 }
 

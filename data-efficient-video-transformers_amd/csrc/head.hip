@@ -9,6 +9,7 @@
 // column-owner threads from per-row vectors parked in the workspace.  The gradients are those of an upstream gradient of
 // 1; backward is the scaled store below (the loss scale / 1 / world factor arrives as a device scalar).
 #include "common.h"
+#include "loss_terms.h"
 
 namespace {
 
@@ -142,11 +143,11 @@ __global__ __launch_bounds__(512) void head_bce_kernel(const dvt_head_bce_desc p
       zmine = lane == c ? z : zmine;
     }
     // ---- BCE on lanes < C, dz through LDS to the whole wave
-    float term = fmaxf(zmine, 0.f) - zmine * tgt + log1pf(expf(-fabsf(zmine)));
+    float term = bce_logits_term(zmine, tgt);
     term = lane < C ? term : 0.f;
     if (lane < C && live) {
       p.logits[(int64_t)r * C + lane] = zmine;
-      s_dz[r * kHeadMaxC + lane] = gsc * (1.0f / (1.0f + expf(-zmine)) - tgt);
+      s_dz[r * kHeadMaxC + lane] = gsc * bce_logits_grad(sigmoidf_(zmine), tgt);
     }
     const float tsum = wave_sum_dpp(term);
     loss_acc += live ? tsum : 0.f;

@@ -1,5 +1,4 @@
-// lstm.hip -- the recurrent chain of nn.LSTM(batch_first=True) (src/models/LSTM.py:32-38 forward, :40-45 its use) and the
-// sigmoid -> nn.BCELoss() criterion of LSTMRegressor.training_step (LSTM.py:55-57).
+// lstm.hip -- the recurrent chain of nn.LSTM(batch_first=True) (src/models/LSTM.py:32-38 forward, :40-45 its use).
 //
 // One layer over a whole sequence is T dependent steps.  The input projection x W_ih^T of every step is one large GEMM
 // done before the chain (dvt_gemm), and the weight / bias / input gradients are large GEMMs done after the backward chain;
@@ -66,8 +65,6 @@ __device__ __forceinline__ f32x4 mma(const Frag<float>& a, const Frag<float>& b,
   for (int j = 0; j < 8; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], c, 0, 0, 0);
   return c;
 }
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // Step t of the forward chain.  G [B, T, 4H] = x W_ih^T (no bias); b_ih, b_hh [4H] f32 (nullable); whh [4H, H];
 // hprev [B, T, H]: hprev[:, t] = h_{t-1} (the step reads it; it writes h_t to hprev[:, t + 1] and the zero h_{-1} at t = 0);
@@ -209,40 +206,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(const T* __restrict__ sr
   }
 }
 
-// nn.BCELoss()(sigmoid(z), y), mean over n, each log term clamped at -100 as torch does; p = sigmoid(z) in fp32.
-// One workgroup, per-thread partials summed in a fixed tree: bitwise reproducible.
-template <typename T>
-__global__ __launch_bounds__(256) void sigmoid_bce_fwd_kernel(const T* __restrict__ z, const float* __restrict__ y,
-                                                             float* __restrict__ loss, float* __restrict__ prob, int64_t n) {
-  __shared__ float part[256];
-  float acc = 0.f;
-  for (int64_t i = threadIdx.x; i < n; i += 256) {
-    const float p = sigmoidf_(to_f32<T>(z[i]));
-    if (prob) prob[i] = p;
-    const float yi = y[i];
-    acc += (yi - 1.f) * fmaxf(log1pf(-p), -100.f) - yi * fmaxf(logf(p), -100.f);
-  }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = part[0] / (float)n;
-}
-
-// dz = gloss / n * (p - y) / max(p (1 - p), 1e-12) * p (1 - p): BCELoss's backward, then sigmoid's, as torch evaluates them.
-template <typename T>
-__global__ __launch_bounds__(256) void sigmoid_bce_bwd_kernel(const T* __restrict__ z, const float* __restrict__ y,
-                                                             const float* __restrict__ gloss, T* __restrict__ dz, int64_t n) {
-  const float g = gloss[0] / (float)n;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float p = sigmoidf_(to_f32<T>(z[i]));
-    const float dp = g * (p - y[i]) / fmaxf((1.f - p) * p, 1e-12f);
-    dz[i] = from_f32<T>(dp * ((1.f - p) * p));
-  }
-}
-
 int lstm_check(const char* fn, int64_t B, int64_t T, int64_t H, int dtype) {
   DVT_REQUIRE(B > 0 && T > 0 && H > 0, "%s: B, T, H must be positive (got %lld, %lld, %lld)", fn, (long long)B,
               (long long)T, (long long)H);
@@ -302,28 +265,5 @@ int dvt_lstm_seq_bwd(const void* w_hh, const float* gates, const float* c, const
       DVT_LAUNCH_CHECK("dvt_lstm_seq_bwd");
     }
   });
-  return DVT_OK;
-}
-
-int dvt_sigmoid_bce_fwd(const void* z, const float* target, float* loss, float* prob, int64_t n, int dtype,
-                        dvt_stream_t stream) {
-  DVT_REQUIRE(z && target && loss && n > 0, "dvt_sigmoid_bce_fwd: null pointer or n <= 0");
-  hipStream_t st = (hipStream_t)stream;
-  DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((sigmoid_bce_fwd_kernel<T>), dim3(1), dim3(256), 0, st, (const T*)z, target, loss,
-                                        prob, n));
-  DVT_LAUNCH_CHECK("dvt_sigmoid_bce_fwd");
-  return DVT_OK;
-}
-
-int dvt_sigmoid_bce_bwd(const void* z, const float* target, const float* gloss, void* dz, int64_t n, int dtype,
-                        dvt_stream_t stream) {
-  DVT_REQUIRE(z && target && gloss && dz && n > 0, "dvt_sigmoid_bce_bwd: null pointer or n <= 0");
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned blocks = (unsigned)(dvt_cdiv(n, 256) < 1024 ? dvt_cdiv(n, 256) : 1024);
-  DVT_DISPATCH_DTYPE(dtype, T,
-                     hipLaunchKernelGGL((sigmoid_bce_bwd_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)z, target,
-                                        gloss, (T*)dz, n));
-  DVT_LAUNCH_CHECK("dvt_sigmoid_bce_bwd");
   return DVT_OK;
 }

@@ -13,14 +13,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-inline int grid_for(int64_t work_items) {
-  int64_t blocks = dvt_cdiv(work_items, kBlock);
-  int64_t cap = (int64_t)dvt_num_cus() * 8;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
 // 1 - b1^t and sqrt(1 - b2^t).  Two ways to fill it that round differently and stay apart: dvt_adamw_step computes the
 // pair from its host step in double, every device-counter kernel with bias_corr_dev in float.
 struct BiasCorr {
@@ -596,7 +588,7 @@ int dvt_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
   hipStream_t st = (hipStream_t)stream;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, param, grad, exp_avg,
+  hipLaunchKernelGGL(adamw_kernel, dim3(dvt_grid(n)), dim3(kBlock), 0, st, param, grad, exp_avg,
                      exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, (float)bc1,
                      (float)sqrt(bc2));
   DVT_LAUNCH_CHECK("dvt_adamw_step");
@@ -609,7 +601,7 @@ int dvt_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* e
   if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
   DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && step_dev && n >= 0, "dvt_adamw_step_dev: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(adamw_dev_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, param, grad, exp_avg,
+  hipLaunchKernelGGL(adamw_dev_kernel, dim3(dvt_grid(n)), dim3(kBlock), 0, st, param, grad, exp_avg,
                      exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, (const int64_t*)step_dev, skip64);
   hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, st, step_dev);
   DVT_LAUNCH_CHECK("dvt_adamw_step_dev");
@@ -626,7 +618,7 @@ int dvt_adamw_step_fused(float* param, const float* grad, float* exp_avg, float*
   DVT_REQUIRE(!mirror || (dvt_is_16bit(mirror_dtype) && ((uintptr_t)mirror & 7u) == 0),
               "dvt_adamw_step_fused: mirror must be bf16 / f16 and 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(grid_for((n >> 2) + 1)), block(256);
+  const dim3 grid(dvt_grid((n >> 2) + 1)), block(256);
   DVT_LAUNCH_MIRRORED(adamw_fused_kernel, mirror, mirror_dtype, grid, block, st, param, grad, exp_avg, exp_avg_sq, n, lr,
                       beta1, beta2, eps, weight_decay, step_dev2, skip64);
   DVT_LAUNCH_CHECK("dvt_adamw_step_fused");
@@ -642,8 +634,8 @@ int dvt_adamw_step_scaled(float* param, const float* grad, float* exp_avg, float
               "dvt_adamw_step_scaled: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   if (n > 0) {
-    hipLaunchKernelGGL(check_finite_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, grad, n, (int*)found_inf);
-    hipLaunchKernelGGL(adamw_scaled_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, param, grad, exp_avg, exp_avg_sq, n,
+    hipLaunchKernelGGL(check_finite_kernel, dim3(dvt_grid(n)), dim3(kBlock), 0, st, grad, n, (int*)found_inf);
+    hipLaunchKernelGGL(adamw_scaled_kernel, dim3(dvt_grid(n)), dim3(kBlock), 0, st, param, grad, exp_avg, exp_avg_sq, n,
                        lr, beta1, beta2, eps, weight_decay, (const int64_t*)step_dev, (const float*)scale,
                        (const int*)found_inf, skip64);
   }
@@ -672,7 +664,7 @@ int dvt_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n
                  float weight_decay, const uint8_t* skip64, dvt_stream_t stream) {
   if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
   DVT_REQUIRE(param && grad && n >= 0 && (momentum == 0.f || momentum_buf), "dvt_sgd_step: bad arguments");
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, param, grad, momentum_buf,
+  hipLaunchKernelGGL(sgd_kernel, dim3(dvt_grid(n)), dim3(kBlock), 0, (hipStream_t)stream, param, grad, momentum_buf,
                      n, lr, momentum, weight_decay, skip64);
   DVT_LAUNCH_CHECK("dvt_sgd_step");
   return DVT_OK;
@@ -683,7 +675,7 @@ int dvt_adagrad_step(float* param, const float* grad, float* state_sum, int64_t 
   if (n == 0) return DVT_OK;   // empty tensors carry null pointers: nothing to validate, nothing to launch
   DVT_REQUIRE(param && grad && state_sum && n >= 0 && step >= 1, "dvt_adagrad_step: bad arguments");
   const float clr = (float)((double)lr / (1.0 + (double)(step - 1) * (double)lr_decay));
-  hipLaunchKernelGGL(adagrad_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, param, grad, state_sum,
+  hipLaunchKernelGGL(adagrad_kernel, dim3(dvt_grid(n)), dim3(kBlock), 0, (hipStream_t)stream, param, grad, state_sum,
                      n, clr, eps, weight_decay, skip64);
   DVT_LAUNCH_CHECK("dvt_adagrad_step");
   return DVT_OK;

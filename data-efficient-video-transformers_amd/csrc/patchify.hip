@@ -43,14 +43,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-inline int patchify_grid(int64_t work_items) {
-  int64_t blocks = dvt_cdiv(work_items, kBlock);
-  const int64_t cap = (int64_t)dvt_num_cus() * 8;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
 // const T* when the kernel reads the tensor, T* when it writes it
 template <bool READS, typename T> using ptr_t = typename std::conditional<READS, const T*, T*>::type;
 
@@ -250,15 +242,15 @@ int patchify_dispatch(ptr_t<FWD, void> pix, ptr_t<!FWD, void> vec, int64_t frame
     }
   }
   if (vec_ok && P == 16 && C == 3) {
-    hipLaunchKernelGGL((patchify_vec_kernel<16, 3, S, D, FWD>), dim3(patchify_grid(items)), dim3(kBlock), 0, st, pixp, vecp,
+    hipLaunchKernelGGL((patchify_vec_kernel<16, 3, S, D, FWD>), dim3(dvt_grid(items)), dim3(kBlock), 0, st, pixp, vecp,
                        frames, H, W, pt);
   } else if (vec_ok && P == 8 && C == 3) {
-    hipLaunchKernelGGL((patchify_vec_kernel<8, 3, S, D, FWD>), dim3(patchify_grid(items)), dim3(kBlock), 0, st, pixp, vecp,
+    hipLaunchKernelGGL((patchify_vec_kernel<8, 3, S, D, FWD>), dim3(dvt_grid(items)), dim3(kBlock), 0, st, pixp, vecp,
                        frames, H, W, pt);
   } else {
     if ((int64_t)P * P * C * pt >= ((int64_t)1 << 31)) DVT_UNSUPPORTED("%s: a row of pt*P*P*C >= 2^31 elements", name);
     const int64_t rows = frames / pt * nh * nw;
-    hipLaunchKernelGGL((patchify_scalar_kernel<S, D, FWD>), dim3(patchify_grid(rows * kBlock)), dim3(kBlock), 0, st, pixp, vecp,
+    hipLaunchKernelGGL((patchify_scalar_kernel<S, D, FWD>), dim3(dvt_grid(rows * kBlock)), dim3(kBlock), 0, st, pixp, vecp,
                        rows, C, H, W, P, pt);
   }
   DVT_LAUNCH_CHECK(name);

@@ -20,6 +20,7 @@
 //
 // Every reduction runs in a fixed order: two identical calls from the same state give bitwise-equal results.
 #include "common.h"
+#include "loss_terms.h"
 
 #include <type_traits>
 
@@ -253,14 +254,11 @@ __global__ __launch_bounds__(kLossThreads) void probe_loss_kernel(dvt_probe_desc
     lg += a.b2[i % C];
     if (a.logits) a.logits[i] = lg;
     if (!a.target) continue;
-    const float p = 1.0f / (1.0f + expf(-lg));
+    const float p = sigmoidf_(lg);
     const float y = a.target[i];
     a.prob[i] = p;
-    acc += (y - 1.f) * fmaxf(log1pf(-p), -100.f) - y * fmaxf(logf(p), -100.f);
-    if (a.training) {
-      const float dp = gscale * (p - y) / fmaxf((1.f - p) * p, 1e-12f);       // BCELoss's backward, then sigmoid's
-      a.dlogits[i] = dp * ((1.f - p) * p);
-    }
+    acc += bce_clamped_term(p, y);
+    if (a.training) a.dlogits[i] = bce_clamped_grad_logit(p, y, gscale);
   }
   red[t] = acc;
   __syncthreads();

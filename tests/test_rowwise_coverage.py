@@ -46,23 +46,23 @@ TEMPLATES = [
     ("elementwise.hip", "rows_gather_bwd_kernel<{T}>", "test_gpu_rowwise::test_rows_gather[{n}-1]"),
     ("elementwise.hip", "mean_rows_kernel<{T}, true>", "test_gpu_rowwise::test_mean_rows[{n}]"),
     ("elementwise.hip", "mean_rows_kernel<{T}, false>", "test_gpu_rowwise::test_mean_rows[{n}]"),
-    ("elementwise.hip", "bce_fwd_kernel<{T}>", "test_gpu_rowwise::test_bce_logits[{n}]"),
-    ("elementwise.hip", "bce_bwd_kernel<{T}>", "test_gpu_rowwise::test_bce_logits[{n}]"),
-    ("elementwise.hip", "ce_argmax_kernel<{T}, true>", "test_gpu_rowwise::test_ce_argmax[{n}]"),
-    ("elementwise.hip", "ce_argmax_kernel<{T}, false>", "test_gpu_rowwise::test_ce_argmax[{n}]"),
+    ("losses.hip", "bce_fwd_kernel<{T}>", "test_gpu_rowwise::test_bce_logits[{n}]"),
+    ("losses.hip", "bce_bwd_kernel<{T}>", "test_gpu_rowwise::test_bce_logits[{n}]"),
+    ("losses.hip", "ce_argmax_kernel<{T}, true>", "test_gpu_rowwise::test_ce_argmax[{n}]"),
+    ("losses.hip", "ce_argmax_kernel<{T}, false>", "test_gpu_rowwise::test_ce_argmax[{n}]"),
     ("lstm.hip", "lstm_step_fwd_kernel<{T}>", "test_gpu_lstm::test_forward_step_k_loop_sums_every_group_once[{l}]"),
     ("lstm.hip", "lstm_step_bwd_kernel<{T}>", "test_gpu_lstm::test_lstm_seq_fwd_bwd_direct[{l}-both]"),
     ("lstm.hip", "transpose_kernel<{T}>", "test_gpu_lstm::test_lstm_seq_fwd_bwd_direct[{l}-both]"),
-    ("lstm.hip", "sigmoid_bce_fwd_kernel<{T}>", "test_gpu_rowwise::test_sigmoid_bce[{n}]"),
-    ("lstm.hip", "sigmoid_bce_bwd_kernel<{T}>", "test_gpu_rowwise::test_sigmoid_bce[{n}]"),
+    ("losses.hip", "sigmoid_bce_fwd_kernel<{T}>", "test_gpu_rowwise::test_sigmoid_bce[{n}]"),
+    ("losses.hip", "sigmoid_bce_bwd_kernel<{T}>", "test_gpu_rowwise::test_sigmoid_bce[{n}]"),
     ("conv.hip", "transpose_kernel<{T}>", "test_gpu_rowwise::test_transpose_last2[{n}]"),
 ]
 
 COVERAGE = {(f, k.format(T=_T[n])): c.format(n=n, l=_LSTM_ID[n], o=_OPS_ID[n]) for f, k, c in TEMPLATES for n in _T}
 COVERAGE.update({
-    ("fusion_ssl.hip", "contrastive_rows_fwd_kernel"): "test_gpu_rowwise::test_contrastive_rows[0.1]",
-    ("fusion_ssl.hip", "contrastive_rows_bwd_kernel"): "test_gpu_rowwise::test_contrastive_rows[0.1]",
-    ("fusion_ssl.hip", "mean_kernel"): "test_gpu_rowwise::test_contrastive_rows[0.5]",
+    ("losses.hip", "contrastive_rows_fwd_kernel"): "test_gpu_rowwise::test_contrastive_rows[0.1]",
+    ("losses.hip", "contrastive_rows_bwd_kernel"): "test_gpu_rowwise::test_contrastive_rows[0.1]",
+    ("losses.hip", "mean_kernel"): "test_gpu_rowwise::test_contrastive_rows[0.5]",
 })
 COVERAGE.update({("elementwise.hip", f"cast_kernel<{_T[s]}, {_T[d]}>"): f"test_gpu_rowwise::test_cast[{s}-{d}]"
                  for s, d in (("fp32", "bf16"), ("fp32", "fp16"), ("bf16", "fp32"), ("fp16", "fp32"), ("fp32", "fp32"),
@@ -77,13 +77,16 @@ SCOPE = {
     "elementwise.hip": {"cast_kernel", "add_kernel", "add_rowtable_kernel", "copy2d_kernel", "permute021_kernel", "axpby_kernel",
                         "act_kernel", "tokens_fwd_kernel", "tokens_bwd_emb_kernel", "tokens_bwd_pos_kernel",
                         "strided_rows_sum_kernel", "few_rows_sum_kernel", "rows_gather_fwd_kernel", "rows_gather_bwd_kernel",
-                        "mean_rows_kernel", "bce_fwd_kernel", "bce_bwd_kernel", "ce_argmax_kernel"},
-    "lstm.hip": {"lstm_step_fwd_kernel", "lstm_step_bwd_kernel", "transpose_kernel", "sigmoid_bce_fwd_kernel",
-                 "sigmoid_bce_bwd_kernel"},
+                        "mean_rows_kernel"},
+    "lstm.hip": {"lstm_step_fwd_kernel", "lstm_step_bwd_kernel", "transpose_kernel"},
+    "losses.hip": {"bce_fwd_kernel", "bce_bwd_kernel", "ce_argmax_kernel", "sigmoid_bce_fwd_kernel", "sigmoid_bce_bwd_kernel",
+                   "contrastive_rows_fwd_kernel", "contrastive_rows_bwd_kernel", "mean_kernel"},
     "conv.hip": {"transpose_kernel"},
 }
 # the other kernels of elementwise.hip have tests of their own in tests/test_gpu_ops.py (dropout)
 ELEMENTWISE_ELSEWHERE = {"dropout_kernel", "dropout_fused_kernel", "rng_advance_kernel"}
+# the other kernels of losses.hip have a test of their own: test_gpu_contrastive::test_cross_entropy_against_torch
+LOSSES_ELSEWHERE = {"ce_labels_fwd_kernel", "ce_labels_bwd_kernel"}
 
 _GLOBAL = re.compile(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", re.S)
 
@@ -152,6 +155,7 @@ def test_scope_accounts_for_every_kernel_of_its_files():
     where = _defined_in()
     assert where["transpose_kernel"] == {"lstm.hip", "conv.hip"}
     assert {k for k, fs in where.items() if "elementwise.hip" in fs} == SCOPE["elementwise.hip"] | ELEMENTWISE_ELSEWHERE
+    assert {k for k, fs in where.items() if "losses.hip" in fs} == SCOPE["losses.hip"] | LOSSES_ELSEWHERE
     for f, names in SCOPE.items():
         for k in names or ():
             assert f in where.get(k, ()), f"{f} defines no kernel {k}"
