@@ -629,8 +629,9 @@ int dvt_adamw_step_scaled(float* param, const float* grad, float* exp_avg, float
                           float beta1, float beta2, float eps, float weight_decay, int64_t* step_dev, float* scale,
                           int32_t* found_inf, int32_t* good_steps, int growth_interval, float growth, float backoff,
                           float* loss_grad, float loss_grad_base, const uint8_t* skip64, dvt_stream_t stream) {
-  DVT_REQUIRE(param && grad && exp_avg && exp_avg_sq && step_dev && scale && found_inf && good_steps && loss_grad &&
-                  n >= 0 && growth_interval > 0 && growth >= 1.f && backoff > 0.f && backoff <= 1.f,
+  // empty tensors carry null pointers: the scaler state still moves (a clean step), nothing else is launched
+  DVT_REQUIRE((n == 0 || (param && grad && exp_avg && exp_avg_sq)) && step_dev && scale && found_inf && good_steps &&
+                  loss_grad && n >= 0 && growth_interval > 0 && growth >= 1.f && backoff > 0.f && backoff <= 1.f,
               "dvt_adamw_step_scaled: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   if (n > 0) {

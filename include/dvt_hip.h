@@ -1082,7 +1082,8 @@ int dvt_adamw_step_fused(float* param, const float* grad, float* exp_avg, float*
  * grad holds the gradient of (scale * loss).  On the device, in stream order: found_inf |= any non-finite grad;
  * unless found_inf: the dvt_adamw_step_dev update with grad / scale and step_dev += 1; then
  * found_inf ? scale *= backoff : (every growth_interval clean steps: scale *= growth); found_inf = 0;
- * loss_grad[0] = scale * loss_grad_base (the seed of the next backward, e.g. base = 1 / world).  No host sync. */
+ * loss_grad[0] = scale * loss_grad_base (the seed of the next backward, e.g. base = 1 / world).  No host sync.
+ * n == 0: the four tensors may be NULL; the scaler state alone moves, as after a clean step. */
 int dvt_adamw_step_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                           float beta1, float beta2, float eps, float weight_decay, int64_t* step_dev, float* scale,
                           int32_t* found_inf, int32_t* good_steps, int growth_interval, float growth, float backoff,
