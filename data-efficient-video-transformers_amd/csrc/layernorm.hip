@@ -365,10 +365,10 @@ int dvt_layernorm_bwd_ex(const dvt_ln_bwd_desc* q, dvt_stream_t stream) {
 int dvt_layernorm_reduce_group(const dvt_ln_pending* list, int count, dvt_stream_t stream) {
   DVT_REQUIRE(count >= 0 && (count == 0 || list), "dvt_layernorm_reduce_group: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  for (int base = 0; base < count; base += kLnGroup) {
-    LnGroup grp{};
+  for (int i = 0; i < count;) {                    // (i runs on across launches: a skipped entry must not make the next
+    LnGroup grp{};                                 // launch start inside the span this one has already taken)
     int n = 0, dmax = 0;
-    for (int i = base; i < count && n < kLnGroup; ++i) {
+    for (; i < count && n < kLnGroup; ++i) {
       if (!list[i].valid) continue;
       DVT_REQUIRE(list[i].partial && list[i].dgamma && list[i].dbeta && list[i].nparts > 0 && list[i].d > 0,
                   "dvt_layernorm_reduce_group: bad entry");

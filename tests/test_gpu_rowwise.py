@@ -4,19 +4,18 @@ is the float64 result rounded to the dtype or a neighbouring value), at edge sha
 
 Every output a wrapper allocates is, for the duration of the call, a view into a larger NaN-filled buffer (``guarded``
 stands in for torch.empty / torch.empty_like inside ops): the bands before and after must still be NaN afterwards, and no
-NaN may be left inside.  Destinations the caller owns get the same bands from ``poisoned``."""
-import contextlib
+NaN may be left inside.  Destinations the caller owns get the same bands from ``poisoned`` (both of tests/guards.py)."""
 import math
 
 import pytest
 import torch
 
 from tests import rowwise_ref as R
+from tests.guards import guarded, poisoned
 
 pytestmark = pytest.mark.gpu
 
 DT = ["fp32", "bf16", "fp16"]
-GUARD = 64                                    # elements on each side: a multiple of 16 bytes in every dtype
 ROWS = [1, 3, 4, 5, 9]                        # four rows per workgroup: a part block, a whole one, one more than whole
 DS = [1, 7, 63, 64, 65, 200]                  # lanes stride by 64
 NS = [1, 7, 8, 9, 255, 257, 2051]
@@ -27,57 +26,6 @@ def dvt(device):
     import dvt_amd
     dvt_amd._lib.load()
     return dvt_amd
-
-
-class _GuardedTorch:
-    """torch, except that empty / empty_like hand out the middle of a NaN-filled buffer"""
-
-    def __init__(self):
-        self.live = []
-
-    def __getattr__(self, name):
-        return getattr(torch, name)
-
-    def empty(self, *shape, dtype=None, device=None, **kw):
-        if len(shape) == 1 and isinstance(shape[0], (tuple, list, torch.Size)):
-            shape = tuple(shape[0])
-        if dtype is None or not dtype.is_floating_point or device is None or torch.device(device).type != "cuda":
-            return torch.empty(shape, dtype=dtype, device=device, **kw)
-        n = math.prod(shape)
-        buf = torch.full((n + 2 * GUARD,), math.nan, dtype=dtype, device=device)
-        self.live.append((buf, n))
-        return buf[GUARD:GUARD + n].view(shape)
-
-    def empty_like(self, t, **kw):
-        return self.empty(tuple(t.shape), dtype=kw.get("dtype", t.dtype), device=t.device)
-
-    def check(self):
-        assert self.live, "the call allocated no output"
-        for buf, n in self.live:
-            assert bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[GUARD + n:]).all()), "a guard band was written"
-
-
-@contextlib.contextmanager
-def guarded(ops):
-    g = _GuardedTorch()
-    ops.torch = g
-    try:
-        yield g
-    finally:
-        ops.torch = torch
-    g.check()
-
-
-def poisoned(shape, dtype, device, fill=math.nan):
-    """(view, check): a caller-owned destination inside NaN bands; the view itself starts as ``fill``"""
-    n = math.prod(shape)
-    buf = torch.full((n + 2 * GUARD,), math.nan, dtype=dtype, device=device)
-    view = buf[GUARD:GUARD + n].view(shape)
-    view.fill_(fill)
-
-    def check():
-        assert bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[GUARD + n:]).all()), "a guard band was written"
-    return view, check
 
 
 def _gen(seed):

@@ -1,6 +1,7 @@
 """CPU gate on the direct tests of the row, gating, loss, data-movement and LSTM-step kernels: every kernel symbol of those
-families in the built library is tied to a named GPU case of tests/test_gpu_rowwise.py, tests/test_gpu_lstm.py or (cast,
-add, token assembly, rows_sum) tests/test_gpu_ops.py whose dtype is the symbol's element type, or is listed as unreachable
+families in the built library is tied to a named GPU case of tests/test_gpu_rowwise.py, tests/test_gpu_lstm.py,
+tests/test_gpu_layernorm.py (the cross-entropy on integer labels) or (cast, add, token assembly, rows_sum)
+tests/test_gpu_ops.py whose dtype is the symbol's element type, or is listed as unreachable
 through ops with a reason.  Only the names of the listing are read.
 
 A kernel name is attributed to the csrc file that defines it, so the two ``transpose_kernel`` templates (one in an
@@ -56,6 +57,8 @@ TEMPLATES = [
     ("losses.hip", "sigmoid_bce_fwd_kernel<{T}>", "test_gpu_rowwise::test_sigmoid_bce[{n}]"),
     ("losses.hip", "sigmoid_bce_bwd_kernel<{T}>", "test_gpu_rowwise::test_sigmoid_bce[{n}]"),
     ("conv.hip", "transpose_kernel<{T}>", "test_gpu_rowwise::test_transpose_last2[{n}]"),
+    ("losses.hip", "ce_labels_fwd_kernel<{T}>", "test_gpu_layernorm::test_ce_labels[{n}]"),
+    ("losses.hip", "ce_labels_bwd_kernel<{T}>", "test_gpu_layernorm::test_ce_labels[{n}]"),
 ]
 
 COVERAGE = {(f, k.format(T=_T[n])): c.format(n=n, l=_LSTM_ID[n], o=_OPS_ID[n]) for f, k, c in TEMPLATES for n in _T}
@@ -80,13 +83,14 @@ SCOPE = {
                         "mean_rows_kernel"},
     "lstm.hip": {"lstm_step_fwd_kernel", "lstm_step_bwd_kernel", "transpose_kernel"},
     "losses.hip": {"bce_fwd_kernel", "bce_bwd_kernel", "ce_argmax_kernel", "sigmoid_bce_fwd_kernel", "sigmoid_bce_bwd_kernel",
-                   "contrastive_rows_fwd_kernel", "contrastive_rows_bwd_kernel", "mean_kernel"},
+                   "contrastive_rows_fwd_kernel", "contrastive_rows_bwd_kernel", "mean_kernel", "ce_labels_fwd_kernel",
+                   "ce_labels_bwd_kernel"},
     "conv.hip": {"transpose_kernel"},
 }
 # the other kernels of elementwise.hip have tests of their own in tests/test_gpu_ops.py (dropout)
 ELEMENTWISE_ELSEWHERE = {"dropout_kernel", "dropout_fused_kernel", "rng_advance_kernel"}
-# the other kernels of losses.hip have a test of their own: test_gpu_contrastive::test_cross_entropy_against_torch
-LOSSES_ELSEWHERE = {"ce_labels_fwd_kernel", "ce_labels_bwd_kernel"}
+# every kernel of losses.hip is in scope (the cross-entropy on integer labels: the cases of tests/test_gpu_layernorm.py)
+LOSSES_ELSEWHERE = set()
 
 _GLOBAL = re.compile(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", re.S)
 
