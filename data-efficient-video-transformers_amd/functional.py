@@ -2452,6 +2452,32 @@ def cross_entropy(logits: Tensor, labels: Tensor, ignore_index: int = ops.CE_IGN
     return _CrossEntropy.apply(logits, labels, int(ignore_index))
 
 
+class _SoftTargetCrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets):
+        lc = logits.contiguous()
+        tc = targets.detach().contiguous()
+        loss, lse = ops.ce_soft_fwd(lc, tc)
+        ctx.save_for_backward(lc, tc, lse)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        lc, tc, lse = ctx.saved_tensors
+        return ops.ce_soft_bwd(lc, tc, lse, _f32(gloss).reshape(1)), None
+
+
+def soft_target_cross_entropy(logits: Tensor, targets: Tensor) -> Tensor:
+    """timm's ``SoftTargetCrossEntropy``: mean over the rows of ``sum_c -t_c log_softmax(logits)_c`` for logits [M, C] and
+    float32 targets [M, C] (mixed, smoothed or plain one-hot rows; they need not sum to 1), fp32 arithmetic.  With the
+    smoothed one-hot rows of ``ops.targets_mix`` it is ``nn.CrossEntropyLoss(label_smoothing=)``.  No gradient reaches
+    ``targets``."""
+    if targets.dtype != torch.float32 or targets.shape != logits.shape or logits.dim() != 2:
+        raise TypeError(f"soft_target_cross_entropy: logits [M, C] and float32 targets [M, C], got {tuple(logits.shape)} and "
+                        f"{targets.dtype} {tuple(targets.shape)}")
+    return _SoftTargetCrossEntropy.apply(logits, targets)
+
+
 class MlpLayer:
     """One layer of ``mlp_chain``: ``linear`` (y = x W^T (+ b), optionally ReLU in the GEMM epilogue, optionally an fp32
     output), ``bn_relu`` (y = bn(relu(x)): its input is a pre-activation) or ``dropout`` (after a ReLU Linear)."""

@@ -374,3 +374,144 @@ def train_transform_autoaugment(dtype=torch.bfloat16, generator=None):          
     first = RandomResizedCropFlip(224, hflip_p=0.3, vflip_p=0.3, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype=torch.uint8,
                                   generator=generator)
     return _CropFlipAutoAugment(first, AutoAugment("imagenet", IMAGENET_MEAN, IMAGENET_STD, dtype, generator))
+
+
+# ---------------------------------------------------------------- Mixup / CutMix (timm.data.Mixup; VideoMix boxes for clips)
+def draw_beta(alpha: float, generator=None, n=None):
+    """``Beta(alpha, alpha)`` from the torch CPU generator: ``g1 / (g1 + g2)`` of two ``Gamma(alpha, 1)`` draws, an exact Beta
+    sampler (``np.random.beta`` in timm).  A Python float, or with ``n`` a float64 tensor [n]."""
+    g = torch._standard_gamma(torch.full((1 if n is None else int(n), 2), float(alpha), dtype=torch.float64),
+                              generator=generator)
+    lam = g[:, 0] / (g[:, 0] + g[:, 1])
+    lam = torch.where(torch.isfinite(lam), lam, torch.full_like(lam, 0.5))       # both draws underflowed to 0
+    return float(lam[0]) if n is None else lam
+
+
+def _cut(size: int, ratio: float, generator):
+    """timm's ``rand_bbox`` along one axis: a truncated integer side, a uniform integer centre, clipped to the axis."""
+    side = int(size * ratio)
+    centre = _randint(size, generator)
+    return min(max(centre - side // 2, 0), size), min(max(centre + side // 2, 0), size)
+
+
+def scale_box(row, src, dst):
+    """The box ``(t0, t1, y0, y1, x0, x1)`` drawn on a ``src = (T, H, W)`` grid, on a ``dst`` grid: per axis
+    ``lo' = lo * n' // n`` and ``hi' = ceil(hi * n' / n)`` -- the smallest box of the second grid that covers the first; an
+    empty box stays empty and a full axis stays full."""
+    out = []
+    for a in range(3):
+        lo, hi = int(row[2 * a]), int(row[2 * a + 1])
+        n, m = int(src[a]), int(dst[a])
+        out += [lo * m // n, lo * m // n] if hi <= lo else [lo * m // n, -((-hi * m) // n)]
+    return out
+
+
+class Mixup:
+    """timm's ``Mixup`` for batches of clips: Mixup and CutMix across the batch with the partner ``B - 1 - i`` (the batch
+    flip), and the mixed targets.  Arguments as timm's, plus ``generator`` (torch CPU generator of the draws) and ``box``:
+    ``'tube'`` (VideoMix: a spatial box through every frame, side ratio ``sqrt(1 - lam)``), ``'spatiotemporal'`` (ratio
+    ``cbrt(1 - lam)`` on t, y and x) or ``'temporal'`` (a run of ``int(T (1 - lam))`` whole frames).
+
+    The draws follow timm's rule, on the host: ``rand < prob`` decides whether the batch (``mode='batch'``), the sample
+    (``'elem'``) or the pair (``'pair'``, mirrored onto both members; the middle sample of an odd batch is left alone) is
+    mixed; with both alphas positive ``rand < switch_prob`` picks CutMix; ``lam ~ Beta(alpha, alpha)``; a CutMix box has
+    truncated integer sides, a uniform integer centre and is clipped to the clip, and its lambda is then corrected to
+    ``1 - box volume / (T H W)``.  ``draw(B, T, H, W)`` -> ``(table, lam_input, lam_target)``: the int32 table [B, 8]
+    (partner, kind, t0, t1, y0, y1, x0, x1; kind 0 = leave alone, 1 = mixup, 2 = cutmix) and two float32 [B].
+
+    ``__call__(x, target, params=None)``: ``x`` is a tensor ``[B, ..., C, H, W]`` or a tuple of such tensors that share the
+    batch and the table (FrameTransformer's ``img`` and ``vid``); they are mixed in place (``ops.clips_mix``) and returned.
+    The box is drawn on the first tensor's ``(T, H, W)`` (T = the folded middle dimensions) and taken to another grid by
+    ``scale_box``; ``lam_target`` is the first tensor's.  ``target``: float ``[B, C]`` (multi-label rows, mixed as they are,
+    ``label_smoothing`` ignored) or int64 ``[B]`` (smoothed one-hot rows, needs ``num_classes``) -> float32 ``[B, C]`` from
+    ``ops.targets_mix``.  ``params``: a ``draw`` result to use instead of drawing; what was used is kept in ``.last_params``.
+    """
+
+    def __init__(self, mixup_alpha=1.0, cutmix_alpha=0.0, cutmix_minmax=None, prob=1.0, switch_prob=0.5, mode="batch",
+                 label_smoothing=0.1, num_classes=None, generator=None, box="tube"):
+        if cutmix_minmax is not None:
+            raise NotImplementedError("Mixup(cutmix_minmax=) is not built: boxes come from the Beta draw")
+        if mode not in ("batch", "elem", "pair"):
+            raise ValueError(f"mode must be 'batch', 'elem' or 'pair', got {mode!r}")
+        if box not in ("tube", "spatiotemporal", "temporal"):
+            raise ValueError(f"box must be 'tube', 'spatiotemporal' or 'temporal', got {box!r}")
+        self.mixup_alpha, self.cutmix_alpha, self.prob, self.switch_prob = float(mixup_alpha), float(cutmix_alpha), prob, switch_prob
+        self.mode, self.label_smoothing, self.num_classes, self.generator, self.box = mode, float(label_smoothing), num_classes, generator, box
+        self.last_params = None
+
+    def _draw_one(self, T: int, H: int, W: int):
+        """-> (kind, t0, t1, y0, y1, x0, x1, lam_input, lam_target) of one batch, sample or pair"""
+        g = self.generator
+        leave = (0, 0, 0, 0, 0, 0, 0, 1.0, 1.0)
+        if not (self.prob and (self.mixup_alpha > 0 or self.cutmix_alpha > 0)) or not torch.rand(1, generator=g).item() < self.prob:
+            return leave
+        if self.mixup_alpha > 0 and self.cutmix_alpha > 0:
+            cut = torch.rand(1, generator=g).item() < self.switch_prob
+        else:
+            cut = self.cutmix_alpha > 0
+        lam = draw_beta(self.cutmix_alpha if cut else self.mixup_alpha, g)
+        if lam == 1.0:
+            return leave
+        if not cut:
+            lam32 = float(torch.tensor(lam, dtype=torch.float32))
+            return (1, 0, T, 0, H, 0, W, lam32, lam32)
+        t0, t1, y0, y1, x0, x1 = 0, T, 0, H, 0, W
+        if self.box == "tube":
+            r = math.sqrt(1.0 - lam)
+            (y0, y1), (x0, x1) = _cut(H, r, g), _cut(W, r, g)
+        elif self.box == "spatiotemporal":
+            r = (1.0 - lam) ** (1.0 / 3.0)
+            (t0, t1), (y0, y1), (x0, x1) = _cut(T, r, g), _cut(H, r, g), _cut(W, r, g)
+        else:
+            t0, t1 = _cut(T, 1.0 - lam, g)
+        lam_t = 1.0 - ((t1 - t0) * (y1 - y0) * (x1 - x0)) / float(T * H * W)
+        return (2, t0, t1, y0, y1, x0, x1, lam_t, lam_t)
+
+    def draw(self, B: int, T: int, H: int, W: int):
+        if self.mode == "batch":
+            rows = [self._draw_one(T, H, W)] * B
+        elif self.mode == "elem":
+            rows = [self._draw_one(T, H, W) for _ in range(B)]
+        else:
+            half = [self._draw_one(T, H, W) for _ in range(B // 2)]
+            rows = half + ([(0, 0, 0, 0, 0, 0, 0, 1.0, 1.0)] if B % 2 else []) + half[::-1]
+        table = torch.tensor([[B - 1 - i, *r[:7]] for i, r in enumerate(rows)], dtype=torch.int32).reshape(-1, 8)
+        lam_input = torch.tensor([r[7] for r in rows], dtype=torch.float32)
+        lam_target = torch.tensor([r[8] for r in rows], dtype=torch.float32)
+        return table, lam_input, lam_target
+
+    @staticmethod
+    def _grid(t: torch.Tensor):
+        if not isinstance(t, torch.Tensor) or t.dim() < 4:
+            raise ValueError("x must be [B, ..., C, H, W] (or a tuple of such tensors)")
+        C, H, W = t.shape[-3:]
+        return (int(t[0].numel() // (C * H * W)) if t.shape[0] else 1, H, W)
+
+    def __call__(self, x, target, params=None):
+        xs = tuple(x) if isinstance(x, (tuple, list)) else (x,)
+        grids = [self._grid(t) for t in xs]
+        B = xs[0].shape[0]
+        if any(t.shape[0] != B for t in xs) or target.shape[0] != B:
+            raise ValueError("x (every tensor of it) and target share the batch dimension")
+        soft = target.is_floating_point()
+        if not soft and (target.dtype != torch.int64 or target.dim() != 1):
+            raise ValueError("target must be float [B, C] or int64 [B]")
+        if not soft and self.num_classes is None:
+            raise ValueError("Mixup: int64 labels need num_classes")
+        table, lam_input, lam_target = self.draw(B, *grids[0]) if params is None else params
+        table = torch.as_tensor(table, dtype=torch.int32).reshape(-1, 8)
+        for t, grid in zip(xs, grids):
+            tab = table
+            if grid != grids[0]:
+                tab = table.clone()
+                for i in range(B):
+                    tab[i, 2:] = torch.tensor(scale_box(table[i, 2:].tolist(), grids[0], grid), dtype=torch.int32)
+            ops.clips_mix(t, tab, lam_input)
+        if soft:
+            mixed = ops.targets_mix(table, lam_target, y=target.float())
+        else:
+            mixed = ops.targets_mix(table, lam_target, labels=target, num_classes=self.num_classes,
+                                    smoothing=self.label_smoothing)
+        self.last_params = (table.clone(), torch.as_tensor(lam_input, dtype=torch.float32).clone(),
+                            torch.as_tensor(lam_target, dtype=torch.float32).clone())
+        return x, mixed

@@ -9,7 +9,10 @@ fails in ``forward`` with torch's message.  The loss is the mean over the labels
 (``ignore_index``); ``nn.LogSoftmax`` is built and unused, as in the reference.
 
 All arithmetic is HIP (``functional.mlp_chain``: GEMMs with bias / ReLU epilogues, ``dvt_bn1d_relu_*``; the loss on
-``dvt_ce_labels_*``).  ``compute_dtype`` (attribute, default bf16) sets the activation dtype; fp32 is exact fp32 arithmetic.
+``dvt_ce_labels_*``; ``nn.CrossEntropyLoss(label_smoothing=s)`` with s > 0, and float ``[M, C]`` labels, on ``dvt_targets_mix``
++ ``dvt_ce_soft_*``, where every row counts: there ``ignore_index`` is not honoured -- a non-default one is refused, a label of -100 makes the
+loss NaN).
+``compute_dtype`` (attribute, default bf16) sets the activation dtype; fp32 is exact fp32 arithmetic.
 
 Deliberate deviations: the torchmetrics ``f1`` / ``acc`` objects, unused by the reference's steps, are
 not constructed here (``metrics.F1`` is the device-side stand-in: ``model.f1 = metrics.F1(22)``); ``validation_step`` does not print the outputs and labels.
@@ -20,6 +23,7 @@ import torch
 from torch import nn
 
 from .. import functional as F
+from .. import ops
 from .. import optim
 from ..lightning_compat import LightningModule
 from .contrastivemodel import cfg, rows_input
@@ -78,10 +82,28 @@ class BasicMLP(LightningModule):
     def criterion(self, output, labels):
         L = self.loss
         if not (isinstance(L, nn.CrossEntropyLoss) and L.reduction == "mean" and L.weight is None
-                and L.label_smoothing == 0.0):
-            raise NotImplementedError(f"BasicMLP: only nn.CrossEntropyLoss() (mean, no weight, no smoothing) has a HIP "
+                and 0.0 <= L.label_smoothing < 1.0):
+            raise NotImplementedError(f"BasicMLP: only nn.CrossEntropyLoss(label_smoothing=s) (mean, no weight) has a HIP "
                                       f"kernel, got {L!r}")
-        return F.cross_entropy(output, labels, L.ignore_index)
+        soft = labels.is_floating_point()
+        if not soft and L.label_smoothing == 0.0:
+            return F.cross_entropy(output, labels, L.ignore_index)
+        if soft and L.label_smoothing != 0.0:
+            raise NotImplementedError("BasicMLP: label_smoothing on class-probability labels is not built; smooth the integer "
+                                      "labels (input_stage.Mixup does) or pass label_smoothing=0")
+        # smoothed one-hot rows (or the caller's mixed rows, as they are) through the soft-target loss: every row counts, so
+        # a label outside [0, C) -- ignore_index among them -- makes the loss NaN instead of being skipped.  Asking for an
+        # ignore_index of one's own states that such labels are there: that is refused (the default cannot be told from
+        # "none" without reading the labels back from the device)
+        if L.ignore_index != ops.CE_IGNORE_INDEX:
+            raise NotImplementedError(f"BasicMLP: ignore_index={L.ignore_index} is honoured on integer labels without label "
+                                      "smoothing only; the soft-target loss counts every row")
+        M = labels.shape[0]
+        ident = torch.zeros(M, 8, dtype=torch.int32)
+        ident[:, 0] = torch.arange(M, dtype=torch.int32)
+        targets = ops.targets_mix(ident, torch.ones(M), y=labels.float() if soft else None, labels=None if soft else labels,
+                                  num_classes=output.shape[1], smoothing=L.label_smoothing)
+        return F.soft_target_cross_entropy(output, targets)
 
     def _batch(self, batch):
         dev = next(self.parameters()).device

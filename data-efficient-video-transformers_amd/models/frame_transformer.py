@@ -23,6 +23,11 @@ installed; checked against a torch-CPU conv3d restatement).  ``vid_encoder`` / `
 injectable (any module mapping frames / chunks to ``d_model`` vectors; the small tests inject a patch-linear
 stand-in of their own, tests/encoders.py).
 
+``mix=`` (additive, default None: the reference's step) takes an ``input_stage.Mixup``: in ``training_step``, in training
+mode, ``img`` and ``vid`` are mixed in place across the batch under one table and the loss sees the mixed target;
+``train_aprc`` keeps the batch's integer labels; validation and test never mix.  It is an attribute, not a
+hyper-parameter, and adds no parameter and no state-dict key.
+
 Deviations from the literal reference text, all where the reference does not execute
 (SURVEY section 8a notes): missing ``img_cls`` / ``img_model`` / ``scene_transformer``
 members are created; ``torch.cat((data, distil_inject))`` gets the missing
@@ -230,7 +235,9 @@ class FrameTransformer(LightningModule):
         self.img_mlp_head = nn.Sequential(nn.Linear(d, 512), nn.GELU(), nn.Linear(512, 128), nn.GELU(),
                                           nn.Linear(128, self.n_out))                                     # :106
         self.norm = nn.LayerNorm(d)                                                                       # :117
-        for k in ("img_encoder", "vid_encoder"):       # modules are attributes, not hyper-parameters
+        # mix: an input_stage.Mixup applied to the inputs and the target of training_step (no parameter, no state-dict key)
+        self.mix = hp.get("mix", None)
+        for k in ("img_encoder", "vid_encoder", "mix"):       # modules and stages are attributes, not hyper-parameters
             if k in hp:
                 delattr(hp, k)
         # In the image-only modes the video branch (always constructed by the reference) takes no part in the computation
@@ -369,8 +376,16 @@ class FrameTransformer(LightningModule):
             data = self(None, vid)
         return self.criterion(data, target), data
 
+    def _mixed(self, batch):
+        """``self.mix`` on the inputs the batch carries (in place, one table for both) and on the target."""
+        target, img, vid = batch
+        xs = tuple(t for t in (img, vid) if t is not None)
+        _, mixed = self.mix(xs, target if target.is_floating_point() else target.float())
+        return mixed, img, vid
+
     def training_step(self, batch, batch_idx):
-        loss, data = self._loss(batch)
+        # Mixup / CutMix (additive: ``mix=None`` is the reference's step) reaches the loss only; the metric keeps the labels
+        loss, data = self._loss(self._mixed(batch) if self.mix is not None and self.training else batch)
         self.train_aprc(data, batch[0].int())                                  # :275-277
         self.log("train/loss", loss, on_step=False, on_epoch=True)
         self.log("train/aprc", self.train_aprc, on_step=False, on_epoch=True)

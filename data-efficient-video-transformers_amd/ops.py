@@ -1178,6 +1178,113 @@ def frames_erase(x: Tensor, table, value=(0, 0, 0)) -> Tensor:
     return x
 
 
+# ------------------------------------------------------------------ Mixup / CutMix and soft targets (csrc/mix.hip)
+MIX_ROWS_PER_LAUNCH = L.MACROS["DVT_MIX_ROWS_PER_LAUNCH"]      # rows (a pair or sample and one region) per clips_mix launch
+
+
+def _host_lam(lam, rows: int, what: str) -> Tensor:
+    """The lambdas as a contiguous float32 CPU tensor [rows]: validated on the host like the table."""
+    if isinstance(lam, Tensor) and lam.is_cuda:
+        raise ValueError(f"{what}: lam is a host array (validated before any launch), got a device tensor")
+    t = torch.as_tensor(lam, dtype=torch.float32).contiguous()
+    if t.dim() != 1 or t.shape[0] != rows:
+        raise ValueError(f"{what}: lam must be [{rows}], got {tuple(t.shape)}")
+    return t
+
+
+def clips_mix(x: Tensor, table, lam, out: Optional[Tensor] = None) -> Tensor:
+    """Mixup / CutMix across the batch of x [B, ..., C, H, W] (the dimensions between B and C fold into T): host table [B, 8]
+    int32 (partner, kind, t0, t1, y0, y1, x0, x1), kind 0 = leave alone, 1 = mixup ``fmaf(lam, x[i], (1 - lam) x[partner])``,
+    2 = cutmix ``out[i][box] = x[partner][box]``; host lam [B] float32.  ``out=None`` (or x): in place, the partner map must be
+    an involution and only what changes is written; otherwise ``out`` (same shape and dtype, disjoint from x) receives every
+    sample and any partner map goes.  One launch per ``MIX_ROWS_PER_LAUNCH`` rows (a pair, or out of place a sample, and one
+    region of it).  Returns the tensor written."""
+    if not isinstance(x, Tensor) or x.dim() < 4 or x.dtype not in _DT:
+        raise ValueError("x must be a floating-point tensor [B, ..., C, H, W]")
+    tab = _host_table(table, 8, "clips_mix")
+    B = x.shape[0]
+    if tab.shape[0] != B:
+        raise ValueError(f"clips_mix: {tab.shape[0]} table rows for {B} samples")
+    lm = _host_lam(lam, B, "clips_mix")
+    if not x.is_contiguous():
+        raise ValueError("clips_mix needs a contiguous tensor")
+    if out is not None and out is not x:
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+            raise ValueError("clips_mix: out must be contiguous with the shape, dtype and device of x")
+    in_place = out is None or out is x or out.data_ptr() == x.data_ptr()
+    partner = tab[:, 0].tolist()
+    if in_place and any(not (0 <= p < B and partner[p] == i) for i, p in enumerate(partner)):
+        raise ValueError("clips_mix: in place the partner map must be an involution (partner[partner[i]] == i); pass out= "
+                         "for any other map")
+    _need_cuda(x, out)
+    Cc, H, W = x.shape[-3:]
+    T = 1
+    for n in x.shape[1:-3]:
+        T *= int(n)
+    if x.numel() == 0:
+        return x if in_place else out
+    L.check(L.load().dvt_clips_mix(x.data_ptr(), None if in_place else out.data_ptr(), dt(x), B, T, Cc, H, W,
+                                   tab.data_ptr(), lm.data_ptr(), _stream()), "dvt_clips_mix")
+    return x if in_place else out
+
+
+def targets_mix(table, lam, y: Optional[Tensor] = None, labels: Optional[Tensor] = None, num_classes: Optional[int] = None,
+                smoothing: float = 0.0) -> Tensor:
+    """Mixed targets f32 [B, C]: ``lam_i t_i + (1 - lam_i) t_partner(i)`` with the partner of column 0 of the host table
+    [B, 8] and the host lam [B] (the target's lambda).  Exactly one of ``y`` (float32 [B, C], mixed as it is) and ``labels``
+    (int64 [B], with ``num_classes``: rows ``smoothing / C`` everywhere and ``1 - smoothing + smoothing / C`` at the label; a
+    label outside [0, C) gives a NaN row)."""
+    if (y is None) == (labels is None):
+        raise ValueError("targets_mix: exactly one of y and labels")
+    tab = _host_table(table, 8, "targets_mix")
+    src = y if y is not None else labels
+    B = src.shape[0]
+    if tab.shape[0] != B:
+        raise ValueError(f"targets_mix: {tab.shape[0]} table rows for {B} samples")
+    lm = _host_lam(lam, B, "targets_mix")
+    if y is not None:
+        if y.dim() != 2 or y.dtype != torch.float32:
+            raise ValueError("targets_mix: y must be float32 [B, C]")
+        Cc = y.shape[1]
+    else:
+        if labels.dim() != 1 or labels.dtype != torch.int64:
+            raise ValueError("targets_mix: labels must be int64 [B]")
+        if num_classes is None:
+            raise ValueError("targets_mix: integer labels need num_classes")
+        Cc = int(num_classes)
+    _need_cuda(src)
+    src = src.contiguous()
+    out = torch.empty((B, Cc), dtype=torch.float32, device=src.device)
+    L.check(L.load().dvt_targets_mix(_p(src) if y is not None else None, _p(src) if y is None else None, out.data_ptr(), B, Cc,
+                                     tab.data_ptr(), lm.data_ptr(), float(smoothing), _stream()), "dvt_targets_mix")
+    return out
+
+
+def ce_soft_fwd(logits: Tensor, targets: Tensor):
+    """Soft-target cross-entropy: mean over the rows of ``sum_c -t_c log_softmax(x)_c`` -> (loss f32 [1], lse f32 [2 M]: the
+    per-row log-sum-exp, then the per-row sums of the targets)."""
+    _need_cuda(logits, targets)
+    M, Cc = logits.shape
+    assert logits.stride(1) == 1
+    assert targets.dtype == torch.float32 and targets.is_contiguous() and targets.shape == (M, Cc)
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    lse = torch.empty(2 * M, dtype=torch.float32, device=logits.device)
+    L.check(L.load().dvt_ce_soft_fwd(logits.data_ptr(), logits.stride(0), targets.data_ptr(), loss.data_ptr(), lse.data_ptr(), M,
+                                     Cc, dt(logits), _stream()), "dvt_ce_soft_fwd")
+    return loss, lse
+
+
+def ce_soft_bwd(logits: Tensor, targets: Tensor, lse: Tensor, gloss: Tensor) -> Tensor:
+    _need_cuda(logits, targets, lse, gloss)
+    M, Cc = logits.shape
+    assert logits.stride(1) == 1 and gloss.dtype == torch.float32 and lse.numel() == 2 * M
+    assert targets.dtype == torch.float32 and targets.is_contiguous() and targets.shape == (M, Cc)
+    d = torch.empty((M, Cc), dtype=logits.dtype, device=logits.device)
+    L.check(L.load().dvt_ce_soft_bwd(logits.data_ptr(), logits.stride(0), targets.data_ptr(), lse.data_ptr(), gloss.data_ptr(),
+                                     d.data_ptr(), Cc, M, Cc, dt(logits), _stream()), "dvt_ce_soft_bwd")
+    return d
+
+
 def frames_autoaugment(frames_u8: Tensor, table, mean=None, std=None, out_dtype: torch.dtype = torch.bfloat16) -> Tensor:
     """uint8 RGB frames [N, H, W, 3] + host table [N, 2, 8] int32 (two slots {op, p0 .. p6} per sample, applied in order;
     ``input_stage.AutoAugment.draw`` makes one) -> [N, 3, H, W] in ``out_dtype``: torchvision's AutoAugment operations as its

@@ -586,6 +586,42 @@ int dvt_frames_augment(const void* src, int64_t frames, int H0, int W0, const in
                        dvt_stream_t stream);
 int dvt_frames_erase(void* x, int dtype, int64_t frames, int H, int W, const int32_t* table, const float* value,
                      dvt_stream_t stream);
+/* Addition within ABI v5: Mixup / CutMix across the batch (timm.data.Mixup; for clips the VideoMix form, one box for all
+ * frames and channels of a sample), a stage behind the transform chains above (MMX_Frame_dl.py:63-88 has none), the mixed
+ * targets (timm's mixup_target) and the loss that accepts them (timm.loss.SoftTargetCrossEntropy; with a smoothed one-hot
+ * target it is nn.CrossEntropyLoss(label_smoothing=) of src/models/basicmlp.py:38).  The random draws are the caller's.
+ * Every argument is validated on the host before any HIP call; a bad table row returns DVT_ERR_BAD_ARG and
+ * dvt_last_error() names it.
+ * dvt_clips_mix: x[B, T, C, H, W] (dtype, contiguous).  table: HOST array of B x 8 int32 rows {partner, kind, t0, t1, y0, y1,
+ *   x0, x1}, kind 0 = leave alone, 1 = mixup, 2 = cutmix with the half-open box (read for kind 2 only) shared by every
+ *   channel; lam: HOST array of B floats in [0, 1].
+ *     kind 1   out[i] = fmaf(lam_i, x[i], (1.0f - lam_i) * x[partner_i]) in fp32, rounded once to dtype
+ *     kind 2   out[i][box] = x[partner_i][box], a copy; the rest of out[i] is x[i]
+ *   Kind 0, partner_i == i, an empty box and kind 1 with lam_i == 1 leave sample i bit for bit as it is.  out == NULL or
+ *   out == x: in place; the partner map must then be an involution (partner[partner[i]] == i, refused otherwise), pairs
+ *   i < partner_i are taken together -- a lane loads the same elements of both members, then stores both -- and no byte of
+ *   an unchanged sample or outside a box is written; the result equals the out-of-place one bit for bit.  out disjoint
+ *   from x: any partner map; every sample is written.  The work travels to the kernel by value, DVT_MIX_ROWS_PER_LAUNCH
+ *   rows (a pair or sample and one region of it) per launch; launches with nothing to do are not made.  16-byte accesses
+ *   wherever the addresses a row uses sit alike in their 16-byte lines, element accesses for the head and tail of a run
+ *   and where they do not.  T x C x H x W < 2^30.
+ * dvt_targets_mix: out[B, Ccls] f32 = lam_i * t_i + (1.0f - lam_i) * t_partner(i) with partner = column 0 of the same table
+ *   and lam the target's lambda (for cutmix 1 - box volume / (T H W)); exactly one of y (f32 [B, Ccls], taken as it is) and
+ *   labels (int64 [B]) is non-null; a label row is smoothing / Ccls everywhere and 1 - smoothing + smoothing / Ccls at the
+ *   label.  A label outside [0, Ccls) is never used as an index: its row (and a row that mixes it in) is NaN.  A row with
+ *   lam_i == 1 is its own target exactly.
+ * dvt_ce_soft_fwd: loss[0] = mean over the M rows of sum_c -t_rc (x_rc - lse_r), fp32 arithmetic, fixed order; logits
+ *   [M][ld] dtype, targets f32 [M][C]; lse f32 [2 M] receives the per-row log-sum-exp and, at [M + r], sum_c t_rc (rows need
+ *   not sum to 1).  dvt_ce_soft_bwd: dlogits[r] = gloss[0] / M * (softmax(x_r) * sum_c t_rc - t_r).  No gradient to targets. */
+#define DVT_MIX_ROWS_PER_LAUNCH 64
+int dvt_clips_mix(void* x, void* out, int dtype, int64_t B, int T, int C, int H, int W, const int32_t* table,
+                  const float* lam, dvt_stream_t stream);
+int dvt_targets_mix(const float* y, const int64_t* labels, float* out, int64_t B, int64_t Ccls, const int32_t* table,
+                    const float* lam, float smoothing, dvt_stream_t stream);
+int dvt_ce_soft_fwd(const void* logits, int64_t ld, const float* targets, float* loss, float* lse, int64_t M, int64_t C,
+                    int dtype, dvt_stream_t stream);
+int dvt_ce_soft_bwd(const void* logits, int64_t ld, const float* targets, const float* lse, const float* gloss, void* dlogits,
+                    int64_t lddl, int64_t M, int64_t C, int dtype, dvt_stream_t stream);
 /* Addition within ABI v5: the AutoAugment stage of the image branch above (torchvision's AutoAugment on its PIL path, the
  * random draws made by the caller).  dvt_frames_autoaugment: sample n of src[samples, H, W, 3] (uint8, device) takes the
  *   two operations of table[n] in order.  table: HOST array of samples x 2 slots x 8 int32 {op, p0 .. p6}, validated whole
