@@ -552,7 +552,7 @@ __global__ __launch_bounds__(256) void bn_colstats_kernel(const T* __restrict__ 
 // MODE 0: mean, invstd (biased var), running stats update.  MODE 1: dgamma = sum dz*xhat, dbeta = sum dz.
 template <int MODE, int CL = 32>
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restrict__ partial, int nparts, int C,
-                                                           float inv_rows, float eps, float* __restrict__ o0,
+                                                           double inv_rows, float eps, float* __restrict__ o0,
                                                            float* __restrict__ o1, float* __restrict__ run_mean,
                                                            float* __restrict__ run_var, float momentum, float unbias,
                                                            int accumulate, float* __restrict__ pub0 = nullptr,
@@ -565,6 +565,8 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
   // The partial sums are added in double and the variance is formed in double: the one-pass form E[x^2] - mu^2 in fp32
   // loses the variance of channels whose |mean| is large against their spread to the rounding of sums over 10^5..10^7
   // rows; with double accumulation of the (fp32, <= 128-row) partials what is left is the rounding inside one partial.
+  // inv_rows is a double for the same reason: the fp32 reciprocal of a row count that is no power of two is off by up to
+  // 6e-8 of itself, which E[x^2] - mu^2 turns into 6e-8 mu^2 / var of the variance (1e-4 at a mean of 100 and a variance of 4).
   constexpr int PL = 1024 / CL;
   __shared__ double red[2][PL][CL + 1];
   const int cl = threadIdx.x % CL, pl = threadIdx.x / CL;
@@ -631,8 +633,8 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
 #pragma unroll
   for (int p = 0; p < 8; ++p) { s0 += red[0][p][cl]; s1 += red[1][p][cl]; }
   if (MODE == 0) {
-    const double mud = s0 * (double)inv_rows;
-    const double vard = s1 * (double)inv_rows - mud * mud;
+    const double mud = s0 * inv_rows;
+    const double vard = s1 * inv_rows - mud * mud;
     const float mu = (float)mud;
     const float var = vard > 0.0 ? (float)vard : 0.f;
     o0[c] = mu;
@@ -659,7 +661,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
 
 // launch of the finalize kernel with the column-lane count that suits C
 template <int MODE>
-static void bn_finalize_launch(hipStream_t st, const float* partial, int nparts, int C, float inv_rows, float eps, float* o0,
+static void bn_finalize_launch(hipStream_t st, const float* partial, int nparts, int C, double inv_rows, float eps, float* o0,
                                float* o1, float* run_mean, float* run_var, float momentum, float unbias, int accumulate,
                                float* pub0 = nullptr, float* pub1 = nullptr, int c_valid = 1 << 30) {
   if (C <= 256)
@@ -678,7 +680,7 @@ static void bn_finalize_launch(hipStream_t st, const float* partial, int nparts,
 namespace dvt_internal {
 void bn_bwd_finalize(hipStream_t st, const float* partial, int nparts, int C, float* loc, int accumulate, float* dgamma,
                      float* dbeta, int c_valid) {
-  bn_finalize_launch<1>(st, partial, nparts, C, 0.f, 0.f, loc, loc + C, (float*)nullptr, (float*)nullptr, 0.f, 0.f, accumulate,
+  bn_finalize_launch<1>(st, partial, nparts, C, 0.0, 0.f, loc, loc + C, (float*)nullptr, (float*)nullptr, 0.f, 0.f, accumulate,
                         dgamma, dbeta, c_valid);
 }
 }  // namespace dvt_internal
@@ -1726,7 +1728,7 @@ int dvt_bn_stats(const void* x, float* mean, float* invstd, float* running_mean,
   }
   DVT_LAUNCH_CHECK("dvt_bn_stats");
   const float unbias = rows > 1 ? (float)rows / (float)(rows - 1) : 1.f;
-  bn_finalize_launch<0>(st, (const float*)workspace, parts, C, 1.0f / (float)rows, eps, mean, invstd, running_mean,
+  bn_finalize_launch<0>(st, (const float*)workspace, parts, C, 1.0 / (double)rows, eps, mean, invstd, running_mean,
                      running_var, momentum, unbias, 0, nullptr, nullptr, c_valid);
   DVT_LAUNCH_CHECK("dvt_bn_stats(finalize)");
   return DVT_OK;
@@ -1755,7 +1757,7 @@ int dvt_bn_stats_from_partials(float* partial, int64_t parts, float* mean, float
     np = folds;
   }
   bn_finalize_launch<0>(st, src, np, C,
-                     1.0f / (float)rows, eps, mean, invstd, running_mean, running_var, momentum, unbias, 0, nullptr, nullptr,
+                     1.0 / (double)rows, eps, mean, invstd, running_mean, running_var, momentum, unbias, 0, nullptr, nullptr,
                      c_valid);
   DVT_LAUNCH_CHECK("dvt_bn_stats_from_partials");
   return DVT_OK;
@@ -1838,7 +1840,7 @@ int dvt_bn_bwd(const void* dy, const void* x, const void* y, const void* relu_ma
   // keep the local dgamma/dbeta 16-byte aligned behind the partials
   float* loc = part + (((size_t)parts * 2 * C + 3) & ~(size_t)3);
   // dgamma / dbeta are published (overwritten or accumulated) by the same launch that leaves this launch's own sums in `loc`
-  bn_finalize_launch<1>(st, part, parts, C, 0.f, 0.f, loc, loc + C, (float*)nullptr, (float*)nullptr, 0.f, 0.f, accumulate, dgamma, dbeta,
+  bn_finalize_launch<1>(st, part, parts, C, 0.0, 0.f, loc, loc + C, (float*)nullptr, (float*)nullptr, 0.f, 0.f, accumulate, dgamma, dbeta,
                      c_valid);
   DVT_LAUNCH_CHECK("dvt_bn_bwd(finalize)");
   if (cvec) {
@@ -1912,7 +1914,7 @@ int dvt_bn_bwd_pooled(const void* dy_pool, const void* idx, const void* x, const
   float* loc = part + (((size_t)parts * 2 * C + 3) & ~(size_t)3);
   // dgamma / dbeta are published (overwritten or accumulated) by the same launch that leaves this launch's own sums in `loc`
   bn_finalize_launch<1>(st, (const float*)part,
-                     parts, C, 0.f, 0.f, loc, loc + C, (float*)nullptr, (float*)nullptr, 0.f, 0.f, accumulate, dgamma, dbeta);
+                     parts, C, 0.0, 0.f, loc, loc + C, (float*)nullptr, (float*)nullptr, 0.f, 0.f, accumulate, dgamma, dbeta);
   DVT_LAUNCH_CHECK("dvt_bn_bwd_pooled(finalize)");
   if (quad) {
     DVT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((bn_apply_bwd_pool_quad_kernel<T>), dim3(dvt_grid(rows / 4 * (C >> 3))), dim3(kB), 0,
