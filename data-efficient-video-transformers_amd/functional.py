@@ -427,6 +427,85 @@ def tokens_assemble(emb: Tensor, cls: Tensor, pos: Tensor, S: int, T: int, n: in
 
 
 # ---------------------------------------------------------------------------
+# Patch dropout: the two operators above on a kept subset of the patch tokens (csrc/patch_dropout.hip).
+# keep [S, k] int32 ascending per row, slot [S, n] int32 its inverse (-1 = dropped): ops.keep_draw / keep_select / keep_slots.
+# ---------------------------------------------------------------------------
+class _PatchEmbedKeep(torch.autograd.Function):
+    """``_PatchEmbed`` of the kept rows: the gather reads the kept patches only, the Linear and the weight-gradient GEMM
+    run at S*k rows, and the clip's gradient is written whole (zero in the dropped patches) by the gather's adjoint."""
+
+    @staticmethod
+    def forward(ctx, clip, w, b, patch, dtype, tubelet, keep, slot):
+        patches = ops.patchify_keep(clip, patch, tubelet, keep, dtype)      # [S*k, pt*P*P*C]
+        wc = _wc(w, dtype)
+        emb = ops.linear_fwd(patches, wc, _f32(b))
+        ctx.save_for_backward(patches, wc, slot)
+        ctx.clip_shape, ctx.clip_dtype, ctx.patch, ctx.tubelet = tuple(clip.shape), clip.dtype, patch, tubelet
+        ctx.sinks = (_sink(w), _sink(b))
+        return emb
+
+    @staticmethod
+    def backward(ctx, demb):
+        patches, wc, slot = ctx.saved_tensors
+        demb = demb.contiguous()
+        dclip = None
+        if ctx.needs_input_grad[0]:
+            dpatch = ops.linear_dgrad(demb, wc)
+            dclip = ops.patchify_keep_bwd(dpatch, ctx.clip_shape, ctx.patch, ctx.tubelet, slot, ctx.clip_dtype)
+        dw, db = _emit_wgrad_bias(ctx.sinks[0], ctx.sinks[1], demb, patches, True)
+        return dclip, dw, db, None, None, None, None, None
+
+
+def patch_embed_keep(clip: Tensor, w: Tensor, b: Tensor, patch: int, dtype: torch.dtype, tubelet: int, keep: Tensor,
+                     slot: Tensor) -> Tensor:
+    """clip [b, t, C, H, W], keep [S, k], slot [S, n] (S = b * t / tubelet) -> [S * k, d] in ``dtype``: the rows
+    ``keep`` names of ``patch_embed(clip, ..., tubelet=tubelet)``."""
+    return _PatchEmbedKeep.apply(clip, w, b, patch, dtype, tubelet, keep, slot)
+
+
+class _TokensKeep(torch.autograd.Function):
+    """``_Tokens`` on kept rows; the same sink protocol (one accumulate flag for dcls and dpos, the slow form when the two
+    sinks disagree)."""
+
+    @staticmethod
+    def forward(ctx, emb, cls, pos, keep, slot, S, T):
+        cls32 = _f32(cls).reshape(-1)
+        pos32 = _f32(pos)
+        pos32 = pos32.reshape(T, pos32.shape[-2], pos32.shape[-1])
+        if keep.shape[0] != S or slot.shape[0] != S:
+            raise ValueError(f"tokens_assemble_keep: keep {tuple(keep.shape)} / slot {tuple(slot.shape)} for {S} sequences")
+        ctx.T, ctx.pos_rows = T, pos32.shape[1]
+        ctx.cls_shape, ctx.pos_shape = tuple(cls.shape), tuple(pos.shape)
+        ctx.sinks = (_sink(cls), _sink(pos))
+        ctx.slot = slot
+        return ops.tokens_assemble_keep_fwd(emb.contiguous(), cls32, pos32, keep)
+
+    @staticmethod
+    def backward(ctx, dout):
+        sc, sp = ctx.sinks
+        none = (None,) * 6
+        if sc is not None and sp is not None and sc.fresh != sp.fresh:
+            demb, dcls, dpos = ops.tokens_assemble_keep_bwd(dout, ctx.T, ctx.pos_rows, ctx.slot)
+            _emit_into(sc, dcls)
+            _emit_into(sp, dpos)
+            return (demb,) + none
+        if sc is not None and sp is not None:
+            demb, _, _ = ops.tokens_assemble_keep_bwd(dout, ctx.T, ctx.pos_rows, ctx.slot, dcls=sc.buf.view(-1),
+                                                      dpos=sp.buf.view(ctx.T, ctx.pos_rows, -1), accumulate=not sc.fresh)
+            sc.mark_written()
+            sp.mark_written()
+            return (demb,) + none
+        demb, dcls, dpos = ops.tokens_assemble_keep_bwd(dout, ctx.T, ctx.pos_rows, ctx.slot)
+        return (demb, dcls.view(ctx.cls_shape), dpos.view(ctx.pos_shape)) + (None,) * 4
+
+
+def tokens_assemble_keep(emb: Tensor, cls: Tensor, pos: Tensor, keep: Tensor, slot: Tensor, S: int, T: int) -> Tensor:
+    """emb [S*k, d], cls [1,1,d], pos [1,T,rows,d], keep [S, k], slot [S, n] -> [S, k+1, d]: row 0 the CLS token, row 1 + i
+    the kept patch i, each with the positional row of its ORIGINAL position."""
+    return _TokensKeep.apply(emb, cls, pos, keep, slot, S, T)
+
+
+# ---------------------------------------------------------------------------
 # Final space LayerNorm on the CLS rows + temporal CLS concat (vit.py:75,120-123)
 # ---------------------------------------------------------------------------
 class _ClsNormConcat(torch.autograd.Function):

@@ -18,8 +18,14 @@ across pt consecutive frames, csrc/patchify.hip): the space stack runs on ``num_
 state-dict keys stay the reference's; ``to_patch_embedding.1.weight`` is ``[dim, pt*P*P*C]`` and ``pos_embedding``
 ``[1, num_frames // pt, n + 1, dim]``.  ``ViViT.load_frame_checkpoint`` carries a per-frame checkpoint into such a model
 (``inflate_patch_embedding``).
+``patch_dropout`` / ``patch_dropout_mode`` -- in training, the space stack runs on a random subset of
+k = n - floor(patch_dropout * n) patch tokens per sequence (csrc/patch_dropout.hip): ``"tube"`` keeps the same positions in
+every temporal token of a clip (VideoMAE's tube masking), ``"frame"`` draws per temporal token (PatchDropout).  ``forward``
+and ``loss`` also take a caller's ``keep [S, k]`` (int32, ascending rows), used as given in training and in eval.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 from torch import nn
@@ -232,7 +238,7 @@ class ViViT(nn.Module):
     def __init__(self, image_size, patch_size, num_classes, num_frames, dim=192, depth=4, heads=3,
                  pool='cls', in_channels=3, dim_head=64, dropout=0., emb_dropout=0., scale_dim=4, *,
                  compute_dtype: torch.dtype = torch.bfloat16, activation_checkpointing: bool = False,
-                 tubelet_size: int = 1):
+                 patch_dropout: float = 0.0, patch_dropout_mode: str = "tube", tubelet_size: int = 1):
         super().__init__()
         assert pool in {'cls', 'mean'}, 'pool type must be either cls (cls token) or mean (mean pooling)'
         assert image_size % patch_size == 0, 'Image dimensions must be divisible by the patch size.'
@@ -241,6 +247,11 @@ class ViViT(nn.Module):
         if num_frames % tubelet_size != 0:
             raise ValueError(f"num_frames = {num_frames} is not a multiple of tubelet_size = {tubelet_size}")
         num_patches = (image_size // patch_size) ** 2
+        if patch_dropout_mode not in ("tube", "frame"):
+            raise ValueError(f"patch_dropout_mode must be 'tube' or 'frame', got {patch_dropout_mode!r}")
+        self.patch_dropout = float(patch_dropout)
+        self.patch_dropout_mode = patch_dropout_mode
+        self.num_kept(num_patches)             # ValueError unless 0 <= patch_dropout < 1 and k >= 1
         patch_dim = tubelet_size * in_channels * patch_size ** 2
         self.to_patch_embedding = nn.Sequential(
             Patchify(patch_size, tubelet_size),
@@ -267,19 +278,29 @@ class ViViT(nn.Module):
         self.space_transformer.checkpoint = activation_checkpointing
         self.temporal_transformer.checkpoint = activation_checkpointing
 
-    def forward(self, x):
-        pooled, pending = self._trunk(x)
+    def num_kept(self, n: int) -> int:
+        """k = n - floor(patch_dropout * n): the patch tokens a sequence of n positions keeps in training."""
+        p = self.patch_dropout
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"patch_dropout must be in [0, 1), got {p!r}")
+        k = n - math.floor(p * n)
+        if k < 1:
+            raise ValueError(f"patch_dropout = {p!r} keeps no patch of {n}")
+        return k
+
+    def forward(self, x, keep=None):
+        pooled, pending = self._trunk(x, keep)
         if pending is not None:                                                     # the temporal stack's final norm (:43)
             pooled = F.layernorm(pooled, pending.weight, pending.bias, pending.eps)
         hn, hl = self.mlp_head[0], self.mlp_head[1]
         h = F.layernorm(pooled, hn.weight, hn.bias, hn.eps)
         return F.linear(h, hl.weight, hl.bias, out_f32=True)                        # :128
 
-    def loss(self, x, target):
+    def loss(self, x, target, keep=None):
         """nn.BCEWithLogitsLoss()(self(x), target) (the training step of the reference's Lightning wrapper), with the head
         -- final norm on the pooled row, mlp_head, the loss -- as one launch where the shape allows (8 rows at the metric
         shape: the separate kernels are pure launch cost).  -> (loss, logits)."""
-        pooled, pending = self._trunk(x)
+        pooled, pending = self._trunk(x, keep)
         hn, hl = self.mlp_head[0], self.mlp_head[1]
         if pooled.is_cuda and F.head_bce_supported(pooled, hl.weight):
             mixed = pooled.dtype == torch.float32 and self.compute_dtype in (torch.bfloat16, torch.float16)
@@ -330,7 +351,27 @@ class ViViT(nn.Module):
             for k, dst in own.items():
                 dst.copy_(new[k])
 
-    def _trunk(self, x):
+    def _kept_rows(self, x, keep, S, t, n):
+        """-> (keep [S, k], slot [S, n]) or (None, None): a caller's ``keep`` as given (checked on the host: no device value
+        is read), else -- in training with patch_dropout > 0 -- a draw at a site of the dropout generator."""
+        if keep is not None:
+            if (not isinstance(keep, torch.Tensor) or keep.dtype != torch.int32 or keep.dim() != 2 or keep.shape[0] != S
+                    or not 1 <= keep.shape[1] <= n):
+                raise ValueError(f"keep must be an int32 tensor [{S}, k] with 1 <= k <= {n}, got "
+                                 f"{getattr(keep, 'dtype', type(keep))} of shape {tuple(getattr(keep, 'shape', ()))}")
+            if keep.device != x.device:
+                raise ValueError(f"keep is on {keep.device}, the clip on {x.device}")
+            from .. import ops
+            keep = keep.contiguous()
+            return keep, ops.keep_slots(keep, n)
+        if not (self.training and self.patch_dropout > 0.0):
+            return None, None
+        from .. import ops
+        k = self.num_kept(n)
+        R, rows_per = (S // t, t) if self.patch_dropout_mode == "tube" else (S, 1)
+        return ops.keep_draw(R, n, k, F._rng.tensor(x.device), F._rng.take(R * n), rows_per)
+
+    def _trunk(self, x, keep=None):
         """-> (pooled [b, dim], the LayerNorm still to be applied to it or None)."""
         if x.dim() != 5:
             raise ValueError("ViViT expects a clip tensor [b, t, c, H, W]")
@@ -343,8 +384,13 @@ class ViViT(nn.Module):
         F.lp_clear()            # 16-bit gradient copies a previous step's backward left untaken (functional._lp_hand)
         n = (x.shape[3] // self.patch_size) * (x.shape[4] // self.patch_size)
         pe = self.to_patch_embedding[1]
-        emb = F.patch_embed(x, pe.weight, pe.bias, self.patch_size, T, tubelet=self.tubelet_size)   # vit.py:110
-        tok = F.tokens_assemble(emb, self.space_token, self.pos_embedding, b * t, t, n)   # :113-115
+        keep, slot = self._kept_rows(x, keep, b * t, t, n)
+        if keep is None:
+            emb = F.patch_embed(x, pe.weight, pe.bias, self.patch_size, T, tubelet=self.tubelet_size)   # vit.py:110
+            tok = F.tokens_assemble(emb, self.space_token, self.pos_embedding, b * t, t, n)   # :113-115
+        else:                                               # the same two lines on the kept patch tokens
+            emb = F.patch_embed_keep(x, pe.weight, pe.bias, self.patch_size, T, self.tubelet_size, keep, slot)
+            tok = F.tokens_assemble_keep(emb, self.space_token, self.pos_embedding, keep, slot, b * t, t)
         tok = F.dropout(tok, self.emb_dropout_p, self.training)                            # :116
         st, tt = self.space_transformer, self.temporal_transformer
         sn = st.norm

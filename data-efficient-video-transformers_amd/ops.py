@@ -270,6 +270,145 @@ def tubelet_patchify_bwd(dout: Tensor, shape, patch: int, tubelet: int, dx_dtype
     """The adjoint (inverse) of ``tubelet_patchify``: dout [(frames / tubelet) * n, tubelet*P*P*C] -> dx of ``shape``."""
     return _patch_gather("tubelet_patchify_bwd", dout, shape, patch, tubelet, dx_dtype)
 
+
+# ------------------------------------------------------------------ patch dropout (csrc/patch_dropout.hip)
+def _index_table(what: str, t: Tensor, rows: Optional[int] = None, cols: Optional[int] = None) -> Tensor:
+    """An int32 device matrix (keys, keep or slot) as the kernels take it; ValueError otherwise."""
+    if not isinstance(t, Tensor) or t.dtype != torch.int32 or t.dim() != 2:
+        raise ValueError(f"{what}: expected a 2-D int32 tensor, got {getattr(t, 'dtype', type(t))} "
+                         f"of shape {tuple(getattr(t, 'shape', ()))}")
+    if (rows is not None and t.shape[0] != rows) or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f"{what}: shape {tuple(t.shape)} where [{'*' if rows is None else rows}, "
+                         f"{'*' if cols is None else cols}] is expected")
+    _need_cuda(t)
+    return t.contiguous()
+
+
+def keep_select(keys: Tensor, k: int, rows_per: int = 1) -> Tuple[Tensor, Tensor]:
+    """keys [R, n] int32 -> (keep [R*rows_per, k] ascending, slot [R*rows_per, n], -1 = dropped): position i is kept iff
+    fewer than k positions j have (key_j, j) < (key_i, i) -- the first k of a stable argsort; every row written rows_per
+    times (tube masking: R = b, rows_per = t')."""
+    keys = _index_table("keep_select: keys", keys)
+    R, n = keys.shape
+    keep = torch.empty((R * rows_per, k), dtype=torch.int32, device=keys.device)
+    slot = torch.empty((R * rows_per, n), dtype=torch.int32, device=keys.device)
+    L.check(L.load().dvt_keep_select(keys.data_ptr(), R, n, k, rows_per, keep.data_ptr(), slot.data_ptr(), _stream()),
+            "dvt_keep_select")
+    return keep, slot
+
+
+def keep_draw(R: int, n: int, k: int, rng_state: Tensor, call_offset: int, rows_per: int = 1) -> Tuple[Tensor, Tensor]:
+    """``keep_select`` on keys that are a pure function of (rng_state on the device, call_offset, row, position): one launch.
+    A site takes ceil(R*n / 4) Philox blocks (``functional._rng.take(R * n)``)."""
+    _need_cuda(rng_state)
+    keep = torch.empty((R * rows_per, k), dtype=torch.int32, device=rng_state.device)
+    slot = torch.empty((R * rows_per, n), dtype=torch.int32, device=rng_state.device)
+    L.check(L.load().dvt_keep_draw(rng_state.data_ptr(), call_offset, R, n, k, rows_per, keep.data_ptr(), slot.data_ptr(),
+                                   None, _stream()), "dvt_keep_draw")
+    return keep, slot
+
+
+def keep_keys(R: int, n: int, rng_state: Tensor, call_offset: int) -> Tensor:
+    """The keys [R, n] int32 ``keep_draw`` selects on at the same (rng_state, call_offset)."""
+    _need_cuda(rng_state)
+    keys = torch.empty((R, n), dtype=torch.int32, device=rng_state.device)
+    L.check(L.load().dvt_keep_draw(rng_state.data_ptr(), call_offset, R, n, 1, 1, None, None, keys.data_ptr(), _stream()),
+            "dvt_keep_draw")
+    return keys
+
+
+def keep_slots(keep: Tensor, n: int) -> Tensor:
+    """slot [S, n] int32 of a caller's keep [S, k]: slot[s, keep[s, i]] = i, -1 elsewhere."""
+    keep = _index_table("keep_slots: keep", keep)
+    S, k = keep.shape
+    slot = torch.empty((S, n), dtype=torch.int32, device=keep.device)
+    L.check(L.load().dvt_keep_slots(keep.data_ptr(), S, n, k, slot.data_ptr(), _stream()), "dvt_keep_slots")
+    return slot
+
+
+def patchify_keep(x: Tensor, patch: int, tubelet: int, keep: Tensor, out_dtype: torch.dtype) -> Tensor:
+    """[..., t, C, H, W], keep [S, k] -> [S*k, tubelet*P*P*C]: the rows ``keep`` names of ``tubelet_patchify``, read from
+    the kept patches only."""
+    frames, Cc, H, W = _tubelet_geometry(x.shape, patch, tubelet, "patchify_keep")
+    keep = _index_table("patchify_keep: keep", keep, rows=frames // tubelet)
+    _need_cuda(x)
+    x = x.contiguous()
+    k = keep.shape[1]
+    out = torch.empty((keep.shape[0] * k, tubelet * patch * patch * Cc), dtype=out_dtype, device=x.device)
+    nbytes = out.numel() * (x.element_size() + out.element_size())
+    with _timed(("hbm", "patchify_keep", out.numel()), nbytes):
+        L.check(L.load().dvt_patchify_keep(x.data_ptr(), dt(x), out.data_ptr(), _DT[out_dtype], keep.data_ptr(), frames, Cc, H,
+                                           W, patch, tubelet, k, _stream()), "dvt_patchify_keep")
+    return out
+
+
+def patchify_keep_bwd(dout: Tensor, shape, patch: int, tubelet: int, slot: Tensor, dx_dtype: torch.dtype) -> Tensor:
+    """The adjoint of ``patchify_keep``: dout [S*k, tubelet*P*P*C], slot [S, n] -> dx of ``shape``, every pixel written once
+    (zero where the patch was dropped)."""
+    _need_cuda(dout)
+    frames, Cc, H, W = _tubelet_geometry(shape, patch, tubelet, "patchify_keep_bwd")
+    if H % patch or W % patch:
+        raise ValueError(f"patchify_keep_bwd: image {H}x{W} is not divisible by patch {patch}")
+    slot = _index_table("patchify_keep_bwd: slot", slot, rows=frames // tubelet, cols=(H // patch) * (W // patch))
+    dout = dout.contiguous()
+    cols = tubelet * patch * patch * Cc
+    if dout.dim() != 2 or dout.shape[1] != cols or dout.shape[0] % slot.shape[0] or dout.shape[0] == 0:
+        raise ValueError(f"patchify_keep_bwd: dout {tuple(dout.shape)} is not [S*k, {cols}] for S = {slot.shape[0]}")
+    k = dout.shape[0] // slot.shape[0]
+    dx = torch.empty(tuple(shape), dtype=dx_dtype, device=dout.device)
+    nbytes = dout.numel() * dout.element_size() + dx.numel() * dx.element_size()
+    with _timed(("hbm", "patchify_keep_bwd", dout.numel()), nbytes):
+        L.check(L.load().dvt_patchify_keep_bwd(dout.data_ptr(), dt(dout), dx.data_ptr(), _DT[dx_dtype], slot.data_ptr(), frames,
+                                               Cc, H, W, patch, tubelet, k, _stream()), "dvt_patchify_keep_bwd")
+    return dx
+
+
+def tokens_assemble_keep_fwd(emb: Tensor, cls: Tensor, pos: Tensor, keep: Tensor) -> Tensor:
+    """emb [S*k, d]; cls [d] f32; pos [T, rows >= n+1, d] f32; keep [S, k] -> [S, k+1, d]:
+    out[s, 0] = cls + pos[s % T, 0], out[s, 1+i] = emb[s*k + i] + pos[s % T, 1 + keep[s, i]]."""
+    _need_cuda(emb, cls, pos)
+    keep = _index_table("tokens_assemble_keep_fwd: keep", keep)
+    S, k = keep.shape
+    d = emb.shape[-1]
+    assert emb.is_contiguous() and cls.is_contiguous() and pos.is_contiguous()
+    assert cls.dtype == torch.float32 and pos.dtype == torch.float32 and pos.dim() == 3
+    if emb.numel() != S * k * d:
+        raise ValueError(f"tokens_assemble_keep_fwd: emb {tuple(emb.shape)} does not hold [S*k, d] for keep {tuple(keep.shape)}")
+    T, pos_rows = pos.shape[0], pos.shape[1]
+    out = torch.empty((S, k + 1, d), dtype=emb.dtype, device=emb.device)
+    with _timed(("hbm", "tokens_assemble_keep_fwd", emb.numel()), (emb.numel() + 2 * out.numel()) * emb.element_size()):
+        L.check(L.load().dvt_tokens_assemble_keep_fwd(emb.data_ptr(), cls.data_ptr(), pos.data_ptr(), keep.data_ptr(),
+                                                      out.data_ptr(), S, T, pos_rows - 1, k, d, pos_rows, dt(emb), _stream()),
+                "dvt_tokens_assemble_keep_fwd")
+    return out
+
+
+def tokens_assemble_keep_bwd(dout: Tensor, T: int, pos_rows: int, slot: Tensor, *, dcls: Optional[Tensor] = None,
+                             dpos: Optional[Tensor] = None, accumulate: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """dout [S, k+1, d], slot [S, n] -> (demb [S*k, d], dcls [d], dpos [T, pos_rows, d]); dcls / dpos may be caller-owned
+    fp32 destinations (gradient sinks).  A positional row nobody kept gets exactly zero when overwriting and stays as it is
+    when accumulating.  Deterministic: the sum over the clips of a position runs in ascending clip order."""
+    _need_cuda(dout)
+    dout = dout.contiguous()
+    S, k1, d = dout.shape
+    k = k1 - 1
+    slot = _index_table("tokens_assemble_keep_bwd: slot", slot, rows=S)
+    n = slot.shape[1]
+    if pos_rows < n + 1:
+        raise ValueError(f"tokens_assemble_keep_bwd: the positional table has {pos_rows} rows < n + 1 = {n + 1}")
+    demb = torch.empty((S * k, d), dtype=dout.dtype, device=dout.device)
+    if dcls is None:
+        assert not accumulate
+        dcls = torch.empty((d,), dtype=torch.float32, device=dout.device)
+    if dpos is None:
+        assert not accumulate
+        dpos = torch.empty((T, pos_rows, d), dtype=torch.float32, device=dout.device)
+    assert dcls.is_contiguous() and dpos.is_contiguous() and dcls.numel() == d and dpos.numel() == T * pos_rows * d
+    L.check(L.load().dvt_tokens_assemble_keep_bwd(dout.data_ptr(), slot.data_ptr(), demb.data_ptr(), dcls.data_ptr(),
+                                                  dpos.data_ptr(), S, T, n, k, d, pos_rows, dt(dout), int(accumulate),
+                                                  _stream()), "dvt_tokens_assemble_keep_bwd")
+    return demb, dcls, dpos
+
 def tokens_assemble_fwd(emb: Tensor, cls: Tensor, pos: Tensor, S: int, T: int, n: int) -> Tensor:
     """emb [S*n, d]; cls [d] f32; pos [T, rows>=n+1, d] f32 -> [S, n+1, d]."""
     _need_cuda(emb, cls, pos)

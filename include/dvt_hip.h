@@ -161,6 +161,56 @@ int dvt_tokens_assemble_bwd(const void* dout, void* demb, float* dcls, float* dp
                             int64_t T, int64_t n, int64_t d, int64_t pos_rows, int dtype,
                             int accumulate, dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- patch dropout (csrc/patch_dropout.hip)
+ * The tokeniser of src/models/vit.py:110-116 on a kept subset of the patch tokens (tube masking as in VideoMAE, or drawn
+ * per frame as in PatchDropout; the reference has neither).  A clip [b, t, C, H, W] at patch P and tubelet pt has
+ * S = b * (t / pt) sequences of n = (H/P) * (W/P) positions; a sequence keeps k of them:
+ *   keep [S, k] int32, strictly ascending per row;  slot [S, n] int32, the inverse map, -1 for a dropped position.
+ * The kernels that read keep / slot treat an entry of keep outside [0, n) or of slot outside [0, k) as dropped: no address
+ * is formed from it.
+ *
+ * Selection (specialises the row choice of vit.py:110-116): keys [R, n] int32; position i of a row is kept iff fewer than k
+ * positions j have (key_j, j) < (key_i, i) in signed order, ties to the lower position -- the first k of a stable argsort;
+ * the output index of a kept position is the number of kept positions below it.  Every key row is written rows_per times
+ * (rows r * rows_per .. of keep / slot): tube masking is R = b, rows_per = t / pt; per frame R = b * t / pt, rows_per = 1.
+ * DVT_ERR_BAD_ARG before any launch unless 1 <= n <= 1024, 1 <= k <= n, rows_per >= 1.  Integer work, no atomics. */
+int dvt_keep_select(const int32_t* keys, int64_t R, int n, int k, int rows_per, int32_t* keep, int32_t* slot,
+                    dvt_stream_t stream);
+/* The same selection, in one launch, on keys drawn on the device (vit.py:110-116 in training mode): key(r, i) is, as int32,
+ * Philox4x32-10 word (e & 3) of counter rng_state[1] + call_offset + e / 4 under key rng_state[0], e = r * n + i -- the
+ * generator and the device state {seed, step base} of dvt_dropout (a site takes ceil(R * n / 4) blocks), so a captured
+ * hipGraph draws a new subset on every replay once dvt_rng_advance has moved the base.  keys_out (nullable, [R, n]) receives
+ * the keys; keep and slot are given together, or both NULL with keys_out (keys only). */
+int dvt_keep_draw(const uint64_t* rng_state, uint64_t call_offset, int64_t R, int n, int k, int rows_per, int32_t* keep,
+                  int32_t* slot, int32_t* keys_out, dvt_stream_t stream);
+/* slot [S, n] of a caller's keep [S, k] (vit.py:110-116 with the rows chosen by the caller); same argument ranges. */
+int dvt_keep_slots(const int32_t* keep, int64_t S, int n, int k, int32_t* slot, dvt_stream_t stream);
+/* Kept gather (the Rearrange of vit.py:110 on the kept patches): dvt_tubelet_patchify's element order, kept rows only,
+ *   out[s*k + i, ((kf*P + p1)*P + p2)*C + c] = x[s*pt + kf, c, ph*P + p1, pw*P + p2],  ph*nw + pw = keep[s, i];
+ * out: [(frames / pt) * k, pt*P*P*C].  Reads only the kept patches.  Same argument checks and dtype pairs as
+ * dvt_tubelet_patchify, and 1 <= k <= n. */
+int dvt_patchify_keep(const void* x, int x_dtype, void* out, int out_dtype, const int32_t* keep, int64_t frames, int C, int H,
+                      int W, int P, int pt, int k, dvt_stream_t stream);
+/* Its adjoint (vit.py:110 in backward): writes EVERY pixel of dx [frames, C, H, W] exactly once -- a pixel of a kept patch
+ * from row s*k + slot[s, position] of dout, a pixel of a dropped patch zero.  No pre-zeroing, no atomics. */
+int dvt_patchify_keep_bwd(const void* dout, int dout_dtype, void* dx, int dx_dtype, const int32_t* slot, int64_t frames, int C,
+                          int H, int W, int P, int pt, int k, dvt_stream_t stream);
+/* Token assembly on kept rows (vit.py:113-115):
+ *   out[s, 0, :]   = cls[:]           + pos[s % T, 0, :]
+ *   out[s, 1+i, :] = emb[s*k + i, :]  + pos[s % T, 1 + keep[s, i], :]
+ * emb: [S*k, d] dtype; cls: [d] f32; pos: [T, pos_rows, d] f32 (pos_rows >= n+1); out: [S, k+1, d] dtype. */
+int dvt_tokens_assemble_keep_fwd(const void* emb, const float* cls, const float* pos, const int32_t* keep, void* out,
+                                 int64_t S, int64_t T, int n, int k, int64_t d, int64_t pos_rows, int dtype,
+                                 dvt_stream_t stream);
+/* Backward of the above (vit.py:113-115): demb [S*k, d] = dout[:, 1:, :]; dcls (+)= sum_s dout[s, 0, :];
+ * dpos[tau, 0, :] (+)= sum_b dout[b*T + tau, 0, :]; dpos[tau, 1+j, :] (+)= the sum, over those b with
+ * slot[b*T + tau, j] >= 0 in ascending b, of dout[b*T + tau, 1 + slot, :] -- a fixed order, no float atomics.  A row of dpos
+ * whose position nobody kept (and every row above n) gets exactly zero when overwriting and is not touched when
+ * `accumulate` != 0.  slot must be the inverse of a keep [S, k]: demb is written from the rows slot names. */
+int dvt_tokens_assemble_keep_bwd(const void* dout, const int32_t* slot, void* demb, float* dcls, float* dpos, int64_t S,
+                                 int64_t T, int n, int k, int64_t d, int64_t pos_rows, int dtype, int accumulate,
+                                 dvt_stream_t stream);
+
 /* Row gather with an optional leading token (vit.py:120-123, x[:, 0] then
  * cat(temporal_token, .)):  out[b, 0, :] = tok (if tok != NULL, then lead = 1)
  * out[b, lead + t, :] = src[(b*T + t) * src_row_stride : + d].  */
