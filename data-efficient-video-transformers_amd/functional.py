@@ -688,8 +688,9 @@ class _AttnBlock(torch.autograd.Function):
         M = x2.shape[0]
         T = x.dtype if cdt is None else cdt
         ctx.mixed = mixed = T != x.dtype
-        if mixed and not (x.dtype == torch.float32 and prenorm and residual and w_out is not None and attn_dropout == 0.0):
-            raise ValueError("the fp32 stream form is the pre-norm residual block with an output projection")
+        # (residual False: the un-added branch of an fp32 stream, fp32 out -- stochastic depth, drop_path_block)
+        if mixed and not (x.dtype == torch.float32 and prenorm and w_out is not None and attn_dropout == 0.0):
+            raise ValueError("the fp32 stream form is the pre-norm block with an output projection")
         if prenorm:
             g, bb = _f32(ln_w), _f32(ln_b)
             xn, mean, rstd = ops.layernorm_fwd(x2, g, bb, eps, out_dtype=T)
@@ -716,7 +717,7 @@ class _AttnBlock(torch.autograd.Function):
                 y = ops.linear_fwd(o2, wo, _f32(b_out), epilogue=L.EPI_RESIDUAL, residual=x2,
                                    out_dtype=torch.float32 if mixed else None)
             else:
-                y = ops.linear_fwd(o2, wo, _f32(b_out))
+                y = ops.linear_fwd(o2, wo, _f32(b_out), out_dtype=torch.float32 if mixed else None)
         else:
             wo = None
             y = ops.add(o2, x2) if residual else o2
@@ -753,7 +754,7 @@ class _AttnBlock(torch.autograd.Function):
         dwq, dbq, dxn = _linear_bwd(ctx.sinks[2], ctx.sinks[5], dqkv, xn, wq, has_qkv_bias)                    # dxn [M, d]
         dg = db = None
         if ctx.mixed:
-            dx, dg, db, dx_lp = _ln_bwd(dxn, x2, g, mean, rstd, ctx.sinks[0], ctx.sinks[1], dx_add=dy32,
+            dx, dg, db, dx_lp = _ln_bwd(dxn, x2, g, mean, rstd, ctx.sinks[0], ctx.sinks[1], dx_add=dy32 if residual else None,
                                         dx_dtype=torch.float32, dx_lp=T)
             _lp_put(dx, dx_lp)
         elif prenorm:
@@ -1016,8 +1017,8 @@ class _MlpBlock(torch.autograd.Function):
             x2 = x2.contiguous()
         T = x.dtype if cdt is None else cdt
         ctx.mixed = mixed = T != x.dtype                 # fp32 residual stream, 16-bit GEMM operands (see _lp_hand)
-        if mixed and not (x.dtype == torch.float32 and prenorm and residual):
-            raise ValueError("the fp32 stream form is the pre-norm residual block")
+        if mixed and not (x.dtype == torch.float32 and prenorm):      # residual False: the un-added branch, fp32 out
+            raise ValueError("the fp32 stream form is the pre-norm block")
         if prenorm:
             g, bb = _f32(ln_w), _f32(ln_b)
             xn, mean, rstd = ops.layernorm_fwd(x2, g, bb, eps, out_dtype=T)
@@ -1036,7 +1037,7 @@ class _MlpBlock(torch.autograd.Function):
             y = ops.linear_fwd(h, w2c, _f32(b2), epilogue=L.EPI_RESIDUAL, residual=x2,
                                out_dtype=torch.float32 if mixed else None)
         else:
-            y = ops.linear_fwd(h, w2c, _f32(b2))
+            y = ops.linear_fwd(h, w2c, _f32(b2), out_dtype=torch.float32 if mixed else None)
         ctx.save_for_backward(x2, g, mean, rstd, xn if prenorm else None, w1c, w2c, u, h)
         ctx.cfg = (act, prenorm, residual, b1 is not None, b2 is not None)
         ctx.xshape = shp
@@ -1065,7 +1066,8 @@ class _MlpBlock(torch.autograd.Function):
         dw1, db1, dxn = _linear_bwd(sk[2], sk[3], du, xn, w1c, has_b1)
         dg = db = None
         if ctx.mixed:
-            dx, dg, db, dx_lp = _ln_bwd(dxn, x2, g, mean, rstd, sk[0], sk[1], dx_add=dy32, dx_dtype=torch.float32, dx_lp=T)
+            dx, dg, db, dx_lp = _ln_bwd(dxn, x2, g, mean, rstd, sk[0], sk[1], dx_add=dy32 if residual else None,
+                                        dx_dtype=torch.float32, dx_lp=T)
             _lp_put(dx, dx_lp)
         elif prenorm:
             dx, dg, db = _ln_bwd(dxn, x2, g, mean, rstd, sk[0], sk[1], dx_add=dy2 if residual else None)
@@ -2123,6 +2125,52 @@ def checkpoint(fn, x: Tensor, params=()) -> Tensor:
     if not torch.is_grad_enabled():
         return fn(x)
     return _Checkpoint.apply(fn, x, *params)
+
+
+# ---------------------------------------------------------------------------
+# Stochastic depth on whole sequences (csrc/drop_path.hip): a residual branch on a subset of the sequences of a stack
+# ---------------------------------------------------------------------------
+class _DropPathBlock(torch.autograd.Function):
+    """out = x + alpha * scatter(branch(x[keep])) -- timm's DropPath on ``x = fn(x) + x`` (vit.py:73-74) with the branch run on
+    the kept sequences only.  The branch is recorded in forward on a detached copy of the gathered rows (its activations are
+    those of k sequences); backward gathers the kept rows of the gradient scaled by alpha, back-propagates through the branch
+    (parameter gradients leave through the inner backward, as in ``_Checkpoint``) and writes the input's gradient
+    ``g + scatter(dxg)`` in one launch.  ``gather_input`` False: keep names every sequence or -1 (a Bernoulli draw, k = S) and
+    the branch runs on x itself -- the sequences of a stack do not meet inside a branch, so a dropped one only costs time."""
+
+    @staticmethod
+    def forward(ctx, x, branch, keep, slot, alpha, gather_input, *params):
+        x = x.contiguous()
+        xg = ops.seq_gather(x, keep, 1.0) if gather_input else x.detach()
+        xin = xg.requires_grad_(True)
+        with torch.enable_grad():
+            yb = branch(xin)
+        ctx.xin, ctx.yb = xin, yb
+        ctx.keep, ctx.slot, ctx.alpha = keep, slot, alpha
+        return ops.seq_scatter_add(x, yb.detach(), slot, alpha)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        xin, yb = ctx.xin, ctx.yb
+        ctx.xin = ctx.yb = None
+        dyb = ops.seq_gather(g, ctx.keep, ctx.alpha)
+        torch.autograd.backward(yb, _as(dyb, yb.dtype).view(yb.shape))
+        dx = ops.seq_scatter_add(g, _as(xin.grad.contiguous(), g.dtype), ctx.slot, 1.0)
+        return (dx,) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
+def drop_path_block(x: Tensor, branch, keep: Tensor, slot: Tensor, alpha: float, params=(), gather_input: bool = True) -> Tensor:
+    """x [S, N, d]; ``branch``: a callable returning the UN-ADDED branch output for the rows it is given; keep [k] int32
+    (ascending unique sequence indices, or -1 = dropped), slot [S] int32 its inverse (-1 = dropped)
+    -> x + alpha * scatter(branch(gather(x, keep))).  The subset is the caller's: under ``checkpoint`` draw it outside the
+    recomputed closure, so that the recomputation sees the same one without drawing a site again.  ``params``: the branch's
+    parameters (they make the output require grad when x does not)."""
+    if not torch.is_grad_enabled():
+        x = x.contiguous()
+        yb = branch(ops.seq_gather(x, keep, 1.0) if gather_input else x)
+        return ops.seq_scatter_add(x, yb, slot, alpha)
+    return _DropPathBlock.apply(x, branch, keep, slot, float(alpha), bool(gather_input), *params)
 
 
 # ---------------------------------------------------------------------------

@@ -22,6 +22,16 @@ state-dict keys stay the reference's; ``to_patch_embedding.1.weight`` is ``[dim,
 k = n - floor(patch_dropout * n) patch tokens per sequence (csrc/patch_dropout.hip): ``"tube"`` keeps the same positions in
 every temporal token of a clip (VideoMAE's tube masking), ``"frame"`` draws per temporal token (PatchDropout).  ``forward``
 and ``loss`` also take a caller's ``keep [S, k]`` (int32, ascending rows), used as given in training and in eval.
+``drop_path`` / ``drop_path_mode`` -- stochastic depth in training (csrc/drop_path.hip).  The rate rises linearly from 0 to
+``drop_path`` over the 2 * depth layers in execution order (space stack first; timm's ``linspace`` rule); the attention
+branch and the MLP branch of a layer draw independently at the layer's rate p.  ``"subset"``: a branch runs on exactly
+k = S - floor(p S) of the S sequences of its stack, drawn on the device, and is added back scaled by S / k (DINOv2's
+efficient stochastic depth) -- S = b * t' in the space stack and S = b in the temporal stack, so at b = 8 a rate below 1/8
+drops nothing there; S <= 1024.  ``"bernoulli"``: timm's rule -- every sequence is dropped independently with probability
+p, the branch runs on all of them, scale 1 / (1 - p).  ``ViViT.drop_keep`` (None, or one entry per residual branch in
+execution order: 2 * depth of the space stack, then 2 * depth of the temporal stack; an entry is None -- the branch runs
+fused on all sequences -- or an int32 device tensor [k] of ascending unique sequence indices) replaces the draws, in
+training and in eval; it is checked on the host for type, shape and device only.
 """
 from __future__ import annotations
 
@@ -31,6 +41,8 @@ import torch
 from torch import nn
 
 from .. import functional as F
+
+_BY_RATE = object()       # "no plan of this forward is known: judge stochastic depth by the rates"
 
 
 class Patchify(nn.Module):
@@ -156,16 +168,27 @@ class Attention(nn.Module):
 class Transformer(nn.Module):
     """vit.py:60-75: depth x [x = attn(LN x) + x; x = ff(LN x) + x], final LayerNorm."""
 
-    def __init__(self, dim, depth, heads, dim_head, mlp_dim, dropout=0.):
+    def __init__(self, dim, depth, heads, dim_head, mlp_dim, dropout=0., drop_path=None):
         super().__init__()
         self.layers = nn.ModuleList([])
         self.norm = nn.LayerNorm(dim)
         self.checkpoint = False          # build-side: recompute each block in backward (saves ~11 of 12 activations)
+        rates = [0.0] * depth if drop_path is None else [float(p) for p in drop_path]
+        if len(rates) != depth or not all(0.0 <= p < 1.0 for p in rates):
+            raise ValueError(f"drop_path must be {depth} per-layer rates in [0, 1), got {drop_path!r}")
+        self.drop_path_rates = rates     # build-side: stochastic depth of layer i's two branches (no parameter, no buffer)
         for _ in range(depth):
             self.layers.append(nn.ModuleList([
                 PreNorm(dim, Attention(dim, heads=heads, dim_head=dim_head, dropout=dropout)),
                 PreNorm(dim, FeedForward(dim, mlp_dim, dropout=dropout)),
             ]))
+
+    def _drop_live(self, plan, rates) -> bool:
+        """Does stochastic depth act on the branches ``rates`` / ``plan`` speak of?  Without a plan: while training at a
+        non-zero rate.  With the plan of a forward (a caller's ``drop_keep``): where an entry names a subset."""
+        if plan is _BY_RATE:
+            return self.training and any(p > 0.0 for p in rates)
+        return plan is not None and any(e is not None for e in plan)
 
     def stream_f32_ok(self, rows: int, cdt: torch.dtype) -> bool:
         """May this stack run on an fp32 residual stream with ``cdt`` GEMM operands for ``rows`` rows?  (The launch-bound
@@ -180,35 +203,73 @@ class Transformer(nn.Module):
         from .. import ops
         return ops.gemm_is_launch_bound(rows, d, inner, cdt) and ops.gemm_is_launch_bound(rows, d, hidden, cdt)
 
-    def forward_layers(self, x, cdt=None):
-        """All residual blocks, without the final norm.  cdt: GEMM operand type when x is an fp32 stream."""
-        for attn, ff in self.layers:
+    def _block(self, attn, ff, cdt, da, df):
+        """x -> one layer.  da / df: None (the fused residual route) or (keep, slot, alpha, gather_input) -- the attention /
+        feed-forward branch on a subset of the sequences (F.drop_path_block; the blocks give their un-added form)."""
+        def a_branch(t):
+            return attn.fn(t, _norm=attn.norm, _residual=False, _cdt=cdt)
+
+        def f_branch(t):
+            return ff.fn(t, _norm=ff.norm, _residual=False, _cdt=cdt)
+
+        def block(t):
+            if da is None:
+                t = attn.fn(t, _norm=attn.norm, _residual=True, _cdt=cdt)
+            else:
+                t = F.drop_path_block(t, a_branch, da[0], da[1], da[2], tuple(attn.parameters()), da[3])
+            if df is None:
+                return ff.fn(t, _norm=ff.norm, _residual=True, _cdt=cdt)
+            return F.drop_path_block(t, f_branch, df[0], df[1], df[2], tuple(ff.parameters()), df[3])
+        return block
+
+    def forward_layers(self, x, cdt=None, drops=None):
+        """All residual blocks, without the final norm.  cdt: GEMM operand type when x is an fp32 stream.  drops: None, or
+        one entry per residual branch in execution order (2 per layer), as ``_block`` takes them -- made before the blocks
+        run, so a checkpointed block recomputes on the subset it ran on."""
+        for i, (attn, ff) in enumerate(self.layers):
+            da, df = (None, None) if drops is None else (drops[2 * i], drops[2 * i + 1])
+            if da is None and df is None:
+                if self.checkpoint and self.training and torch.is_grad_enabled():
+                    def block(t, attn=attn, ff=ff):
+                        t = attn.fn(t, _norm=attn.norm, _residual=True, _cdt=cdt)
+                        return ff.fn(t, _norm=ff.norm, _residual=True, _cdt=cdt)
+                    x = F.checkpoint(block, x, tuple(attn.parameters()) + tuple(ff.parameters()))
+                else:
+                    x = attn.fn(x, _norm=attn.norm, _residual=True, _cdt=cdt)
+                    x = ff.fn(x, _norm=ff.norm, _residual=True, _cdt=cdt)
+                continue
+            block = self._block(attn, ff, cdt, da, df)
             if self.checkpoint and self.training and torch.is_grad_enabled():
-                def block(t, attn=attn, ff=ff):
-                    t = attn.fn(t, _norm=attn.norm, _residual=True, _cdt=cdt)
-                    return ff.fn(t, _norm=ff.norm, _residual=True, _cdt=cdt)
                 x = F.checkpoint(block, x, tuple(attn.parameters()) + tuple(ff.parameters()))
             else:
-                x = attn.fn(x, _norm=attn.norm, _residual=True, _cdt=cdt)
-                x = ff.fn(x, _norm=ff.norm, _residual=True, _cdt=cdt)
+                x = block(x)
         return x
 
-    def cls_prunable(self) -> bool:
+    def cls_prunable(self, plan=_BY_RATE) -> bool:
         """True when the last layer may be evaluated for row 0 only (``forward_layers_cls``)."""
         if len(self.layers) == 0:
             return False
         attn = self.layers[-1][0].fn
         dropping = self.training and (attn.dropout_p > 0.0 or self.layers[-1][1].fn.dropout_p > 0.0)
+        if self._drop_live(plan if plan is _BY_RATE or plan is None else plan[-2:], self.drop_path_rates[-1:]):
+            dropping = True                                                  # the CLS route has no un-added form
         return attn.project_out and not dropping
 
-    def forward_layers_cls(self, x, cdt=None):
+    def forward_layers_cls(self, x, cdt=None, drops=None):
         """``forward_layers(x)[:, 0]`` for x [S, N, d] -> [S, d]: what the reference reads of the space
         transformer (vit.py:119-120) and, under pool == 'cls', of the temporal one (:126).  In the last
         layer only the keys and values are computed for all rows; query, attention, output projection and
         the whole feed-forward run on row 0 of every sequence (F.attn_block_cls)."""
         *head, (attn, ff) = self.layers
-        for a, f in head:
-            if self.checkpoint and self.training and torch.is_grad_enabled():
+        if drops is not None and (drops[-1] is not None or drops[-2] is not None):
+            raise ValueError("drop_path: the CLS route of the last layer has no un-added form")
+        for i, (a, f) in enumerate(head):
+            da, df = (None, None) if drops is None else (drops[2 * i], drops[2 * i + 1])
+            if da is not None or df is not None:
+                block = self._block(a, f, cdt, da, df)
+                x = (F.checkpoint(block, x, tuple(a.parameters()) + tuple(f.parameters()))
+                     if self.checkpoint and self.training and torch.is_grad_enabled() else block(x))
+            elif self.checkpoint and self.training and torch.is_grad_enabled():
                 def block(t, a=a, f=f):
                     t = a.fn(t, _norm=a.norm, _residual=True, _cdt=cdt)
                     return f.fn(t, _norm=f.norm, _residual=True, _cdt=cdt)
@@ -227,8 +288,8 @@ class Transformer(nn.Module):
             return F.checkpoint(last, x, tuple(attn.parameters()) + tuple(ff.parameters()))
         return last(x)
 
-    def forward(self, x, cdt=None):
-        x = self.forward_layers(x, cdt)
+    def forward(self, x, cdt=None, drops=None):
+        x = self.forward_layers(x, cdt, drops)
         return F.layernorm(x, self.norm.weight, self.norm.bias, self.norm.eps)
 
 
@@ -238,7 +299,8 @@ class ViViT(nn.Module):
     def __init__(self, image_size, patch_size, num_classes, num_frames, dim=192, depth=4, heads=3,
                  pool='cls', in_channels=3, dim_head=64, dropout=0., emb_dropout=0., scale_dim=4, *,
                  compute_dtype: torch.dtype = torch.bfloat16, activation_checkpointing: bool = False,
-                 patch_dropout: float = 0.0, patch_dropout_mode: str = "tube", tubelet_size: int = 1):
+                 patch_dropout: float = 0.0, patch_dropout_mode: str = "tube", drop_path: float = 0.0,
+                 drop_path_mode: str = "subset", tubelet_size: int = 1):
         super().__init__()
         assert pool in {'cls', 'mean'}, 'pool type must be either cls (cls token) or mean (mean pooling)'
         assert image_size % patch_size == 0, 'Image dimensions must be divisible by the patch size.'
@@ -252,6 +314,15 @@ class ViViT(nn.Module):
         self.patch_dropout = float(patch_dropout)
         self.patch_dropout_mode = patch_dropout_mode
         self.num_kept(num_patches)             # ValueError unless 0 <= patch_dropout < 1 and k >= 1
+        if isinstance(drop_path, bool) or not isinstance(drop_path, (int, float)) or not 0.0 <= drop_path < 1.0:
+            raise ValueError(f"drop_path must be a rate in [0, 1), got {drop_path!r}")
+        if drop_path_mode not in ("subset", "bernoulli"):
+            raise ValueError(f"drop_path_mode must be 'subset' or 'bernoulli', got {drop_path_mode!r}")
+        self.drop_path = float(drop_path)
+        self.drop_path_mode = drop_path_mode
+        self.drop_keep = None                  # a caller's subsets, one entry per residual branch (see the module docstring)
+        self.last_drop_plan = None             # what the last forward ran on: per branch None or (keep, slot, alpha, gather)
+        rates = self.drop_path_rates(depth, self.drop_path)
         patch_dim = tubelet_size * in_channels * patch_size ** 2
         self.to_patch_embedding = nn.Sequential(
             Patchify(patch_size, tubelet_size),
@@ -259,9 +330,9 @@ class ViViT(nn.Module):
         )
         self.pos_embedding = nn.Parameter(torch.randn(1, num_frames // tubelet_size, num_patches + 1, dim))
         self.space_token = nn.Parameter(torch.randn(1, 1, dim))
-        self.space_transformer = Transformer(dim, depth, heads, dim_head, dim * scale_dim, dropout)
+        self.space_transformer = Transformer(dim, depth, heads, dim_head, dim * scale_dim, dropout, rates[:depth])
         self.temporal_token = nn.Parameter(torch.randn(1, 1, dim))
-        self.temporal_transformer = Transformer(dim, depth, heads, dim_head, dim * scale_dim, dropout)
+        self.temporal_transformer = Transformer(dim, depth, heads, dim_head, dim * scale_dim, dropout, rates[depth:])
         self.dropout = nn.Dropout(emb_dropout)
         self.pool = pool
         self.mlp_head = nn.Sequential(
@@ -287,6 +358,20 @@ class ViViT(nn.Module):
         if k < 1:
             raise ValueError(f"patch_dropout = {p!r} keeps no patch of {n}")
         return k
+
+    @staticmethod
+    def drop_path_rates(depth: int, drop_path: float):
+        """The rate of each of the 2 * depth layers in execution order (space stack first): linear from 0 to ``drop_path``
+        (timm: ``torch.linspace(0, drop_path_rate, number of layers)``)."""
+        n = 2 * depth
+        return [drop_path * i / (n - 1) if n > 1 else drop_path for i in range(n)]
+
+    @staticmethod
+    def drop_path_kept(S: int, p: float) -> int:
+        """k = S - floor(p S): the sequences of a stack of S a branch at rate p runs on in ``"subset"`` mode."""
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"drop_path: rate {p!r} outside [0, 1)")
+        return S - math.floor(p * S)
 
     def forward(self, x, keep=None):
         pooled, pending = self._trunk(x, keep)
@@ -371,6 +456,70 @@ class ViViT(nn.Module):
         R, rows_per = (S // t, t) if self.patch_dropout_mode == "tube" else (S, 1)
         return ops.keep_draw(R, n, k, F._rng.tensor(x.device), F._rng.take(R * n), rows_per)
 
+    def _drop_plan(self, x, S_space: int, S_time: int):
+        """-> (space entries, temporal entries, by_caller): per residual branch None (fused, all sequences) or
+        (keep, slot, alpha, gather_input), or (None, None, False) when stochastic depth does not act.  Every subset is made
+        here, before any block runs.  A caller's ``drop_keep`` is checked on the host only: no device value is read."""
+        from .. import ops
+        st, tt = self.space_transformer, self.temporal_transformer
+        nb = 2 * len(st.layers)
+        stacks = ((st, S_space), (tt, S_time))
+        dk = self.drop_keep
+        if dk is not None:
+            if not isinstance(dk, (list, tuple)) or len(dk) != 2 * nb:
+                raise ValueError(f"drop_keep must be a sequence of {2 * nb} entries (one per residual branch: {nb} of the "
+                                 f"space stack, then {nb} of the temporal stack), got "
+                                 f"{len(dk) if isinstance(dk, (list, tuple)) else type(dk).__name__}")
+            plans = []
+            for si, (stack, S) in enumerate(stacks):
+                plan = []
+                for j in range(nb):
+                    e = dk[si * nb + j]
+                    if e is None:
+                        plan.append(None)
+                        continue
+                    if (not isinstance(e, torch.Tensor) or e.dtype != torch.int32 or e.dim() != 1
+                            or not 1 <= e.numel() <= S):
+                        raise ValueError(f"drop_keep[{si * nb + j}] must be None or an int32 tensor [k] with 1 <= k <= {S}, "
+                                         f"got {getattr(e, 'dtype', type(e))} of shape {tuple(getattr(e, 'shape', ()))}")
+                    if e.device != x.device:
+                        raise ValueError(f"drop_keep[{si * nb + j}] is on {e.device}, the clip on {x.device}")
+                    if S > ops.DROP_PATH_MAX_SEQS:
+                        raise ValueError(f"drop_keep: a subset of S = {S} sequences; the limit is {ops.DROP_PATH_MAX_SEQS}")
+                    e = e.contiguous()
+                    k = e.numel()
+                    p = stack.drop_path_rates[j // 2]
+                    alpha = S / k if self.drop_path_mode == "subset" else 1.0 / (1.0 - p)
+                    plan.append((e, ops.keep_slots(e.view(1, k), S).view(S), alpha, True))
+                plans.append(plan)
+            return plans[0], plans[1], True
+        if not (self.training and self.drop_path > 0.0):
+            return None, None, False
+        state = F._rng.tensor(x.device)
+        plans = []
+        for stack, S in stacks:
+            plan = []
+            for j in range(nb):
+                p = stack.drop_path_rates[j // 2]
+                if self.drop_path_mode == "bernoulli":
+                    if p > 0.0:
+                        m = ops.drop_path_draw(S, p, state, F._rng.take(S))
+                        plan.append((m, m, 1.0 / (1.0 - p), False))
+                    else:
+                        plan.append(None)
+                    continue
+                if p > 0.0 and S > ops.DROP_PATH_MAX_SEQS:
+                    raise ValueError(f"drop_path_mode='subset' draws from at most {ops.DROP_PATH_MAX_SEQS} sequences, this "
+                                     f"stack has S = {S}; use drop_path_mode='bernoulli' or a smaller batch")
+                k = self.drop_path_kept(S, p)
+                if k == S:
+                    plan.append(None)
+                else:
+                    kp, sl = ops.keep_draw(1, S, k, state, F._rng.take(S))
+                    plan.append((kp.view(k), sl.view(S), S / k, True))
+            plans.append(plan)
+        return plans[0], plans[1], False
+
     def _trunk(self, x, keep=None):
         """-> (pooled [b, dim], the LayerNorm still to be applied to it or None)."""
         if x.dim() != 5:
@@ -382,6 +531,9 @@ class ViViT(nn.Module):
         t //= self.tubelet_size                 # temporal tokens: everything below sees a clip of t tubelets
         T = self.compute_dtype
         F.lp_clear()            # 16-bit gradient copies a previous step's backward left untaken (functional._lp_hand)
+        sd, td, planned = self._drop_plan(x, b * t, b)          # stochastic depth: every subset of this step, or None
+        self.last_drop_plan = None if sd is None else sd + td
+        sp, tp = ((sd, td) if planned else (_BY_RATE, _BY_RATE))
         n = (x.shape[3] // self.patch_size) * (x.shape[4] // self.patch_size)
         pe = self.to_patch_embedding[1]
         keep, slot = self._kept_rows(x, keep, b * t, t, n)
@@ -394,10 +546,10 @@ class ViViT(nn.Module):
         tok = F.dropout(tok, self.emb_dropout_p, self.training)                            # :116
         st, tt = self.space_transformer, self.temporal_transformer
         sn = st.norm
-        if st.cls_prunable():                                                       # only x[:, 0] is read (:120)
-            s = st.forward_layers_cls(tok).view(b * t, 1, -1)
+        if st.cls_prunable(sp):                                                     # only x[:, 0] is read (:120)
+            s = st.forward_layers_cls(tok, drops=sd).view(b * t, 1, -1)
         else:
-            s = st.forward_layers(tok)                                              # :118-119
+            s = st.forward_layers(tok, drops=sd)                                    # :118-119
         # The temporal stack and the heads are the launch-bound zone of the step (b (t + 1) rows: 264 at the metric shape):
         # single rows carry whole gradients there and nothing averages the rounding of 16-bit storage, while fp32 storage
         # of so few rows costs no bandwidth -- its residual stream and row gradients are kept in fp32 (GEMM operands stay T).
@@ -405,7 +557,7 @@ class ViViT(nn.Module):
         cdt = T if zone32 else None
         seq = F.cls_norm_concat(s, sn.weight, sn.bias, self.temporal_token, b, t, sn.eps,
                                 out_dtype=torch.float32 if zone32 else None)       # :119-123
-        if self.pool == 'cls' and tt.cls_prunable():                                # only x[:, 0] is read (:126)
-            return tt.forward_layers_cls(seq, cdt), tt.norm
-        z = tt(seq, cdt)                                                            # :125
+        if self.pool == 'cls' and tt.cls_prunable(tp):                              # only x[:, 0] is read (:126)
+            return tt.forward_layers_cls(seq, cdt, td), tt.norm
+        z = tt(seq, cdt, td)                                                        # :125
         return (F.mean_rows(z) if self.pool == 'mean' else F.select_first_row(z)), None  # :126

@@ -409,6 +409,87 @@ def tokens_assemble_keep_bwd(dout: Tensor, T: int, pos_rows: int, slot: Tensor, 
                                                   _stream()), "dvt_tokens_assemble_keep_bwd")
     return demb, dcls, dpos
 
+
+# ------------------------------------------------------------------ stochastic depth (csrc/drop_path.hip)
+DROP_PATH_MAX_SEQS = 1024          # sequences a fixed-size subset is drawn from: keep_draw holds the selection in LDS
+
+
+def _seq_index(what: str, t: Tensor, count: Optional[int], like: Tensor) -> Tensor:
+    """A 1-D int32 device vector of sequence indices (idx, slot or a Bernoulli draw); ValueError otherwise."""
+    if not isinstance(t, Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() < 1:
+        raise ValueError(f"{what}: expected a non-empty 1-D int32 tensor, got {getattr(t, 'dtype', type(t))} "
+                         f"of shape {tuple(getattr(t, 'shape', ()))}")
+    if count is not None and t.numel() != count:
+        raise ValueError(f"{what}: {t.numel()} entries where {count} are expected")
+    if t.device != like.device:
+        raise ValueError(f"{what}: on {t.device}, the data on {like.device}")
+    return t.contiguous()
+
+
+def _seq_rows(what: str, x: Tensor) -> Tuple[int, int]:
+    if not isinstance(x, Tensor) or x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"{what}: expected [S, ...] with at least two dimensions and no empty one, got "
+                         f"{tuple(getattr(x, 'shape', ()))}")
+    if x.dtype not in _DT:
+        raise ValueError(f"{what}: dtype {x.dtype} is not float32, bfloat16 or float16")
+    return x.shape[0], x.numel() // x.shape[0]
+
+
+def seq_gather(x: Tensor, idx: Tensor, alpha: float = 1.0) -> Tensor:
+    """x [S, ...], idx [k] int32 -> y [k, ...]: y[j] = alpha * x[idx[j]] where 0 <= idx[j] < S, a row of zeros otherwise
+    (-1 = dropped)."""
+    S, L_ = _seq_rows("seq_gather: x", x)
+    idx = _seq_index("seq_gather: idx", idx, None, x)
+    _need_cuda(x, idx)
+    x = x.contiguous()
+    k = idx.numel()
+    y = torch.empty((k,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    with _timed(("hbm", "seq_gather", y.numel()), 2 * y.numel() * y.element_size()):
+        L.check(L.load().dvt_seq_gather(x.data_ptr(), idx.data_ptr(), y.data_ptr(), S, k, L_, float(alpha), dt(x), _stream()),
+                "dvt_seq_gather")
+    return y
+
+
+def seq_scatter_add(res: Tensor, y: Tensor, slot: Tensor, alpha: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
+    """res [S, ...], y [k, ...], slot [S] int32 -> out [S, ...]: out[s] = res[s] + alpha * y[slot[s]] where
+    0 <= slot[s] < k, res[s] otherwise.  The adjoint of ``seq_gather``.  ``out`` may be ``res`` itself (in place)."""
+    S, L_ = _seq_rows("seq_scatter_add: res", res)
+    k, Ly = _seq_rows("seq_scatter_add: y", y)
+    if Ly != L_ or y.dtype != res.dtype or y.device != res.device:
+        raise ValueError(f"seq_scatter_add: y {tuple(y.shape)} {y.dtype} on {y.device} does not hold rows of res "
+                         f"{tuple(res.shape)} {res.dtype} on {res.device}")
+    slot = _seq_index("seq_scatter_add: slot", slot, S, res)
+    if out is not None and (not isinstance(out, Tensor) or out.shape != res.shape or out.dtype != res.dtype
+                            or out.device != res.device or not out.is_contiguous() or not res.is_contiguous()):
+        raise ValueError("seq_scatter_add: out must be a contiguous tensor of res's shape, dtype and device "
+                         "(and res contiguous)")
+    _need_cuda(res, y, slot)
+    if out is None:
+        res = res.contiguous()
+        out = torch.empty_like(res)
+    y = y.contiguous()
+    nbytes = (2 * res.numel() + y.numel()) * res.element_size()
+    with _timed(("hbm", "seq_scatter_add", res.numel()), nbytes):
+        L.check(L.load().dvt_seq_scatter_add(res.data_ptr(), y.data_ptr(), slot.data_ptr(), out.data_ptr(), S, k, L_,
+                                             float(alpha), dt(res), _stream()), "dvt_seq_scatter_add")
+    return out
+
+
+def drop_path_draw(S: int, p: float, rng_state: Tensor, call_offset: int) -> Tensor:
+    """m [S] int32: m[s] = s with probability 1 - p, else -1 -- a pure function of (rng_state on the device, call_offset,
+    s).  A site takes ceil(S / 4) Philox blocks (``functional._rng.take(S)``)."""
+    if isinstance(S, bool) or not isinstance(S, int) or S < 1:
+        raise ValueError(f"drop_path_draw: S must be an integer >= 1, got {S!r}")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"drop_path_draw: p must be in [0, 1), got {p!r}")
+    _need_cuda(rng_state)
+    m = torch.empty((S,), dtype=torch.int32, device=rng_state.device)
+    with _timed(("hbm", "drop_path_draw", S), 4 * S):
+        L.check(L.load().dvt_drop_path_draw(rng_state.data_ptr(), call_offset, S, float(p), m.data_ptr(), _stream()),
+                "dvt_drop_path_draw")
+    return m
+
+
 def tokens_assemble_fwd(emb: Tensor, cls: Tensor, pos: Tensor, S: int, T: int, n: int) -> Tensor:
     """emb [S*n, d]; cls [d] f32; pos [T, rows>=n+1, d] f32 -> [S, n+1, d]."""
     _need_cuda(emb, cls, pos)

@@ -211,6 +211,35 @@ int dvt_tokens_assemble_keep_bwd(const void* dout, const int32_t* slot, void* de
                                  int64_t T, int n, int k, int64_t d, int64_t pos_rows, int dtype, int accumulate,
                                  dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- stochastic depth (csrc/drop_path.hip)
+ * timm's DropPath on the residual lines `x = attn(x) + x`, `x = ff(x) + x` (src/models/vit.py:73-74; the reference has no
+ * drop path), in the form that runs the branch on the kept sequences only.  A "sequence" is one contiguous row of
+ * L = N * d elements of a [S, N, d] tensor; input and output share one element type (f32, bf16, f16), arithmetic is fp32
+ * with one rounding on the store.  16-byte accesses when L * sizeof(T) is a multiple of 16 and every base pointer is
+ * 16-byte aligned, a scalar form otherwise.  An index read from device memory is compared against its bound before any
+ * address is formed from it.  DVT_ERR_BAD_ARG before any launch on a null pointer or S, k, L < 1 (S, k < 2^31).
+ *
+ * Gather (replaces DropPath on vit.py:73-74: the rows the branch runs on; in backward the rows of the gradient it sees):
+ *   y[j, :] = alpha * x[idx[j], :]  where 0 <= idx[j] < S;  a row of zeros otherwise (-1 is the "dropped" value).
+ * x: [S, L]; idx: [k] int32; y: [k, L]. */
+int dvt_seq_gather(const void* x, const int32_t* idx, void* y, int64_t S, int64_t k, int64_t L, float alpha, int dtype,
+                   dvt_stream_t stream);
+/* Scatter-add, the adjoint of the gather (replaces DropPath's `+ x` on vit.py:73-74, and in backward the sum of the
+ * shortcut's and the branch's gradient):
+ *   out[s, :] = res[s, :] + alpha * y[slot[s], :]  (one fmaf) where 0 <= slot[s] < k;  out[s, :] = res[s, :] otherwise.
+ * res, out: [S, L]; y: [k, L]; slot: [S] int32.  Every row of out is written exactly once; no atomics, no zero-filled
+ * intermediate, bitwise repeatable.  out MAY ALIAS res (in place): a lane reads a piece of res before it writes the same
+ * piece of out and nobody else touches it.  out must not overlap y. */
+int dvt_seq_scatter_add(const void* res, const void* y, const int32_t* slot, void* out, int64_t S, int64_t k, int64_t L,
+                        float alpha, int dtype, dvt_stream_t stream);
+/* Per-sequence Bernoulli draw (replaces the random tensor of DropPath on vit.py:73-74):  m[s] = s with probability 1 - p,
+ * else -1 -- usable as idx and as slot of the two kernels above at k = S.  Sequence s is kept iff word (s & 3) of
+ * Philox4x32-10 block rng_state[1] + call_offset + s / 4 under key rng_state[0] is >= round(p * 2^32): dvt_dropout's
+ * generator, device state and rule (a site takes ceil(S / 4) blocks), so a captured hipGraph draws anew on every replay.
+ * 0 <= p < 1. */
+int dvt_drop_path_draw(const uint64_t* rng_state, uint64_t call_offset, int64_t S, float p, int32_t* m,
+                       dvt_stream_t stream);
+
 /* Row gather with an optional leading token (vit.py:120-123, x[:, 0] then
  * cat(temporal_token, .)):  out[b, 0, :] = tok (if tok != NULL, then lead = 1)
  * out[b, lead + t, :] = src[(b*T + t) * src_row_stride : + d].  */
