@@ -1544,8 +1544,11 @@ int dvt_im2col(const void* x, int x_dtype, int x_nchw, void* out, int out_dtype,
 
 int dvt_col2im_nchw(const void* dcol, int dtype, void* dx, int dx_dtype, int64_t N, int C, int H, int W, int kh,
                     int kw, int sh, int sw, int ph, int pw, int64_t ld, dvt_stream_t stream) {
-  DVT_REQUIRE(dcol && dx && N >= 0 && C > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0, "dvt_col2im_nchw: bad arguments");
+  DVT_REQUIRE(dcol && dx && N >= 0 && C > 0 && H > 0 && W > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0,
+              "dvt_col2im_nchw: bad arguments");
+  DVT_REQUIRE(ld >= (int64_t)kh * kw * C, "dvt_col2im_nchw: ld smaller than kh*kw*C");
   const int Ho = (H + 2 * ph - kh) / sh + 1, Wo = (W + 2 * pw - kw) / sw + 1;
+  DVT_REQUIRE(Ho > 0 && Wo > 0, "dvt_col2im_nchw: empty column matrix");
   if (N == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(dvt_grid(N * H * W * C)), block(kB);
@@ -1569,11 +1572,13 @@ int dvt_col2im_nchw(const void* dcol, int dtype, void* dx, int dx_dtype, int64_t
 
 int dvt_col2im(const void* dcol, void* dx, int64_t N, int C, int H, int W, int kh, int kw, int sh, int sw,
                int ph, int pw, int64_t ld, const void* add, int add_stride, int dtype, dvt_stream_t stream) {
-  DVT_REQUIRE(dcol && dx && N >= 0 && C > 0 && add_stride >= 0, "dvt_col2im: bad arguments");
+  DVT_REQUIRE(dcol && dx && N >= 0 && C > 0 && H > 0 && W > 0 && kh > 0 && kw > 0 && add_stride >= 0, "dvt_col2im: bad arguments");
+  DVT_REQUIRE(ld >= (int64_t)kh * kw * C, "dvt_col2im: ld smaller than kh*kw*C");
   const bool cvec = C % 8 == 0 && ld % 8 == 0 && dvt_aligned16(dcol) && dvt_aligned16(dx) && dvt_aligned16(add);
   if (add && !cvec) DVT_UNSUPPORTED("dvt_col2im: the fused second gradient path needs C %% 8 == 0 and 16-byte aligned buffers");
   DVT_REQUIRE(sh > 0 && sw > 0 && ph >= 0 && pw >= 0, "dvt_col2im: bad stride / padding");
   const int Ho = (H + 2 * ph - kh) / sh + 1, Wo = (W + 2 * pw - kw) / sw + 1;
+  DVT_REQUIRE(Ho > 0 && Wo > 0, "dvt_col2im: empty column matrix");
   if (N == 0) return DVT_OK;
   hipStream_t st = (hipStream_t)stream;
   if (cvec) {

@@ -4,9 +4,9 @@ template arguments (element type, MODE, POOL, MSRC, RES, MASK, DRES, CL) are der
 mirrors of tests/batchnorm_ref.py -- a row that names the wrong case fails.  Only the names of the listing are read.
 
 Scope: the statistics, finalize, fold, apply, pooled and max-pool kernels.  conv.hip's other kernels (OUT_OF_SCOPE: the
-im2col / col2im, weight pack, pad, layout and transpose kernels) stay with the tests they already have in
-tests/test_gpu_cnn.py, tests/test_gpu_ops.py and the convolution gates; a kernel added to conv.hip later has to be placed
-in one list or the other."""
+im2col / col2im, weight pack, pad, layout and pixel-pair kernels) have their own gate, tests/test_conv_data_coverage.py,
+over the exact cases of tests/test_gpu_conv_data.py, and the transpose kernel its rows in tests/test_rowwise_coverage.py;
+a kernel added to conv.hip later has to be placed in one list or the other."""
 import importlib
 import itertools
 import os
