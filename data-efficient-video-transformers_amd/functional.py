@@ -506,6 +506,81 @@ def tokens_assemble_keep(emb: Tensor, cls: Tensor, pos: Tensor, keep: Tensor, sl
 
 
 # ---------------------------------------------------------------------------
+# Masked-autoencoder pre-training (csrc/mae.hip): the kept rows back at their positions for the decoder, and the masked
+# patch loss against pixel targets read from the clip.
+# ---------------------------------------------------------------------------
+class _TokensRestore(torch.autograd.Function):
+    """The sink protocol of ``_TokensKeep``: one accumulate flag for dmask and dpos, the slow form when the two sinks
+    disagree."""
+
+    @staticmethod
+    def forward(ctx, y, mask, pos, keep, slot, S, T, skip):
+        mask32 = _f32(mask).reshape(-1)
+        pos32 = _f32(pos)
+        pos32 = pos32.reshape(T, pos32.shape[-2], pos32.shape[-1])
+        if keep.shape[0] != S or slot.shape[0] != S or y.shape[0] != S:
+            raise ValueError(f"tokens_restore: y {tuple(y.shape)} / keep {tuple(keep.shape)} / slot {tuple(slot.shape)} "
+                             f"for {S} sequences")
+        ctx.T, ctx.skip = T, skip
+        ctx.mask_shape, ctx.pos_shape = tuple(mask.shape), tuple(pos.shape)
+        ctx.sinks = (_sink(mask), _sink(pos))
+        ctx.keep, ctx.slot = keep, slot
+        return ops.tokens_restore_fwd(y.contiguous(), mask32, pos32, slot, keep.shape[1], skip)
+
+    @staticmethod
+    def backward(ctx, dout):
+        sm, sp = ctx.sinks
+        none = (None,) * 7
+        if sm is not None and sp is not None and sm.fresh != sp.fresh:
+            dy, dmask, dpos = ops.tokens_restore_bwd(dout, ctx.keep, ctx.slot, ctx.T, ctx.skip)
+            _emit_into(sm, dmask)
+            _emit_into(sp, dpos)
+            return (dy,) + none
+        if sm is not None and sp is not None:
+            dy, _, _ = ops.tokens_restore_bwd(dout, ctx.keep, ctx.slot, ctx.T, ctx.skip, dmask=sm.buf.view(-1),
+                                              dpos=sp.buf.view(ctx.T, ctx.slot.shape[1], -1), accumulate=not sm.fresh)
+            sm.mark_written()
+            sp.mark_written()
+            return (dy,) + none
+        dy, dmask, dpos = ops.tokens_restore_bwd(dout, ctx.keep, ctx.slot, ctx.T, ctx.skip)
+        return (dy, dmask.view(ctx.mask_shape), dpos.view(ctx.pos_shape)) + (None,) * 5
+
+
+def tokens_restore(y: Tensor, mask_token: Tensor, pos: Tensor, keep: Tensor, slot: Tensor, S: int, T: int,
+                   skip: int = 1) -> Tensor:
+    """y [S, skip + k, d], mask_token [1, 1, d], pos [1, T, n, d], keep [S, k], slot [S, n] -> [S, n, d]: row j is the
+    encoded row of position j where it was kept, the mask token where it was dropped, plus the positional row j (the ``skip``
+    leading rows of y -- the CLS row -- are left out and get a zero gradient)."""
+    return _TokensRestore.apply(y, mask_token, pos, keep, slot, S, T, skip)
+
+
+class _MaeLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, clip, slot, k, patch, tubelet, norm_pix):
+        pc, cc = pred.contiguous(), clip.detach().contiguous()
+        loss, per_patch, stats = ops.mae_loss_fwd(pc, cc, slot, k, patch, tubelet, norm_pix)
+        ctx.save_for_backward(pc, cc, slot, *(() if stats is None else (stats,)))
+        ctx.args = (k, patch, tubelet)
+        ctx.mark_non_differentiable(per_patch)
+        return loss.view(()), per_patch
+
+    @staticmethod
+    def backward(ctx, gloss, _gper):
+        pc, cc, slot, *stats = ctx.saved_tensors
+        k, patch, tubelet = ctx.args
+        dpred = ops.mae_loss_bwd(pc, cc, slot, k, patch, tubelet, stats[0] if stats else None, _f32(gloss).reshape(1))
+        return dpred, None, None, None, None, None, None
+
+
+def mae_loss(pred: Tensor, clip: Tensor, slot: Tensor, k: int, patch: int, tubelet: int, norm_pix: bool = True):
+    """pred [S, n, pt*P*P*C], clip [b, t, C, H, W], slot [S, n] (-1 = dropped), k kept per sequence -> (loss, per_patch [S, n]
+    f32): the mean squared error on the dropped patches only, against pixel targets read straight from the clip in the
+    tubelet gather's order; ``norm_pix``: per-patch normalised targets (mean, unbiased variance, eps 1e-6 -- MAE's
+    ``norm_pix_loss``).  ``per_patch`` carries no gradient; no gradient reaches the clip."""
+    return _MaeLoss.apply(pred, clip, slot, k, patch, tubelet, bool(norm_pix))
+
+
+# ---------------------------------------------------------------------------
 # Final space LayerNorm on the CLS rows + temporal CLS concat (vit.py:75,120-123)
 # ---------------------------------------------------------------------------
 class _ClsNormConcat(torch.autograd.Function):

@@ -13,3 +13,5 @@ from .contrastivemodel import SpatioTemporalContrastiveModel  # noqa: F401,E402
 from .basicmlp import BasicMLP  # noqa: F401,E402
 from . import evaluator  # noqa: F401,E402
 from .evaluator import SSLEvaluator  # noqa: F401,E402
+from . import mae  # noqa: F401,E402
+from .mae import MaskedClipAutoencoder  # noqa: F401,E402

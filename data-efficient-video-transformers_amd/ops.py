@@ -490,6 +490,131 @@ def drop_path_draw(S: int, p: float, rng_state: Tensor, call_offset: int) -> Ten
     return m
 
 
+# ------------------------------------------------------------------ masked-autoencoder pre-training (csrc/mae.hip)
+def _restore_geometry(what: str, t: Tensor, slot: Tensor, rows: Optional[int]):
+    """(S, n, d) of a row tensor [S, rows or any, d] against slot [S, n]; ValueError on a mismatch or d % 8 != 0."""
+    if not isinstance(t, Tensor) or t.dim() != 3 or t.dtype not in _DT or t.numel() == 0:
+        raise ValueError(f"{what}: expected a non-empty [S, rows, d] tensor in float32 / bfloat16 / float16, got "
+                         f"{getattr(t, 'dtype', type(t))} of shape {tuple(getattr(t, 'shape', ()))}")
+    S, r, d = t.shape
+    if d % 8:
+        raise ValueError(f"{what}: d = {d} must be a multiple of 8")
+    slot = _index_table(f"{what}: slot", slot, rows=S)
+    if rows is not None and r != rows:
+        raise ValueError(f"{what}: {r} rows per sequence where {rows} are expected")
+    return S, slot.shape[1], d, slot
+
+
+def tokens_restore_fwd(y: Tensor, mask: Tensor, pos: Tensor, slot: Tensor, k: int, skip: int = 1) -> Tensor:
+    """y [S, skip + k, d]; mask [d] f32; pos [T, n, d] f32; slot [S, n] -> out [S, n, d] in y's type:
+    out[s, j] = (y[s, skip + slot[s, j]] if slot[s, j] >= 0 else mask) + pos[s % T, j]."""
+    S, n, d, slot = _restore_geometry("tokens_restore_fwd", y, slot, None)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= n or skip < 0 or y.shape[1] != skip + k:
+        raise ValueError(f"tokens_restore_fwd: y {tuple(y.shape)} does not hold skip + k = {skip} + {k} rows per sequence "
+                         f"with 1 <= k <= n = {n}")
+    if (mask.dtype != torch.float32 or pos.dtype != torch.float32 or mask.numel() != d or pos.dim() != 3
+            or tuple(pos.shape[1:]) != (n, d) or S % pos.shape[0]):
+        raise ValueError(f"tokens_restore_fwd: mask {tuple(mask.shape)} {mask.dtype} / pos {tuple(pos.shape)} {pos.dtype} "
+                         f"where float32 [{d}] and [T, {n}, {d}] with T dividing S = {S} are expected")
+    _need_cuda(y, mask, pos)
+    assert y.is_contiguous() and mask.is_contiguous() and pos.is_contiguous()
+    out = torch.empty((S, n, d), dtype=y.dtype, device=y.device)
+    nbytes = (S * k * d + out.numel()) * y.element_size() + (pos.numel() + d) * 4 + slot.numel() * 4
+    with _timed(("hbm", "tokens_restore_fwd", out.numel()), nbytes):
+        L.check(L.load().dvt_tokens_restore_fwd(y.data_ptr(), mask.data_ptr(), pos.data_ptr(), slot.data_ptr(), out.data_ptr(),
+                                                S, pos.shape[0], n, k, skip, d, dt(y), _stream()), "dvt_tokens_restore_fwd")
+    return out
+
+
+def tokens_restore_bwd(dout: Tensor, keep: Tensor, slot: Tensor, T: int, skip: int = 1, *, dmask: Optional[Tensor] = None,
+                       dpos: Optional[Tensor] = None, accumulate: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """dout [S, n, d], keep [S, k], slot [S, n] -> (dy [S, skip + k, d], dmask [d], dpos [T, n, d]); dmask / dpos may be
+    caller-owned fp32 destinations (gradient sinks).  dy[s, skip + i] = dout[s, keep[s, i]] with zero skip rows; dmask sums
+    the dropped rows, dpos every row of its position in ascending clip order.  Deterministic."""
+    S, n, d, slot = _restore_geometry("tokens_restore_bwd", dout, slot, None)
+    if dout.shape[1] != n:
+        raise ValueError(f"tokens_restore_bwd: dout {tuple(dout.shape)} for slot {tuple(slot.shape)}")
+    keep = _index_table("tokens_restore_bwd: keep", keep, rows=S)
+    k = keep.shape[1]
+    if not 1 <= k <= n or skip < 0 or T < 1 or S % T:
+        raise ValueError(f"tokens_restore_bwd: k = {k}, n = {n}, skip = {skip}, T = {T}, S = {S}")
+    _need_cuda(dout)
+    dout = dout.contiguous()
+    dy = torch.empty((S, skip + k, d), dtype=dout.dtype, device=dout.device)
+    if dmask is None:
+        assert not accumulate
+        dmask = torch.empty((d,), dtype=torch.float32, device=dout.device)
+    if dpos is None:
+        assert not accumulate
+        dpos = torch.empty((T, n, d), dtype=torch.float32, device=dout.device)
+    assert dmask.is_contiguous() and dpos.is_contiguous() and dmask.numel() == d and dpos.numel() == T * n * d
+    assert dmask.dtype == torch.float32 and dpos.dtype == torch.float32
+    partial = workspace(T * n * d * 4, dout.device, slot="mae")
+    nbytes = (dout.numel() + dy.numel()) * dout.element_size() + (3 + int(accumulate)) * T * n * d * 4 + slot.numel() * 4
+    with _timed(("hbm", "tokens_restore_bwd", dout.numel()), nbytes):
+        L.check(L.load().dvt_tokens_restore_bwd(dout.data_ptr(), keep.data_ptr(), slot.data_ptr(), dy.data_ptr(),
+                                                dmask.data_ptr(), dpos.data_ptr(), partial.data_ptr(), S, T, n, k, skip, d,
+                                                dt(dout), int(accumulate), _stream()), "dvt_tokens_restore_bwd")
+    return dy, dmask, dpos
+
+
+MAE_EPS = 1e-6                     # the epsilon of the per-patch normalised target (MAE / MAE-ST)
+
+
+def _mae_geometry(what: str, pred: Tensor, clip: Tensor, slot: Tensor, k: int, patch: int, tubelet: int):
+    frames, Cc, H, W = _tubelet_geometry(clip.shape, patch, tubelet, what)
+    if isinstance(patch, bool) or not isinstance(patch, int) or patch < 1 or H % patch or W % patch:
+        raise ValueError(f"{what}: image {H}x{W} is not divisible by patch {patch!r}")
+    S, n, D = frames // tubelet, (H // patch) * (W // patch), tubelet * patch * patch * Cc
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k < n:
+        raise ValueError(f"{what}: k = {k!r} must satisfy 1 <= k < n = {n}: no masked patch (M == 0) or no kept one")
+    if (not isinstance(pred, Tensor) or pred.dtype not in _DT or clip.dtype not in _DT or pred.numel() != S * n * D
+            or pred.shape[-1] != D):
+        raise ValueError(f"{what}: pred {tuple(getattr(pred, 'shape', ()))} {getattr(pred, 'dtype', type(pred))} does not "
+                         f"hold [{S}, {n}, {D}] for a clip {tuple(clip.shape)} {clip.dtype}")
+    slot = _index_table(f"{what}: slot", slot, rows=S, cols=n)
+    _need_cuda(pred, clip)
+    return frames, Cc, H, W, S, n, D, slot
+
+
+def mae_loss_fwd(pred: Tensor, clip: Tensor, slot: Tensor, k: int, patch: int, tubelet: int, norm_pix: bool,
+                 eps: float = MAE_EPS):
+    """pred [S, n, D], clip [b, t, C, H, W] (its own dtype), slot [S, n] -> (loss f32 [1], per_patch f32 [S, n], stats f32
+    [S, n, 2] or None): the mean over the S (n - k) dropped patches of mean_D (pred - target)^2, the target read from the
+    clip in the tubelet gather's order (per-patch normalised, unbiased variance, under ``norm_pix``)."""
+    frames, Cc, H, W, S, n, D, slot = _mae_geometry("mae_loss_fwd", pred, clip, slot, k, patch, tubelet)
+    pred, clip = pred.contiguous(), clip.contiguous()
+    per_patch = torch.empty((S, n), dtype=torch.float32, device=pred.device)
+    stats = torch.empty((S, n, 2), dtype=torch.float32, device=pred.device) if norm_pix else None
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    masked = S * (n - k) * D
+    nbytes = masked * (pred.element_size() + clip.element_size()) + S * n * (8 + (8 if norm_pix else 0))
+    with _timed(("hbm", "mae_loss_fwd", masked), nbytes):
+        L.check(L.load().dvt_mae_loss_fwd(pred.data_ptr(), dt(pred), clip.data_ptr(), dt(clip), slot.data_ptr(),
+                                          per_patch.data_ptr(), _p(stats), loss.data_ptr(), frames, Cc, H, W, patch, tubelet, k,
+                                          int(bool(norm_pix)), float(eps), _stream()), "dvt_mae_loss_fwd")
+    return loss, per_patch, stats
+
+
+def mae_loss_bwd(pred: Tensor, clip: Tensor, slot: Tensor, k: int, patch: int, tubelet: int, stats: Optional[Tensor],
+                 gloss: Tensor) -> Tensor:
+    """dpred [S, n, D] in pred's type = gloss * 2 / (M D) * (pred - target) at dropped positions, exact zeros at kept ones;
+    ``gloss`` is a device f32 scalar, ``stats`` the forward's (None without norm_pix)."""
+    frames, Cc, H, W, S, n, D, slot = _mae_geometry("mae_loss_bwd", pred, clip, slot, k, patch, tubelet)
+    _need_cuda(gloss)
+    assert gloss.dtype == torch.float32 and gloss.numel() == 1
+    assert stats is None or (stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == 2 * S * n)
+    pred, clip = pred.contiguous(), clip.contiguous()
+    dpred = torch.empty((S, n, D), dtype=pred.dtype, device=pred.device)
+    masked = S * (n - k) * D
+    nbytes = (masked + S * n * D) * pred.element_size() + masked * clip.element_size() + S * n * (4 + (8 if stats is not None else 0))
+    with _timed(("hbm", "mae_loss_bwd", masked), nbytes):
+        L.check(L.load().dvt_mae_loss_bwd(pred.data_ptr(), dt(pred), clip.data_ptr(), dt(clip), slot.data_ptr(), _p(stats),
+                                          gloss.data_ptr(), dpred.data_ptr(), frames, Cc, H, W, patch, tubelet, k,
+                                          int(stats is not None), _stream()), "dvt_mae_loss_bwd")
+    return dpred
+
+
 def tokens_assemble_fwd(emb: Tensor, cls: Tensor, pos: Tensor, S: int, T: int, n: int) -> Tensor:
     """emb [S*n, d]; cls [d] f32; pos [T, rows>=n+1, d] f32 -> [S, n+1, d]."""
     _need_cuda(emb, cls, pos)

@@ -240,6 +240,47 @@ int dvt_seq_scatter_add(const void* res, const void* y, const int32_t* slot, voi
 int dvt_drop_path_draw(const uint64_t* rng_state, uint64_t call_offset, int64_t S, float p, int32_t* m,
                        dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- masked-autoencoder pre-training (csrc/mae.hip)
+ * Additions within ABI v5: new entry points only.  MAE / MAE-ST / VideoMAE on the tokeniser of src/models/vit.py:110-116 (the
+ * reference has no self-supervised clip model): the space stack encodes the k kept tokens of every sequence (the patch
+ * dropout entries above), a decoder reconstructs the pixels of the n - k dropped patches.  keep [S, k] / slot [S, n] as above;
+ * an entry of slot outside [0, k) counts as dropped, an entry of keep outside [0, n) yields a zero row.  fp32 arithmetic, one
+ * rounding per output element, every output element written exactly once, no float atomics, bitwise repeatable.
+ *
+ * Restore (what vit.py:113-115 is to the encoder, for the decoder): the encoded kept rows back at their positions, the
+ * learned mask token everywhere else, plus the decoder's positional table (no CLS row):
+ *   out[s, j, :] = (0 <= slot[s, j] < k ? y[s, skip + slot[s, j], :] : mask[:]) + pos[s % T, j, :]
+ * y: [S, skip + k, d] dtype (the `skip` leading rows of a sequence -- the CLS row -- are not restored); mask: [d] f32;
+ * pos: [T, n, d] f32; out: [S, n, d] dtype.  DVT_ERR_BAD_ARG before any launch unless d % 8 == 0, 1 <= k <= n, skip >= 0,
+ * S % T == 0 and every buffer is 16-byte aligned. */
+int dvt_tokens_restore_fwd(const void* y, const float* mask, const float* pos, const int32_t* slot, void* out, int64_t S,
+                           int64_t T, int n, int k, int skip, int64_t d, int dtype, dvt_stream_t stream);
+/* Its adjoint: dy [S, skip + k, d]: dy[s, skip + i] = dout[s, keep[s, i]], the skip leading rows exactly zero;
+ * dmask [d] (+)= the sum of dout[s, j] over all dropped (s, j); dpos[tau, j] (+)= sum_b dout[b*T + tau, j] in ascending b, over
+ * every position, kept or not.  Fixed orders: dmask is reduced from `partial` [T * n, d] f32 (scratch the caller owns, written
+ * whole by the same pass that sums dpos) by one workgroup per 8 columns.  `accumulate` != 0 adds into dmask / dpos instead
+ * of overwriting; dmask is exactly zero (or untouched in value) when k == n. */
+int dvt_tokens_restore_bwd(const void* dout, const int32_t* keep, const int32_t* slot, void* dy, float* dmask, float* dpos,
+                           float* partial, int64_t S, int64_t T, int n, int k, int skip, int64_t d, int dtype, int accumulate,
+                           dvt_stream_t stream);
+/* Masked patch loss: the mean over the M = S * (n - k) dropped patches (S = frames / pt) of the mean over D = pt*P*P*C of
+ * (pred - target)^2.  The target of a dropped (s, j) is row (s, j) of dvt_tubelet_patchify(clip), read from the clip:
+ *   target[((kf*P + p1)*P + p2)*C + c] = clip[s*pt + kf, c, ph*P + p1, pw*P + p2],  ph*nw + pw = j;
+ * with norm_pix != 0 it is (x - mean) / sqrt(var + eps), mean and UNBIASED variance (divisor D - 1) over the D values of the
+ * patch, the variance as a sum of squared deviations from the mean.  pred: [S, n, D] pred_dtype; clip: [frames, C, H, W]
+ * clip_dtype (any pair of f32 / bf16 / f16); per_patch: [S, n] f32, exactly 0 at kept positions; stats: [S, n, 2] f32
+ * {mean, rstd} (required with norm_pix, zeros at kept positions; else ignored, may be NULL); loss: one f32, written by a
+ * second launch that sums per_patch and divides by M in double.  k is an argument, not counted on the device.
+ * DVT_ERR_BAD_ARG before any launch unless 1 <= k < n (M == 0 is refused), frames % pt == 0, P divides H and W. */
+int dvt_mae_loss_fwd(const void* pred, int pred_dtype, const void* clip, int clip_dtype, const int32_t* slot, float* per_patch,
+                     float* stats, float* loss, int64_t frames, int C, int H, int W, int P, int pt, int k, int norm_pix,
+                     float eps, dvt_stream_t stream);
+/* dpred[s, j, :] = gloss[0] * 2 / (M * D) * (pred - target) at dropped positions, exactly 0 at kept ones; pred_dtype.  gloss is
+ * a DEVICE f32 scalar; the target is recomputed from the clip with the forward's stats.  The clip gets no gradient. */
+int dvt_mae_loss_bwd(const void* pred, int pred_dtype, const void* clip, int clip_dtype, const int32_t* slot,
+                     const float* stats, const float* gloss, void* dpred, int64_t frames, int C, int H, int W, int P, int pt,
+                     int k, int norm_pix, dvt_stream_t stream);
+
 /* Row gather with an optional leading token (vit.py:120-123, x[:, 0] then
  * cat(temporal_token, .)):  out[b, 0, :] = tok (if tok != NULL, then lead = 1)
  * out[b, lead + t, :] = src[(b*T + t) * src_row_stride : + d].  */
