@@ -591,6 +591,106 @@ class FlatParameters:
                            beta2=betas[1], eps=eps, weight_decay=weight_decay, skip=self.skip_mask, mirror=self.compute)
         self._after_step(mirror_written=True)
 
+    # ------------------------------------------------------------------ parameter groups, weight EMA
+    def set_param_groups(self, groups) -> None:
+        """torch-style parameter groups for ``adamw_groups_step``: dicts with ``params`` and, optionally, ``weight_decay``
+        (default 0) and ``lr_scale`` (default 1) -- what ``optim.param_groups`` returns.  Every trainable parameter of
+        the module must be in exactly one group.  Builds the block map (one byte per 64 elements from ``self.offsets``;
+        alignment padding takes group 0, where p = g = m = v = 0 stays 0) and the device table, once: not inside a
+        hipGraph capture."""
+        groups = list(groups)
+        if self.data.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_param_groups builds its block map and table when it is called; make that call in a "
+                               "warm-up step, not inside a hipGraph capture")
+        if not 1 <= len(groups) <= 255:
+            raise ValueError(f"set_param_groups: 1 .. 255 groups, got {len(groups)}")
+        index = {id(p): i for i, p in enumerate(self.params)}
+        group_of = [None] * len(self.params)
+        for gi, grp in enumerate(groups):
+            names = grp.get("names")
+            for k, p in enumerate(grp["params"]):
+                what = names[k] if names else f"of shape {tuple(p.shape)}"
+                i = index.get(id(p))
+                if i is None:
+                    if not p.requires_grad:
+                        continue
+                    raise ValueError(f"set_param_groups: parameter {what} (group {gi}) is not a trainable parameter of the module")
+                if group_of[i] is not None:
+                    raise ValueError(f"set_param_groups: parameter {what} is in group {group_of[i]} and in group {gi}")
+                group_of[i] = gi
+        missing = [i for i, g in enumerate(group_of) if g is None]
+        if missing:
+            raise ValueError(f"set_param_groups: parameter {missing[0]} of shape {tuple(self.params[missing[0]].shape)} "
+                             f"is in no group ({len(missing)} in all)")
+        m = torch.zeros(self.total // _ALIGN, dtype=torch.uint8)
+        for i, gi in enumerate(group_of):
+            lo = self.offsets[i] // _ALIGN
+            hi = (self.offsets[i] + self.params[i].numel() + _ALIGN - 1) // _ALIGN
+            m[lo:hi] = gi
+        self.group64 = m                        # the host copy of the map
+        self.group_hyper = [(float(g.get("lr_scale", 1.0)), float(g.get("weight_decay", 0.0))) for g in groups]
+        self._group_table = (ops.adamw_group_table(m, *zip(*self.group_hyper))
+                             if self.data.device.type == "cuda" else None)
+
+    def adamw_groups_step(self, lr, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+        """``adamw_step`` under the groups of ``set_param_groups``, still one launch: a block's rate is ``lr`` times its
+        group's ``lr_scale``, its decay the group's ``weight_decay``.  ``lr``: a float or a device fp32 scalar (a captured
+        step follows a schedule written into it), as in ``adam_step``.  After ``enable_ema`` the same launch moves the
+        weight EMA.  The step count is the global one of ``adamw_step``.  Loss scaling is not implemented here."""
+        if getattr(self, "group_hyper", None) is None:
+            raise RuntimeError("adamw_groups_step: call set_param_groups first")
+        if getattr(self, "scaler", None) is not None:
+            raise NotImplementedError("adamw_groups_step does not implement loss scaling; the loss-scaled step is adamw_step")
+        if self._group_table is None:
+            raise RuntimeError("libdvt_hip operators need tensors on the GPU (HIP device); there is no CPU path")
+        if self.exp_avg is None:
+            self.init_optimizer_state()
+        lr = self._lr_scalar(lr)
+        self.step_count += 1
+        ema = getattr(self, "ema", None)
+        ops.adamw_groups_step_(self.data, self.grad, self.exp_avg, self.exp_avg_sq, self.step_dev, lr, self._group_table,
+                               beta1=betas[0], beta2=betas[1], eps=eps, skip=self.skip_mask, mirror=self.compute, ema=ema,
+                               ema_decay=self.ema_decay_dev if ema is not None else None)
+        self._after_step(mirror_written=True)
+
+    def enable_ema(self, decay: float) -> torch.Tensor:
+        """An exponential moving average of the weights (timm's ModelEmaV2): ``self.ema`` starts as a copy of the weights
+        as they are now; ``adamw_groups_step`` moves it inside its own launch, ``ema_update()`` after any other step.
+        The decay is a device scalar (``set_ema_decay`` rewrites it; a captured step follows).  Returns ``self.ema``."""
+        self.ema = self.data.clone()
+        self.ema_decay_dev = torch.full((1,), float(decay), dtype=torch.float32, device=self.data.device)
+        return self.ema
+
+    def set_ema_decay(self, decay: float) -> None:
+        self.ema_decay_dev.fill_(float(decay))
+
+    def ema_update(self) -> None:
+        """ema = d ema + (1 - d) weights, one streaming launch: for use after ``adamw_step``, ``adam_step``, ``lars_step``,
+        ``sgd_step`` or ``adagrad_step`` (``adamw_groups_step`` has it fused: do not call both)."""
+        if getattr(self, "ema", None) is None:
+            raise RuntimeError("ema_update: call enable_ema first")
+        ops.ema_update_(self.ema, self.data, self.ema_decay_dev)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate on the averaged weights: inside the block ``self.data`` (so every parameter of the module) holds the
+        EMA and ``self.ema`` the training weights; leaving it exchanges them back, bit for bit.  Plain copies through a
+        scratch buffer; the 16-bit copy and the packed convolution weights are invalidated on entry and on exit."""
+        if getattr(self, "ema", None) is None:
+            raise RuntimeError("ema_weights: call enable_ema first")
+
+        def exchange():
+            tmp = self.data.clone()
+            self.data.copy_(self.ema)
+            self.ema.copy_(tmp)
+            self.invalidate_compute_copy()
+            self.invalidate_packed()
+        exchange()
+        try:
+            yield self
+        finally:
+            exchange()
+
     def _lr_scalar(self, lr) -> torch.Tensor:
         """``lr`` as a device fp32 scalar: a tensor is taken as it is, a float is kept in a scalar of this object that is
         rewritten when the value changes."""
@@ -669,7 +769,8 @@ class FlatParameters:
         self.step_dev = torch.zeros(2, dtype=torch.int64, device=self.data.device)    # {steps taken, ticket of the fused step}
 
     # ------------------------------------------------------------------ checkpoint / resume of the optimizer side
-    _STATE_TENSORS = ("exp_avg", "exp_avg_sq", "step_dev", "momentum_buf", "state_sum", "scale_dev", "good_steps")
+    _STATE_TENSORS = ("exp_avg", "exp_avg_sq", "step_dev", "momentum_buf", "state_sum", "scale_dev", "good_steps", "ema",
+                      "ema_decay_dev")
 
     def state_dict(self) -> dict:
         """Optimizer-side state of the flat buffers (the parameters themselves are saved through the module's own
@@ -688,6 +789,8 @@ class FlatParameters:
         dev = self.data.device
         if "scale_dev" in sd and getattr(self, "scaler", None) is None:
             self.enable_loss_scaling(float(sd["scale_dev"]))
+        if "ema" in sd and getattr(self, "ema", None) is None:      # an EMA loaded into an object without one enables it
+            self.enable_ema(float(sd["ema_decay_dev"]))              # (both are copied in below)
         for k in self._STATE_TENSORS:
             if k in sd:
                 cur = getattr(self, k, None)

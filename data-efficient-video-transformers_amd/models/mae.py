@@ -73,6 +73,11 @@ class MaskedClipAutoencoder(nn.Module):
                              "(something to encode and something to reconstruct)")
         return k
 
+    def no_weight_decay(self):
+        """Names ``optim.param_groups`` leaves undecayed besides the 1-D parameters: the encoder's set under the prefix it
+        is registered with, the mask token and the decoder's positional table."""
+        return {"encoder." + k for k in self.encoder.no_weight_decay()} | {"mask_token", "decoder_pos_embedding"}
+
     def encoder_state_dict(self):
         """The encoder's state dict under the ViViT's own keys: ``ViViT(...).load_state_dict(this, strict=True)``."""
         return self.encoder.state_dict()

@@ -349,6 +349,36 @@ class ViViT(nn.Module):
         self.space_transformer.checkpoint = activation_checkpointing
         self.temporal_transformer.checkpoint = activation_checkpointing
 
+    # ---- the fine-tuning grouping (optim.param_groups): what is not decayed, and the layer of every parameter
+    def no_weight_decay(self):
+        """Parameters with more than one dimension that weight decay leaves alone all the same (timm's convention)."""
+        return {"pos_embedding", "space_token", "temporal_token"}
+
+    @property
+    def num_lr_layers(self) -> int:
+        """The layer id of the head under layer-wise learning-rate decay: both stacks' depths + 1."""
+        return len(self.space_transformer.layers) + len(self.temporal_transformer.layers) + 1
+
+    def layer_id(self, name: str) -> int:
+        """Layer of the parameter ``name`` in execution order, 0 (patch embedding) .. ``num_lr_layers`` (head): space layer i
+        is i + 1, the space stack's final norm shares the last space layer's id, the temporal token opens the temporal
+        stack, temporal layer j is Ds + 1 + j, and the temporal stack's final norm goes with the head."""
+        Ds, Dt = len(self.space_transformer.layers), len(self.temporal_transformer.layers)
+        if name in ("pos_embedding", "space_token") or name.startswith("to_patch_embedding."):
+            return 0
+        if name == "temporal_token":
+            return Ds + 1
+        if name.startswith("space_transformer.norm."):
+            return Ds
+        if name.startswith("temporal_transformer.norm.") or name.startswith("mlp_head."):
+            return Ds + Dt + 1
+        for prefix, base, depth in (("space_transformer.layers.", 1, Ds), ("temporal_transformer.layers.", Ds + 1, Dt)):
+            if name.startswith(prefix):
+                i = name[len(prefix):].split(".", 1)[0]
+                if i.isdigit() and int(i) < depth:
+                    return base + int(i)
+        raise KeyError(f"ViViT.layer_id: {name!r} is not a parameter of this model")
+
     def num_kept(self, n: int) -> int:
         """k = n - floor(patch_dropout * n): the patch tokens a sequence of n positions keeps in training."""
         p = self.patch_dropout

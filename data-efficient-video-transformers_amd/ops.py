@@ -2071,6 +2071,69 @@ def grad_clip_(t: LarsTable, max_norm: float, norm_type=2.0, inv_scale: Optional
     return out
 
 
+# ------------------------------------------------------------------ grouped AdamW and weight EMA (csrc/optim_groups.hip)
+class AdamwGroupTable:
+    """The device side of a parameter grouping: ``group64`` (uint8, one byte per 64 elements, the row each block takes)
+    and ``table`` (f32 [ngroups, 2] = {lr_scale, weight_decay}).  Built by ``adamw_group_table``."""
+
+    def __init__(self, group64: Tensor, table: Tensor):
+        self.group64, self.table, self.ngroups = group64, table, int(table.shape[0])
+
+
+def adamw_group_table(group64, lr_scales, weight_decays) -> AdamwGroupTable:
+    """group64: uint8 [ceil(n / 64)] (any device; it is validated on the host and copied to the GPU), one row index per
+    64-element block; lr_scales / weight_decays: one value per group.  Every map byte must be below the number of groups:
+    the kernel cannot refuse a bad one, so this is checked here, once.  Not to be built inside a hipGraph capture."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("adamw_group_table builds its device map and table when it is called; make that call in a "
+                           "warm-up step, not inside a hipGraph capture")
+    lr_scales, weight_decays = [float(s) for s in lr_scales], [float(w) for w in weight_decays]
+    ngroups = len(lr_scales)
+    if len(weight_decays) != ngroups:
+        raise ValueError(f"adamw_group_table: {ngroups} lr_scales for {len(weight_decays)} weight_decays")
+    if not 1 <= ngroups <= 255:
+        raise ValueError(f"adamw_group_table: ngroups must be in 1 .. 255, got {ngroups}")
+    g = torch.as_tensor(group64)
+    if g.dtype != torch.uint8 or g.dim() != 1:
+        raise TypeError("adamw_group_table: group64 must be a one-dimensional uint8 tensor")
+    host = g.cpu()
+    if host.numel() and int(host.max()) >= ngroups:
+        bad = int((host >= ngroups).nonzero()[0])
+        raise ValueError(f"adamw_group_table: map byte {int(host[bad])} at block {bad} is not below ngroups = {ngroups}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("libdvt_hip operators need tensors on the GPU (HIP device); there is no CPU path")
+    dev = g.device if g.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    table = torch.tensor(list(zip(lr_scales, weight_decays)), dtype=torch.float32).reshape(ngroups, 2)
+    return AdamwGroupTable(host.contiguous().to(dev), table.to(dev))
+
+
+def adamw_groups_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step_dev2: Tensor, lr_dev: Tensor,
+                       table: AdamwGroupTable, *, beta1: float, beta2: float, eps: float, skip: Optional[Tensor] = None,
+                       mirror: Optional[Tensor] = None, ema: Optional[Tensor] = None,
+                       ema_decay: Optional[Tensor] = None) -> None:
+    """AdamW with the rate ``lr_dev[0] * lr_scale`` and the weight decay of each 64-element block's group + the 16-bit
+    mirror + the device step counter (int64[2]) in one launch; with ``ema`` (f32, the size of ``param``) the weight EMA
+    under the device scalar ``ema_decay`` as well, for every element."""
+    _need_cuda(step_dev2, lr_dev, table.group64, table.table, ema, ema_decay)
+    assert step_dev2.dtype == torch.int64 and step_dev2.numel() == 2 and lr_dev.dtype == torch.float32
+    assert table.group64.numel() * 64 >= param.numel()
+    assert ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == param.numel())
+    assert ema_decay is None or ema_decay.dtype == torch.float32
+    L.check(L.load().dvt_adamw_groups_step(*_flat_f32(param, grad, exp_avg, exp_avg_sq), lr_dev.data_ptr(), beta1, beta2, eps,
+                                           table.group64.data_ptr(), table.table.data_ptr(), table.ngroups,
+                                           step_dev2.data_ptr(), _skip(skip, param), *_mirror(mirror, param), _p(ema),
+                                           _p(ema_decay), _stream()), "dvt_adamw_groups_step")
+
+
+def ema_update_(ema: Tensor, param: Tensor, decay_dev: Tensor) -> None:
+    """ema = d ema + (1 - d) param in place, d = ``decay_dev[0]`` (f32 device scalar): one streaming launch."""
+    _need_cuda(ema, param, decay_dev)
+    assert ema.dtype == param.dtype == decay_dev.dtype == torch.float32 and ema.is_contiguous() and param.is_contiguous()
+    assert ema.numel() == param.numel()
+    L.check(L.load().dvt_ema_update(ema.data_ptr(), param.data_ptr(), param.numel(), decay_dev.data_ptr(), _stream()),
+            "dvt_ema_update")
+
+
 # ------------------------------------------------------------------ per-frame CNN encoder (csrc/conv.hip)
 def _pair(v):
     return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))

@@ -64,6 +64,40 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     return ops.grad_clip_(table, max_norm, norm_type)
 
 
+def param_groups(module, lr, weight_decay, *, layer_decay=None, no_weight_decay=None, layer_id=None, num_layers=None):
+    """The fine-tuning grouping of MAE's ``param_groups_lrd`` (also VideoMAE, DeiT, timm): a list of group dicts
+    ``{"params", "names", "weight_decay", "lr_scale", "lr": lr * lr_scale}`` that ``AdamW`` of this module and
+    ``FlatParameters.set_param_groups`` both accept.
+
+    A parameter is NOT decayed if ``p.ndim <= 1``, its name ends in ``.bias`` or its name is in ``no_weight_decay``
+    (default: ``module.no_weight_decay()`` where the module has it).  With ``layer_decay`` the rate shrinks geometrically
+    from the head down: ``lr_scale = layer_decay ** (num_layers - layer_id(name))``; ``layer_id`` / ``num_layers`` default
+    to ``module.layer_id`` / ``module.num_lr_layers``.  Without it every scale is 1 and there are exactly two groups.
+    Groups are ordered by (layer id, decayed first); parameters keep their registration order inside a group."""
+    if no_weight_decay is None:
+        no_weight_decay = module.no_weight_decay() if hasattr(module, "no_weight_decay") else ()
+    no_weight_decay = set(no_weight_decay)
+    if layer_decay is not None:
+        layer_id = layer_id if layer_id is not None else getattr(module, "layer_id", None)
+        num_layers = num_layers if num_layers is not None else getattr(module, "num_lr_layers", None)
+        if layer_id is None or num_layers is None:
+            raise ValueError("param_groups: layer_decay needs layer_id and num_layers (the module has no layer_id / "
+                             "num_lr_layers of its own)")
+    groups, seen = {}, set()
+    for name, p in module.named_parameters():
+        if not p.requires_grad or id(p) in seen:
+            continue
+        seen.add(id(p))
+        decayed = not (p.ndim <= 1 or name.endswith(".bias") or name in no_weight_decay)
+        layer = int(layer_id(name)) if layer_decay is not None else 0
+        scale = float(layer_decay) ** (num_layers - layer) if layer_decay is not None else 1.0
+        g = groups.setdefault((layer, not decayed), {"params": [], "names": [], "weight_decay": weight_decay if decayed else 0.0,
+                                                     "lr_scale": scale, "lr": lr * scale})
+        g["params"].append(p)
+        g["names"].append(name)
+    return [groups[k] for k in sorted(groups)]
+
+
 class _Base(torch.optim.Optimizer):
     """The one ``step()``: closure, groups, parameters with a gradient.  A subclass supplies ``_init_state`` (create what is
     missing from a parameter's state) and ``_update`` (its one kernel call)."""

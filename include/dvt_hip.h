@@ -1506,6 +1506,24 @@ int dvt_grad_norm(const dvt_lars_seg* table, int n, int64_t chunks, float* works
 int dvt_grad_clip(const dvt_lars_seg* table, int n, int64_t chunks, float* workspace, int norm_kind, float max_norm,
                   const float* scale_dev, int scale_is_inverse, float* norm_out, dvt_stream_t stream);
 
+/* ---------------------------------------------------------------- grouped AdamW and weight EMA (csrc/optim_groups.hip)
+ * Additions within ABI v5.  The fine-tuning recipe of a pre-trained ViT (MAE's param_groups_lrd, timm's ModelEmaV2) on
+ * the flat buffer: the dvt_adamw_step_fused launch with the learning rate and the weight decay chosen per 64-element
+ * block.  group64: one byte per 64 elements (ceil(n / 64) bytes, the granularity of skip64) naming a row of group_table,
+ * f32 [ngroups][2] = {lr_scale, weight_decay} on the device, 1 <= ngroups <= 255; a block's rate is
+ * lr_dev[0] * lr_scale (fp32), lr_dev an f32 device scalar as in dvt_adam_step_dev.  The map is on the device, so the
+ * entry cannot check that every byte is below ngroups: the caller does (ops.adamw_group_table).  step_dev2, skip64 and
+ * mirror as dvt_adamw_step_fused.  ema (nullable) f32 [n]: after the update, ema = d ema + (1 - d) param with
+ * d = ema_decay_dev[0], for EVERY element -- blocks that skip64 masks included, as ModelEmaV2 averages every entry
+ * whether or not the optimizer touched it.  One launch, no host synchronisation, no allocation. */
+int dvt_adamw_groups_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                          const float* lr_dev, float beta1, float beta2, float eps, const uint8_t* group64,
+                          const float* group_table, int ngroups, int64_t* step_dev2, const uint8_t* skip64, void* mirror,
+                          int mirror_dtype, float* ema, const float* ema_decay_dev, dvt_stream_t stream);
+/* ema = d ema + (1 - d) param over n f32 elements, d = ema_decay_dev[0]: the same statement as a launch of its own,
+ * for use after any other optimizer step.  Both buffers 16-byte aligned. */
+int dvt_ema_update(float* ema, const float* param, int64_t n, const float* ema_decay_dev, dvt_stream_t stream);
+
 /* ---------------------------------------------------------------- VGGish audio expert: log-mel front end, first layer
  * Additions within ABI v5.  The audio network the reference names at pretrained/models.py:13 (torchvggish, commented out:
  * torch.hub needs the network) and calls at :55-57.  csrc/audio.hip; the definition of the front end (16 kHz mono, frames
