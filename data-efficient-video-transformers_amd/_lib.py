@@ -102,6 +102,7 @@ GemmPlanInfo = STRUCTS["dvt_gemm_plan_info"]
 SplitKPending = STRUCTS["dvt_splitk_pending"]
 AttnDesc = STRUCTS["dvt_attn_desc"]
 AttnPlanInfo = STRUCTS["dvt_attn_plan_info"]
+AttnLongPlanInfo = STRUCTS["dvt_attn_long_plan_info"]
 AttnClsDesc = STRUCTS["dvt_attn_cls_desc"]
 LnBwdDesc = STRUCTS["dvt_ln_bwd_desc"]
 LnPending = STRUCTS["dvt_ln_pending"]

@@ -27,6 +27,9 @@
 //             whole 128-byte rows where the patches keep the occupancy the images allow
 //             (with_patches), per lane otherwise.
 // dvt_attention_plan reports which of these a descriptor takes (resolve_fwd / resolve_bwd).
+// streamed path (bf16 / fp16, dh == 64, any Lq and Lk; its own entry points dvt_attention_long_*): the same forward and
+//             dq / dkdv anatomy with a workgroup per (batch, head, block of 128 rows of the register side) and the staged
+//             side passing through LDS in double-buffered chunks of 128 rows (attn_long_* kernels, resolve_long).
 // generic path: any dtype / head dim / length that fits LDS, fp32 FMA, one wave
 // per row (fp32 parity mode; dh = 448 / 224 / 256 / 32 heads of the reference's
 // 14-token encoders; attention-probability dropout).
@@ -1477,6 +1480,394 @@ __global__ __launch_bounds__(512) void attn_bwd_fused_kernel(const AttnParams p)
   }
 }
 
+// ======================================================================= streamed MFMA kernels (any Lq, Lk; dh = 64)
+// The anatomy of attn_fwd_mfma_kernel / attn_bwd_dq_mfma_kernel<E, 0> / attn_bwd_dkv_mfma_kernel<E, 0> with the staged side
+// passing through LDS in chunks of kLongC rows instead of whole: a workgroup owns (b, h, a block of kLongBlk rows of the
+// register side), each of its kLongW waves one 16-row tile of that block.  The chunk images are the same swizzled [row][64]
+// pairs, double-buffered; the next chunk's global loads are issued into registers before the current chunk's MFMAs and
+// written to the other buffer after them (one barrier per chunk).  Rows of the last chunk past the sequence are zero in
+// both images (they load a clamped row and are zeroed on the way to LDS).  The output patches alias the first buffer: they
+// are only used behind the last chunk's barrier.
+constexpr int kLongW = 8;                          // waves per workgroup
+constexpr int kLongNT = 64 * kLongW;
+constexpr int kLongBlk = 16 * kLongW;              // rows of the register side per workgroup (one tile per wave)
+constexpr int kLongC = 128;                        // rows of the staged side per chunk
+constexpr int kLongRing = 2;                       // chunk buffers
+constexpr int kLongImg = kLongC * kRowBytes;       // bytes of one chunk image
+constexpr int kLongPer = kLongC * 8 / kLongNT;     // 16-byte units per thread, image and chunk
+static_assert(kLongC % 32 == 0 && kLongC * 8 % kLongNT == 0, "a chunk is whole 32-row steps and whole rounds of the block");
+static_assert(kLongW * 2048 <= kLongRing * 2 * kLongImg, "the output patches alias the chunk buffers");
+static_assert(kLongC <= kLongNT, "one thread per row fetches the chunk's lse and delta");
+
+template <typename E>
+struct LongRegs {
+  typename Elem16<E>::v8 a[kLongPer], b[kLongPer];
+};
+
+// issue the loads of rows [row0, row0 + kLongC) of two matrices; rows >= L read row L - 1 (never memory past the sequence)
+template <typename E>
+__device__ __forceinline__ void long_load(LongRegs<E>& st, const E* srca, int64_t sla, const E* srcb, int64_t slb, int row0,
+                                          int L) {
+  using V8 = typename Elem16<E>::v8;
+#pragma unroll
+  for (int u = 0; u < kLongPer; ++u) {
+    const int idx = (int)threadIdx.x + u * kLongNT;
+    const int r = row0 + (idx >> 3), c = idx & 7;
+    const int rr = r < L ? r : L - 1;
+    st.a[u] = *reinterpret_cast<const V8*>(srca + (int64_t)rr * sla + c * 8);
+    st.b[u] = *reinterpret_cast<const V8*>(srcb + (int64_t)rr * slb + c * 8);
+  }
+}
+
+// write them into a buffer's two images; rows >= L as zeros
+template <typename E>
+__device__ __forceinline__ void long_write(const LongRegs<E>& st, char* imga, char* imgb, int row0, int L) {
+  using V8 = typename Elem16<E>::v8;
+#pragma unroll
+  for (int u = 0; u < kLongPer; ++u) {
+    const int idx = (int)threadIdx.x + u * kLongNT;
+    const bool live = row0 + (idx >> 3) < L;
+    *reinterpret_cast<V8*>(imga + img_off(idx >> 3, idx & 7)) = live ? st.a[u] : V8{0, 0, 0, 0, 0, 0, 0, 0};
+    *reinterpret_cast<V8*>(imgb + img_off(idx >> 3, idx & 7)) = live ? st.b[u] : V8{0, 0, 0, 0, 0, 0, 0, 0};
+  }
+}
+
+// ---------------------------------------------------------------- forward
+// The online softmax of attn_fwd_mfma_kernel: the running m and l and the skip-unless-raised rescale continue across chunks.
+template <typename E>
+__global__ __launch_bounds__(kLongNT) void attn_long_fwd_kernel(const AttnParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using V8 = typename Elem16<E>::v8;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int g = lane >> 4, li = lane & 15;
+  const int nblk = (p.Lq + kLongBlk - 1) / kLongBlk;
+  const int bh = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  const int b = bh / p.H, h = bh % p.H;
+  const E* qb = (const E*)p.q + b * p.q_sb + h * p.q_sh;
+  const E* kb = (const E*)p.k + b * p.k_sb + h * p.k_sh;
+  const E* vb = (const E*)p.v + b * p.v_sb + h * p.v_sh;
+  E* ob = (E*)p.out + b * p.o_sb + h * p.o_sh;
+  float* lse = p.lse + ((int64_t)b * p.H + h) * p.Lq;
+  const int nch = (p.Lk + kLongC - 1) / kLongC;
+  const int q0 = blk * kLongBlk + wid * 16;
+  const bool active = q0 < p.Lq;                     // wave-uniform: the waves of a ragged last block past Lq only stage
+  const int qi = q0 + li;
+  const int qrow = qi < p.Lq ? qi : p.Lq - 1;
+
+  LongRegs<E> st;
+  long_load<E>(st, kb, p.k_sl, vb, p.v_sl, 0, p.Lk);
+  V8 qf[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) qf[kk] = *reinterpret_cast<const V8*>(qb + (int64_t)qrow * p.q_sl + kk * 32 + g * 8);
+  long_write<E>(st, smem, smem + kLongImg, 0, p.Lk);
+  __syncthreads();
+
+  const float c2 = p.scale * kLog2e;
+  f32x4 o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  for (int c = 0; c < nch; ++c) {
+    const char* ks = smem + (c & 1) * 2 * kLongImg;
+    const char* vs = ks + kLongImg;
+    const bool more = c + 1 < nch;
+    if (more) long_load<E>(st, kb, p.k_sl, vb, p.v_sl, (c + 1) * kLongC, p.Lk);
+    __builtin_amdgcn_sched_barrier(0);               // the next chunk's loads are in flight under this chunk's MFMAs
+    const int key0 = c * kLongC;
+    const int nst = (min(kLongC, p.Lk - key0) + 31) >> 5;
+    if (active) {
+      for (int kp = 0; kp < nst; ++kp) {
+        f32x4 s[2];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          s[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk)
+            s[tt] = Elem16<E>::mma(img_row_frag<E>(ks, (2 * kp + tt) * 16, kk, g, li), qf[kk], s[tt]);
+        }
+        if (!more && kp == nst - 1) {                // the key mask only exists in the last 32-key step of the last chunk
+#pragma unroll
+          for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (key0 + (2 * kp + tt) * 16 + 4 * g + r >= p.Lk) s[tt][r] = -INFINITY;
+        }
+        float mx = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])),
+                         fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mn = fmaxf(m, mx * c2);
+        const bool raised = mn > m;
+        float ps = 0.f;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float e = __builtin_amdgcn_exp2f(fmaf(s[tt][r], c2, -mn));
+            s[tt][r] = e;
+            ps += e;
+          }
+        const V8 pf = pack_pair<E>(s[0], s[1]);
+        if (__builtin_amdgcn_ballot_w64(raised) != 0) {     // wave-uniform branch
+          const float alpha = __builtin_amdgcn_exp2f(m - mn);
+          l *= alpha;
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
+        }
+        l += ps;
+        m = mn;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+          o[dt] = Elem16<E>::mma(img_tr_frag<E>(vs, 2 * kp, 2 * kp + 1, dt * 16, g, li), pf, o[dt]);
+      }
+    }
+    if (more) {
+      char* nk = smem + ((c + 1) & 1) * 2 * kLongImg;
+      long_write<E>(st, nk, nk + kLongImg, (c + 1) * kLongC, p.Lk);
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  const float inv = 1.0f / l;
+  store_tile<E>(smem + wid * 2048, ob, p.o_sl, q0, p.Lq, o, inv, lane);
+  if (qi < p.Lq && g == 0) lse[qi] = (m + __builtin_amdgcn_logf(l)) * kLn2;
+}
+
+// ---------------------------------------------------------------- backward: dq
+// attn_bwd_dq_mfma_kernel's step on streamed K / V chunks; writes delta = rowsum(dO * O) of its rows to the workspace.
+template <typename E>
+__global__ __launch_bounds__(kLongNT) void attn_long_bwd_dq_kernel(const AttnParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using V8 = typename Elem16<E>::v8;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int g = lane >> 4, li = lane & 15;
+  const int nblk = (p.Lq + kLongBlk - 1) / kLongBlk;
+  const int bh = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  const int b = bh / p.H, h = bh % p.H;
+  const E* qb = (const E*)p.q + b * p.q_sb + h * p.q_sh;
+  const E* kb = (const E*)p.k + b * p.k_sb + h * p.k_sh;
+  const E* vb = (const E*)p.v + b * p.v_sb + h * p.v_sh;
+  const E* ob = (const E*)p.o + b * p.o_sb + h * p.o_sh;
+  const E* gb = (const E*)p.d_o + b * p.o_sb + h * p.o_sh;
+  E* dqb = (E*)p.dq + b * p.q_sb + h * p.q_sh;
+  const float* lse = p.lse + ((int64_t)b * p.H + h) * p.Lq;
+  float* delta = p.delta + ((int64_t)b * p.H + h) * p.Lq;
+  const int nch = (p.Lk + kLongC - 1) / kLongC;
+  const int q0 = blk * kLongBlk + wid * 16;
+  const bool active = q0 < p.Lq;
+  const int qi = q0 + li;
+  const int qrow = qi < p.Lq ? qi : p.Lq - 1;
+
+  LongRegs<E> st;
+  long_load<E>(st, kb, p.k_sl, vb, p.v_sl, 0, p.Lk);
+  V8 qf[2], gf[2], of[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    qf[kk] = *reinterpret_cast<const V8*>(qb + (int64_t)qrow * p.q_sl + kk * 32 + g * 8);
+    gf[kk] = *reinterpret_cast<const V8*>(gb + (int64_t)qrow * p.o_sl + kk * 32 + g * 8);
+    of[kk] = *reinterpret_cast<const V8*>(ob + (int64_t)qrow * p.o_sl + kk * 32 + g * 8);
+  }
+  const float l2 = lse[qrow] * kLog2e;               // lse in log2 units
+  long_write<E>(st, smem, smem + kLongImg, 0, p.Lk);
+  float dl = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dl = fmaf((float)gf[kk][j], (float)of[kk][j], dl);
+  dl = rows_allreduce<false>(dl);                    // delta of query li
+  if (g == 0 && qi < p.Lq) delta[qi] = dl;           // the dk/dv kernel reads it instead of O
+  __syncthreads();
+
+  const float c2 = p.scale * kLog2e;
+  f32x4 acc[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const f32x2 c2v = {c2, c2}, l2v = {-l2, -l2}, dlv = {-dl, -dl};
+  for (int c = 0; c < nch; ++c) {
+    const char* ks = smem + (c & 1) * 2 * kLongImg;
+    const char* vs = ks + kLongImg;
+    const bool more = c + 1 < nch;
+    if (more) long_load<E>(st, kb, p.k_sl, vb, p.v_sl, (c + 1) * kLongC, p.Lk);
+    __builtin_amdgcn_sched_barrier(0);
+    const int key0 = c * kLongC;
+    const int nst = (min(kLongC, p.Lk - key0) + 31) >> 5;
+    if (active) {
+      for (int kp = 0; kp < nst; ++kp) {
+        const bool last = !more && kp == nst - 1;    // keys >= Lk only exist here: K rows zero, dS zeroed explicitly
+        f32x4 s[2], dp[2];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          s[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+          dp[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk) {
+            s[tt] = Elem16<E>::mma(img_row_frag<E>(ks, (2 * kp + tt) * 16, kk, g, li), qf[kk], s[tt]);
+            dp[tt] = Elem16<E>::mma(img_row_frag<E>(vs, (2 * kp + tt) * 16, kk, g, li), gf[kk], dp[tt]);
+          }
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+          for (int r = 0; r < 4; r += 2) {
+            const f32x2 x = __builtin_elementwise_fma(f32x2{s[tt][r], s[tt][r + 1]}, c2v, l2v);
+            const f32x2 d = f32x2{dp[tt][r], dp[tt][r + 1]} + dlv;
+            const f32x2 pr = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
+            const f32x2 ds = pr * d;
+            s[tt][r] = ds[0];
+            s[tt][r + 1] = ds[1];
+            if (last && key0 + (2 * kp + tt) * 16 + 4 * g + r >= p.Lk) s[tt][r] = 0.f;
+            if (last && key0 + (2 * kp + tt) * 16 + 4 * g + r + 1 >= p.Lk) s[tt][r + 1] = 0.f;
+          }
+        const V8 dsf = pack_pair<E>(s[0], s[1]);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+          acc[dt] = Elem16<E>::mma(img_tr_frag<E>(ks, 2 * kp, 2 * kp + 1, dt * 16, g, li), dsf, acc[dt]);
+      }
+    }
+    if (more) {
+      char* nk = smem + ((c + 1) & 1) * 2 * kLongImg;
+      long_write<E>(st, nk, nk + kLongImg, (c + 1) * kLongC, p.Lk);
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  store_tile<E>(smem + wid * 2048, dqb, p.q_sl, q0, p.Lq, acc, p.scale, lane);
+}
+
+// ---------------------------------------------------------------- backward: dk, dv
+// attn_bwd_dkv_mfma_kernel's step with the key tile's K / V rows and dK^T / dV^T in registers for the whole kernel and
+// Q / dO streamed in chunks together with their -lse * log2e and -delta (0 for rows >= Lq, whose image rows are zero: they
+// contribute exact zeros without a mask).
+constexpr int kLongBufKv = 2 * kLongImg + 2 * kLongC * (int)sizeof(float);   // a buffer: two images and the two statistics rows
+static_assert(kLongW * 2048 <= kLongRing * kLongBufKv, "the output patches alias the chunk buffers");
+
+template <typename E>
+__global__ __launch_bounds__(kLongNT) void attn_long_bwd_dkv_kernel(const AttnParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using V8 = typename Elem16<E>::v8;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int g = lane >> 4, li = lane & 15;
+  const int nblk = (p.Lk + kLongBlk - 1) / kLongBlk;
+  const int bh = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  const int b = bh / p.H, h = bh % p.H;
+  const E* qb = (const E*)p.q + b * p.q_sb + h * p.q_sh;
+  const E* kb = (const E*)p.k + b * p.k_sb + h * p.k_sh;
+  const E* vb = (const E*)p.v + b * p.v_sb + h * p.v_sh;
+  const E* gb = (const E*)p.d_o + b * p.o_sb + h * p.o_sh;
+  E* dkb = (E*)p.dk + b * p.k_sb + h * p.k_sh;
+  E* dvb = (E*)p.dv + b * p.v_sb + h * p.v_sh;
+  const float* lse = p.lse + ((int64_t)b * p.H + h) * p.Lq;
+  const float* delta = p.delta + ((int64_t)b * p.H + h) * p.Lq;
+  const int nch = (p.Lq + kLongC - 1) / kLongC;
+  const int k0 = blk * kLongBlk + wid * 16;
+  const bool active = k0 < p.Lk;
+  const int kj = k0 + li;
+  const int krow = kj < p.Lk ? kj : p.Lk - 1;
+  const int tid = threadIdx.x;
+
+  LongRegs<E> st;
+  float lse_r = 0.f, dl_r = 0.f;
+  auto load_stats = [&](int row0) {                  // one thread per row of the chunk
+    if (tid < kLongC) {
+      const int r = row0 + tid;
+      const int rr = r < p.Lq ? r : p.Lq - 1;
+      lse_r = lse[rr];
+      dl_r = delta[rr];
+    }
+  };
+  auto write_stats = [&](char* buf, int row0) {      // both negated: the step adds them
+    if (tid < kLongC) {
+      float* l2s = reinterpret_cast<float*>(buf + 2 * kLongImg);
+      const bool live = row0 + tid < p.Lq;
+      l2s[tid] = live ? -lse_r * kLog2e : 0.f;
+      l2s[kLongC + tid] = live ? -dl_r : 0.f;
+    }
+  };
+  long_load<E>(st, qb, p.q_sl, gb, p.o_sl, 0, p.Lq);
+  load_stats(0);
+  V8 kf[2], vf[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    kf[kk] = *reinterpret_cast<const V8*>(kb + (int64_t)krow * p.k_sl + kk * 32 + g * 8);
+    vf[kk] = *reinterpret_cast<const V8*>(vb + (int64_t)krow * p.v_sl + kk * 32 + g * 8);
+  }
+  long_write<E>(st, smem, smem + kLongImg, 0, p.Lq);
+  write_stats(smem, 0);
+  __syncthreads();
+
+  const float c2 = p.scale * kLog2e;
+  const f32x2 c2v = {c2, c2};
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  for (int c = 0; c < nch; ++c) {
+    const char* qs = smem + (c & 1) * kLongBufKv;
+    const char* gs = qs + kLongImg;
+    const float* l2s = reinterpret_cast<const float*>(qs + 2 * kLongImg);
+    const float* dls = l2s + kLongC;
+    const bool more = c + 1 < nch;
+    if (more) {
+      long_load<E>(st, qb, p.q_sl, gb, p.o_sl, (c + 1) * kLongC, p.Lq);
+      load_stats((c + 1) * kLongC);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const int nst = (min(kLongC, p.Lq - c * kLongC) + 31) >> 5;
+    if (active) {
+      for (int qp = 0; qp < nst; ++qp) {
+        f32x4 s[2], dp[2];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          s[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+          dp[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk) {
+            s[tt] = Elem16<E>::mma(img_row_frag<E>(qs, (2 * qp + tt) * 16, kk, g, li), kf[kk], s[tt]);
+            dp[tt] = Elem16<E>::mma(img_row_frag<E>(gs, (2 * qp + tt) * 16, kk, g, li), vf[kk], dp[tt]);
+          }
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          const int r0 = (2 * qp + tt) * 16 + 4 * g;
+          const f32x4 l2 = *reinterpret_cast<const f32x4*>(l2s + r0);
+          const f32x4 dl = *reinterpret_cast<const f32x4*>(dls + r0);
+#pragma unroll
+          for (int r = 0; r < 4; r += 2) {
+            const f32x2 x = __builtin_elementwise_fma(f32x2{s[tt][r], s[tt][r + 1]}, c2v, f32x2{l2[r], l2[r + 1]});
+            const f32x2 d = f32x2{dp[tt][r], dp[tt][r + 1]} + f32x2{dl[r], dl[r + 1]};
+            const f32x2 pr = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
+            const f32x2 ds = pr * d;
+            s[tt][r] = pr[0];
+            s[tt][r + 1] = pr[1];
+            dp[tt][r] = ds[0];
+            dp[tt][r + 1] = ds[1];
+          }
+        }
+        const V8 pf = pack_pair<E>(s[0], s[1]);
+        const V8 dsf = pack_pair<E>(dp[0], dp[1]);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          dv[dt] = Elem16<E>::mma(img_tr_frag<E>(gs, 2 * qp, 2 * qp + 1, dt * 16, g, li), pf, dv[dt]);
+          dk[dt] = Elem16<E>::mma(img_tr_frag<E>(qs, 2 * qp, 2 * qp + 1, dt * 16, g, li), dsf, dk[dt]);
+        }
+      }
+    }
+    if (more) {
+      char* nb = smem + ((c + 1) & 1) * kLongBufKv;
+      long_write<E>(st, nb, nb + kLongImg, (c + 1) * kLongC, p.Lq);
+      write_stats(nb, (c + 1) * kLongC);
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  store_tile<E>(smem + wid * 2048, dkb, p.k_sl, k0, p.Lk, dk, p.scale, lane);
+  store_tile<E>(smem + wid * 2048, dvb, p.v_sl, k0, p.Lk, dv, 1.0f, lane);
+}
+
 // ======================================================================= host
 constexpr int kMaxLds = 160 * 1024;
 
@@ -1660,9 +2051,93 @@ int resolve_bwd(const dvt_attn_desc* d, AttnParams& p, AttnParams& pq, AttnParam
   return DVT_OK;
 }
 
+// ---------------------------------------------------------------- streamed kernels
+bool long_ok(const dvt_attn_desc* d, bool bwd) {
+  if (!d) return false;
+  bool ok = d->dropout_p == 0.f && d->scale > 0.f && dvt_is_16bit(d->dtype) && d->dh == DH && strides_vec_ok(d) &&
+            dvt_aligned16(d->q) && dvt_aligned16(d->k) && dvt_aligned16(d->v) && dvt_aligned16(d->o);
+  if (bwd) ok = ok && dvt_aligned16(d->d_o) && dvt_aligned16(d->dq) && dvt_aligned16(d->dk) && dvt_aligned16(d->dv);
+  return ok;
+}
+
+// the decisions of dvt_attention_long_fwd / _bwd, in one place: they launch by them and dvt_attention_long_plan reports them
+int resolve_long(const dvt_attn_desc* d, bool bwd, AttnParams& p, dvt_attn_long_plan_info& r, const char* name) {
+  r = dvt_attn_long_plan_info{};
+  r.patch2 = -1;
+  int rc = fill_params(d, p, bwd, name);
+  if (rc) return rc;
+  if (!long_ok(d, bwd))
+    DVT_UNSUPPORTED("%s: needs a 16-bit type, dh == 64, no dropout, scale > 0, strides that are multiples of 8 and 16-byte "
+                    "aligned pointers (dtype %d, dh %d)", name, (int)d->dtype, (int)d->dh);
+  const int64_t bh = (int64_t)p.B * p.H;
+  const int64_t grid = bh * dvt_cdiv(p.Lq, kLongBlk), grid2 = bh * dvt_cdiv(p.Lk, kLongBlk);
+  if (grid >= (1ll << 31) || grid2 >= (1ll << 31)) DVT_UNSUPPORTED("%s: more than 2^31 workgroups", name);
+  r.q_block = kLongBlk; r.k_chunk = kLongC; r.waves = kLongW; r.ring = kLongRing; r.patch = 1;
+  r.chunks = (int32_t)dvt_cdiv(p.Lk, kLongC);
+  r.grid = grid; r.lds = (int64_t)kLongRing * 2 * kLongImg;
+  if (bwd) {
+    r.k_block = kLongBlk; r.q_chunk = kLongC; r.waves2 = kLongW; r.ring2 = kLongRing; r.patch2 = 1;
+    r.chunks2 = (int32_t)dvt_cdiv(p.Lq, kLongC);
+    r.grid2 = grid2; r.lds2 = (int64_t)kLongRing * kLongBufKv;
+    r.workspace = 1;
+  }
+  return DVT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dvt_attention_long_supported(const dvt_attn_desc* d, int bwd) { return long_ok(d, bwd != 0) ? 1 : 0; }
+
+size_t dvt_attention_long_bwd_workspace_bytes(const dvt_attn_desc* d) {
+  if (!d) return 0;
+  return (size_t)d->B * (size_t)d->H * (size_t)d->Lq * sizeof(float);
+}
+
+int dvt_attention_long_plan(const dvt_attn_desc* d, int bwd, dvt_attn_long_plan_info* info) {
+  DVT_REQUIRE(info, "dvt_attention_long_plan: null info");
+  AttnParams p;
+  return resolve_long(d, bwd != 0, p, *info, "dvt_attention_long_plan");
+}
+
+int dvt_attention_long_fwd(const dvt_attn_desc* d, dvt_stream_t stream) {
+  AttnParams p;
+  dvt_attn_long_plan_info r;
+  int rc = resolve_long(d, false, p, r, "dvt_attention_long_fwd");
+  if (rc) return rc;
+  if (p.B == 0) return DVT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)r.grid), block(64 * r.waves);
+  const size_t lds = (size_t)r.lds;
+  DVT_DISPATCH_16BIT(d->dtype, E, {
+    if (int rc_ = set_lds(attn_long_fwd_kernel<E>, lds)) return rc_;
+    hipLaunchKernelGGL((attn_long_fwd_kernel<E>), grid, block, lds, st, p);
+  });
+  DVT_LAUNCH_CHECK("dvt_attention_long_fwd");
+  return DVT_OK;
+}
+
+int dvt_attention_long_bwd(const dvt_attn_desc* d, dvt_stream_t stream) {
+  AttnParams p;
+  dvt_attn_long_plan_info r;
+  int rc = resolve_long(d, true, p, r, "dvt_attention_long_bwd");
+  if (rc) return rc;
+  if (p.B == 0) return DVT_OK;
+  DVT_REQUIRE(d->workspace, "dvt_attention_long_bwd: workspace (dvt_attention_long_bwd_workspace_bytes) required");
+  p.delta = (float*)d->workspace;                  // dq kernel -> dk/dv kernel
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid_q((unsigned)r.grid), grid_kv((unsigned)r.grid2), block_q(64 * r.waves), block_kv(64 * r.waves2);
+  const size_t lds_q = (size_t)r.lds, lds_kv = (size_t)r.lds2;
+  DVT_DISPATCH_16BIT(d->dtype, E, {
+    if (int rc_ = set_lds(attn_long_bwd_dq_kernel<E>, lds_q)) return rc_;
+    if (int rc_ = set_lds(attn_long_bwd_dkv_kernel<E>, lds_kv)) return rc_;
+    hipLaunchKernelGGL((attn_long_bwd_dq_kernel<E>), grid_q, block_q, lds_q, st, p);
+    hipLaunchKernelGGL((attn_long_bwd_dkv_kernel<E>), grid_kv, block_kv, lds_kv, st, p);
+  });
+  DVT_LAUNCH_CHECK("dvt_attention_long_bwd");
+  return DVT_OK;
+}
 
 size_t dvt_attention_bwd_workspace_bytes(const dvt_attn_desc* d) {
   if (!d) return 0;

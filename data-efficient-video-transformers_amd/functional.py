@@ -660,6 +660,34 @@ def select_first_row(x: Tensor) -> Tensor:
 # ---------------------------------------------------------------------------
 # Attention core on separate q/k/v (cross-modal form; MHA)
 # ---------------------------------------------------------------------------
+# Past 640 keys the 16-bit dh = 64 kernels of ops.attention_fwd / _bwd no longer hold K and V of a head in LDS and the
+# launchers fall to the generic fp32 kernels; the streamed kernels (ops.attention_long_*) take those sequences instead.
+ATTN_LONG = True               # A/B switch: False keeps ops.attention_fwd / _bwd for every length
+_ATTN_LONG_ABOVE = 640         # the lengths whose 16-bit dh = 64 forward is the generic family
+
+
+def _attn_long_route(q, k, v, o, scale, dropout, grads=()):
+    """one query per (b, h) keeps the Q1 kernels; dropout, fp32 and odd head widths keep the generic ones"""
+    if not ATTN_LONG or dropout is not None or k.shape[2] <= _ATTN_LONG_ABOVE or q.shape[2] == 1:
+        return False
+    if grads:
+        do, dq, dk, dv = grads
+        return ops.attention_long_supported(q, k, v, o, scale=scale, do=do, dq=dq, dk=dk, dv=dv)
+    return ops.attention_long_supported(q, k, v, o, scale=scale)
+
+
+def _attention_fwd(q, k, v, o, scale, dropout=None):
+    if _attn_long_route(q, k, v, o, scale, dropout):
+        return ops.attention_long_fwd(q, k, v, o, scale)
+    return ops.attention_fwd(q, k, v, o, scale, dropout)
+
+
+def _attention_bwd(q, k, v, o, lse, do, dq, dk, dv, scale, dropout=None):
+    if _attn_long_route(q, k, v, o, scale, dropout, (do, dq, dk, dv)):
+        return ops.attention_long_bwd(q, k, v, o, lse, do, dq, dk, dv, scale)
+    return ops.attention_bwd(q, k, v, o, lse, do, dq, dk, dv, scale, dropout)
+
+
 class _AttentionCore(torch.autograd.Function):
     """q [B,H,Lq,dh], k/v [B,H,Lk,dh] (arbitrary strides, dh contiguous) ->
     o [B,H,Lq,dh] laid out as [B, Lq, H, dh] in memory ('b n (h d)', vit.py:56)."""
@@ -669,7 +697,7 @@ class _AttentionCore(torch.autograd.Function):
         B, H, Lq, dh = q.shape
         o_mem = torch.empty((B, Lq, H, dh), dtype=q.dtype, device=q.device)
         o = o_mem.permute(0, 2, 1, 3)
-        lse = ops.attention_fwd(q, k, v, o, scale)
+        lse = _attention_fwd(q, k, v, o, scale)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.scale = scale
         return o
@@ -688,7 +716,7 @@ class _AttentionCore(torch.autograd.Function):
         dq = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device)
         dk = torch.empty_strided(k.shape, k.stride(), dtype=k.dtype, device=k.device)
         dv = torch.empty_strided(v.shape, v.stride(), dtype=v.dtype, device=v.device)
-        ops.attention_bwd(q, k, v, o, lse, do_v, dq, dk, dv, ctx.scale)
+        _attention_bwd(q, k, v, o, lse, do_v, dq, dk, dv, ctx.scale)
         return dq, dk, dv, None
 
 
@@ -781,7 +809,7 @@ class _AttnBlock(torch.autograd.Function):
         drop = None
         if attn_dropout > 0.0:                        # nn.MultiheadAttention(dropout=p): Philox mask on the probabilities
             drop = (attn_dropout, _rng.tensor(x.device), _rng.take(S * heads * N * N))
-        lse = ops.attention_fwd(q, k, v, _heads_view(o_mem, seq_first), dh ** -0.5, drop)
+        lse = _attention_fwd(q, k, v, _heads_view(o_mem, seq_first), dh ** -0.5, drop)
         if _attn_tap is not None:
             _attn_tap.append(AttnTap("dense", q, k, lse, heads, dh, seq_first, qkv, None))
         ctx.drop = drop
@@ -824,7 +852,7 @@ class _AttnBlock(torch.autograd.Function):
         q, k, v = _split_qkv(qkv, S, N, heads, dh, seq_first)
         dqkv = torch.empty_like(qkv)
         dq, dk, dv = _split_qkv(dqkv, S, N, heads, dh, seq_first)
-        ops.attention_bwd(q, k, v, _heads_view(o_mem, seq_first), lse,
+        _attention_bwd(q, k, v, _heads_view(o_mem, seq_first), lse,
                           _heads_view(do2.view(o_mem.shape), seq_first), dq, dk, dv, dh ** -0.5, ctx.drop)
         dwq, dbq, dxn = _linear_bwd(ctx.sinks[2], ctx.sinks[5], dqkv, xn, wq, has_qkv_bias)                    # dxn [M, d]
         dg = db = None
@@ -908,7 +936,7 @@ class _AttnBlockCls(torch.autograd.Function):
         kv5 = kv.view(S, N, 2, heads, dh)
         k4, v4 = kv5[:, :, 0].permute(0, 2, 1, 3), kv5[:, :, 1].permute(0, 2, 1, 3)
         o = torch.empty((S, inner), dtype=T, device=x.device)
-        lse = ops.attention_fwd(q.view(S, 1, heads, dh).permute(0, 2, 1, 3), k4, v4,
+        lse = _attention_fwd(q.view(S, 1, heads, dh).permute(0, 2, 1, 3), k4, v4,
                                 o.view(S, 1, heads, dh).permute(0, 2, 1, 3), dh ** -0.5)
         if _attn_tap is not None:
             _attn_tap.append(AttnTap("cls", q.view(S, 1, heads, dh).permute(0, 2, 1, 3), k4, lse, heads, dh, False, kv, None))
@@ -973,7 +1001,7 @@ class _AttnBlockCls(torch.autograd.Function):
         dkv = torch.empty_like(kv)
         dkv5 = dkv.view(S, N, 2, heads, dh)
         one = lambda t: t.view(S, 1, heads, dh).permute(0, 2, 1, 3)
-        ops.attention_bwd(one(q), k4, v4, one(o), lse, one(do), one(dq),
+        _attention_bwd(one(q), k4, v4, one(o), lse, one(do), one(dq),
                           dkv5[:, :, 0].permute(0, 2, 1, 3), dkv5[:, :, 1].permute(0, 2, 1, 3), dh ** -0.5)
         xn0 = xn.view(S, N, d)[:, 0]
         w_q, w_kv = wqkv[:inner], wqkv[inner:]
@@ -1040,7 +1068,7 @@ class _CrossAttnBlock(torch.autograd.Function):
         kv5 = kv.view(B, Lk, 2, heads, dh)
         k4, v4 = kv5[:, :, 0].permute(0, 2, 1, 3), kv5[:, :, 1].permute(0, 2, 1, 3)
         o_mem = torch.empty((B, Lq, heads, dh), dtype=T, device=x.device)
-        lse = ops.attention_fwd(q4, k4, v4, o_mem.permute(0, 2, 1, 3), dh ** -0.5)
+        lse = _attention_fwd(q4, k4, v4, o_mem.permute(0, 2, 1, 3), dh ** -0.5)
         y = ops.linear_fwd(o_mem.view(B * Lq, inner), wo, _f32(b_out), epilogue=L.EPI_RESIDUAL, residual=x2)
         ctx.save_for_backward(x2, c2, gq, gk, mq, rq, mk, rk, xn, cn, wq, wkv, wo, q, kv, o_mem, lse)
         ctx.cfg = (B, Lq, Lk, heads, dh, inner, tuple(x.shape), tuple(c.shape), c.dtype)
@@ -1062,7 +1090,7 @@ class _CrossAttnBlock(torch.autograd.Function):
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv)
         dkv5 = dkv.view(B, Lk, 2, heads, dh)
-        ops.attention_bwd(q4, k4, v4, o_mem.permute(0, 2, 1, 3), lse, do2.view(o_mem.shape).permute(0, 2, 1, 3),
+        _attention_bwd(q4, k4, v4, o_mem.permute(0, 2, 1, 3), lse, do2.view(o_mem.shape).permute(0, 2, 1, 3),
                           dq.view(B, Lq, heads, dh).permute(0, 2, 1, 3), dkv5[:, :, 0].permute(0, 2, 1, 3),
                           dkv5[:, :, 1].permute(0, 2, 1, 3), dh ** -0.5)
         dwq = _emit_wgrad(s[4], dq, xn)

@@ -15,3 +15,5 @@ from . import evaluator  # noqa: F401,E402
 from .evaluator import SSLEvaluator  # noqa: F401,E402
 from . import mae  # noqa: F401,E402
 from .mae import MaskedClipAutoencoder  # noqa: F401,E402
+from . import joint_vivit  # noqa: F401,E402
+from .joint_vivit import JointViViT  # noqa: F401,E402

@@ -1184,6 +1184,106 @@ def attention_plan(q: Tensor, k: Tensor, v: Tensor, o: Tensor, *, bwd: bool = Fa
                     bool(r.workspace), r.lds, r.lds2)
 
 
+# ------------------------------------------------------------------ streamed attention (attn_long_*: any length, dh = 64)
+def _attn_long_desc(q, k, v, o, lse, scale, do=None, dq=None, dk=None, dv=None) -> L.AttnDesc:
+    d = _attn_desc(q, k, v, o, lse, scale)
+    if do is not None:
+        d.d_o, d.dq, d.dk, d.dv = do.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    return d
+
+
+def attention_long_supported(q: Tensor, k: Tensor, v: Tensor, o: Tensor, *, scale: Optional[float] = None,
+                             dropout_p: float = 0.0, do: Optional[Tensor] = None, dq: Optional[Tensor] = None,
+                             dk: Optional[Tensor] = None, dv: Optional[Tensor] = None) -> bool:
+    """Do the streamed kernels take these views (dvt_attention_long_supported: 16-bit, dh == 64, no dropout, scale > 0,
+    strides multiples of 8, 16-byte aligned)?  With `do` the gradient views count too (default: their primals')."""
+    d = _attn_desc(q, k, v, o, o, q.shape[3] ** -0.5 if scale is None else float(scale))
+    if dropout_p:
+        d.dropout_p, d.rng_state = float(dropout_p), 256
+    bwd = do is not None
+    if bwd:
+        dq, dk, dv = (q if dq is None else dq), (k if dk is None else dk), (v if dv is None else dv)
+        d.d_o, d.dq, d.dk, d.dv = do.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    return bool(L.load().dvt_attention_long_supported(C.byref(d), int(bwd)))
+
+
+def attention_long_fwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, scale: float, lse: Optional[Tensor] = None) -> Tensor:
+    """``attention_fwd`` on the streamed kernels: writes o, returns lse [B,H,Lq] f32 (the same definition)."""
+    _need_cuda(q, k, v, o)
+    B, H, Lq, _ = q.shape
+    if lse is None:
+        lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+    else:
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() == B * H * Lq and lse.device == q.device
+    d = _attn_long_desc(q, k, v, o, lse, scale)
+    nb = (2 * q.numel() + k.numel() + v.numel()) * q.element_size()
+    with _timed(("hbm", "attention_long_fwd", q.numel(), 4.0 * q.numel() * k.shape[2]), nb):
+        L.check(L.load().dvt_attention_long_fwd(C.byref(d), _stream()), "dvt_attention_long_fwd")
+    return lse
+
+
+def attention_long_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, lse: Tensor, do: Tensor, dq: Tensor,
+                       dk: Tensor, dv: Tensor, scale: float, ws: Optional[Tensor] = None) -> None:
+    """``attention_bwd`` on the streamed kernels (dq launch, then dk/dv; the same layout rules)."""
+    _need_cuda(q, k, v, o, do, dq, dk, dv)
+    for a, b in ((do, o), (dq, q), (dk, k), (dv, v)):
+        assert a.shape == b.shape and all(sa == sb for sa, sb, n in zip(a.stride(), b.stride(), a.shape) if n > 1), \
+            "gradient views must share the layout of their primal"
+    d = _attn_long_desc(q, k, v, o, lse, scale, do, dq, dk, dv)
+    lib = L.load()
+    need = lib.dvt_attention_long_bwd_workspace_bytes(C.byref(d))
+    if ws is None:
+        ws = workspace(need, q.device)
+    else:
+        assert ws.device == q.device and ws.numel() * ws.element_size() >= need
+    d.workspace = _p(ws)
+    nb = (4 * q.numel() + 2 * k.numel() + 2 * v.numel()) * q.element_size()
+    with _timed(("hbm", "attention_long_bwd", q.numel(), 10.0 * q.numel() * k.shape[2]), nb):
+        L.check(lib.dvt_attention_long_bwd(C.byref(d), _stream()), "dvt_attention_long_bwd")
+
+
+class AttnLongPlan(NamedTuple):
+    """What one dvt_attention_long_fwd / _bwd call launches (dvt_attention_long_plan).  Of the forward or dq launch: query
+    rows per workgroup, keys per LDS chunk, waves, chunk buffers, chunks streamed, workgroups, dynamic LDS bytes and whether
+    tiles go out as whole rows through LDS patches; of the dk/dv launch (backward only, else 0 / None): key rows per
+    workgroup, queries per chunk and the same."""
+    q_block: int
+    k_chunk: int
+    waves: int
+    ring: int
+    chunks: int
+    grid: int
+    lds: int
+    patch: bool
+    k_block: int = 0
+    q_chunk: int = 0
+    waves2: int = 0
+    ring2: int = 0
+    chunks2: int = 0
+    grid2: int = 0
+    lds2: int = 0
+    patch2: Optional[bool] = None
+    workspace: bool = False
+
+
+def attention_long_plan(q: Tensor, k: Tensor, v: Tensor, o: Tensor, *, bwd: bool = False, do: Optional[Tensor] = None,
+                        dq: Optional[Tensor] = None, dk: Optional[Tensor] = None, dv: Optional[Tensor] = None,
+                        dropout_p: float = 0.0, scale: Optional[float] = None) -> AttnLongPlan:
+    """What ``attention_long_fwd`` (or, bwd=True, ``attention_long_bwd``) launches for these views; raises what the
+    launcher raises for views it refuses.  No launch, no device needed."""
+    d = _attn_desc(q, k, v, o, o, q.shape[3] ** -0.5 if scale is None else float(scale))
+    if dropout_p:
+        d.dropout_p, d.rng_state = float(dropout_p), 256
+    if bwd:
+        do, dq, dk, dv = (o if do is None else do), (q if dq is None else dq), (k if dk is None else dk), (v if dv is None else dv)
+        d.d_o, d.dq, d.dk, d.dv = do.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    r = L.AttnLongPlanInfo()
+    L.check(L.load().dvt_attention_long_plan(C.byref(d), int(bwd), C.byref(r)), "dvt_attention_long_plan")
+    opt = lambda x: None if x < 0 else bool(x)
+    return AttnLongPlan(r.q_block, r.k_chunk, r.waves, r.ring, r.chunks, r.grid, r.lds, bool(r.patch), r.k_block, r.q_chunk,
+                        r.waves2, r.ring2, r.chunks2, r.grid2, r.lds2, opt(r.patch2), bool(r.workspace))
+
+
 # ------------------------------------------------------------------ single-query attention, K / V projections folded
 def _attn_cls_desc(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, H: int) -> L.AttnClsDesc:
     """x [S, N, d] (16-bit), last dim contiguous."""

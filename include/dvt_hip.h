@@ -602,6 +602,39 @@ typedef struct dvt_attn_plan_info {
 } dvt_attn_plan_info;
 int dvt_attention_plan(const dvt_attn_desc* desc, int bwd, dvt_attn_plan_info* info);
 
+/* Streamed MFMA attention: the same computation on the same descriptor for sequences of any length (csrc/attention.hip,
+ * attn_long_*).  A workgroup owns a block of query rows (forward, dq) or key rows (dk/dv) of one (batch, head) and the other
+ * side passes through LDS in double-buffered chunks, so neither length is bounded by LDS; lse keeps its definition, so
+ * either backward can follow either forward.  16-bit types, dh == 64, dropout_p == 0, scale > 0, strides that are multiples
+ * of 8 and 16-byte aligned pointers: dvt_attention_long_supported (host only; bwd != 0 includes the gradient pointers)
+ * returns 1 for such a descriptor and 0 otherwise, and the launchers refuse what it refuses with DVT_ERR_UNSUPPORTED.  The
+ * backward is two launches (dq, which writes delta = rowsum(dO * O) to the workspace, then dk/dv), without atomics, bitwise
+ * reproducible; bwd_two_pass is ignored.  dvt_attention_long_plan (host only) reports the launchers' decisions. */
+typedef struct dvt_attn_long_plan_info {
+  int32_t q_block;    /* fwd / dq launch: query rows per workgroup */
+  int32_t k_chunk;    /* fwd / dq launch: keys per LDS chunk (a multiple of 32) */
+  int32_t waves;      /* fwd / dq launch: waves per workgroup */
+  int32_t ring;       /* fwd / dq launch: chunk buffers in LDS */
+  int32_t patch;      /* fwd / dq launch: 1 = output tiles stored as whole rows through LDS patches */
+  int32_t k_block;    /* bwd, dk/dv launch: key rows per workgroup; else 0 */
+  int32_t q_chunk;    /* bwd, dk/dv launch: queries per LDS chunk; else 0 */
+  int32_t waves2;     /* bwd, dk/dv launch; else 0 */
+  int32_t ring2;      /* bwd, dk/dv launch; else 0 */
+  int32_t patch2;     /* bwd, dk/dv launch; else -1 */
+  int32_t workspace;  /* 1 if the launch reads and writes desc->workspace */
+  int32_t chunks;     /* fwd / dq launch: chunks each workgroup streams */
+  int32_t chunks2;    /* bwd, dk/dv launch; else 0 */
+  int64_t grid;       /* workgroups of the fwd / dq launch */
+  int64_t grid2;      /* of the dk/dv launch; else 0 */
+  int64_t lds;        /* dynamic LDS bytes of the fwd / dq launch */
+  int64_t lds2;       /* of the dk/dv launch; else 0 */
+} dvt_attn_long_plan_info;
+int dvt_attention_long_supported(const dvt_attn_desc* desc, int bwd);
+size_t dvt_attention_long_bwd_workspace_bytes(const dvt_attn_desc* desc);
+int dvt_attention_long_fwd(const dvt_attn_desc* desc, dvt_stream_t stream);
+int dvt_attention_long_bwd(const dvt_attn_desc* desc, dvt_stream_t stream);
+int dvt_attention_long_plan(const dvt_attn_desc* desc, int bwd, dvt_attn_long_plan_info* info);
+
 /* ---------------------------------------------------------------- single-query attention with folded K / V projections
  * The reference reads only row 0 of the space transformer's output (src/models/vit.py:119-120; :126 for the temporal
  * one under pool == 'cls'), so the attention of a stack's LAST layer (vit.py:46-58) has ONE query per (sequence, head),
